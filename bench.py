@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Headline benchmark: BLS12-381 G1 MSM at n = 2^26 (pf = 1) on MI355X, plus the 2^27 NTT latency.
+"""Headline benchmark: BLS12-381 G1 MSM at n = 2^26 (pf = 1) on MI355X; with --full also the 2^27 NTT latency and the rest.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one complete MSM over the 2^26 synthetic (scalar, point) pairs, inputs already resident
@@ -18,7 +18,7 @@ every rank adds them in rank order.  value = MSMs per second, whole job.
 N > 1 cannot hang: the timed loop exchanges the partials through torch.distributed (the process group
 the launcher's rendezvous already brought up); the exchange inside the library (blz_msm_comm_init /
 blz_msm_all_gather_combine: a second RCCL communicator on the handle's own stream) is tried AFTER the
-headline is measured and reported as the extra key `exchange_native`; every bring-up and every phase
+headline is measured (--full) and reported as the extra key `exchange_native`; every bring-up and every phase
 runs under a deadline, and a rank whose deadline expires prints what it was waiting for and exits
 non-zero (an exit, never a re-exec) - unless the headline is already measured and checked: a deadline
 that expires in one of the EXTRA legs prints the line without the remaining extras (`extras_aborted`
@@ -27,10 +27,16 @@ names the leg) and exits 0.
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts the N ranks itself (a child
 `torch.distributed.run`, before this process touches the GPU) and relays their output.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` for the dominant
-kernel (k_accumulate) and `cpu_baseline` (the CPU oracle's Pippenger on a bounded sample).  The last
-timed result is CHECKED before anything is printed (`result_check`): the synthetic points are
-P_i = (i + 1) G, so the MSM must equal (sum_i s_i (i + 1) mod r) G; a mismatch raises."""
+Rank 0 prints ONE JSON line: `value` (MSMs per second), `ms_per_step` and `roofline` for the dominant
+kernel (k_accumulate, from the timed steps' own event timers).  A plain run sets up, warms up, times
+the K steps and prints; --dump-outputs DIR also writes the last timed step's result to
+DIR/msm_result.npy (the inputs are fixed by their seeds, so two builds compare output for output).
+Everything else runs behind --full, after the headline is measured: the result check
+(`result_check`: the synthetic points are P_i = (i + 1) G, so the MSM must equal
+(sum_i s_i (i + 1) mod r) G; a mismatch raises), the clock record and multiply-add calibration
+(`clock`, `roofline.integer_issue`), and the extra legs of bench_extras.py (`ntt_2e27`, the configs,
+`cpu_baseline`: the CPU oracle's Pippenger on a bounded sample ...); keys of legs that did not run
+are null."""
 import argparse
 import ctypes as C
 import json
@@ -118,7 +124,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="skip the result check (profiling runs only)")
     ap.add_argument("--no-extras", action="store_true", help="skip the reference-semantics legs (hbm_flow, config2_dma)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the result check, the clock and multiply-add calibration, the NTT, the configs and "
+                         "the CPU baselines (a plain run times the headline steps only; the --no-* flags narrow a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's MSM result to DIR/msm_result.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -285,16 +298,24 @@ def main():
     wd.arm(t_run, f"warm-up + {args.steps} timed steps")
     run_steps(args.warmup)
     fence()
-    sclk = SclkSampler(torch, dev)
-    sclk.start()
+    sclk = SclkSampler(torch, dev) if args.full else None
+    if sclk is not None:
+        sclk.start()
     gc.disable()
     t0 = time.perf_counter()
     done = run_steps(args.steps)
     fence()
     dt = time.perf_counter() - t0
     gc.enable()
-    sclk_rec = sclk.stop()
+    sclk_rec = sclk.stop() if sclk is not None else None
     res, api = done[-1]
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the result bytes of the last timed MSM (Z | Y | X, 48 little-endian bytes each;
+        # Z = 1 for an affine point), one float64 per byte so that two builds compare exactly
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "msm_result.npy"), np.frombuffer(bytes(res), dtype=np.uint8).astype(np.float64).reshape(3, -1))
     accum_ms = [a["accumulate_kernel_ms"] for _, a in done]
     total_ms = [a["total_ms"] for _, a in done]
     if multi:
@@ -303,21 +324,22 @@ def main():
         dt = float(t.item())
     wd.disarm()
     # the multiply-add issue rate of THIS chip at its clocks of this moment (50 ms of independent v_mad_u64_u32
-    # chains on every SIMD, right behind the timed steps): what roofline.integer_issue is priced against
+    # chains on every SIMD, right behind the timed steps): what roofline.integer_issue is priced against (--full)
     calib = None
-    try:
-        cal = (C.c_double * 4)()
-        check(blaze_amd.aux().blz_calib_mad_rate(dev, 50, cal))
-        calib = {"mad_lane_ops_per_s": cal[0], "kernel_ms": round(cal[1], 3), "nominal_clock_mhz": cal[2]}
-    except Exception as e:   # noqa: BLE001 - a measurement aid, never fatal
-        print(f"[bench rank {rank}] mad-rate calibration failed: {e}", file=sys.stderr, flush=True)
+    if args.full:
+        try:
+            cal = (C.c_double * 4)()
+            check(blaze_amd.aux().blz_calib_mad_rate(dev, 50, cal))
+            calib = {"mad_lane_ops_per_s": cal[0], "kernel_ms": round(cal[1], 3), "nominal_clock_mhz": cal[2]}
+        except Exception as e:   # noqa: BLE001 - a measurement aid, never fatal
+            print(f"[bench rank {rank}] mad-rate calibration failed: {e}", file=sys.stderr, flush=True)
     ms_per_step = dt / args.steps * 1e3
     value = args.steps / dt
 
     # ---- the number is only worth printing if the timed result is right: linearity over P_i = (i + 1) G
     # (oracle = test infrastructure, used here as the checker only, outside the timed region)
     check_rec = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         if rank == 0:
             import oracle
 
@@ -379,7 +401,7 @@ def main():
     # non-zero window digit (255-bit scalars in 12 occupied windows at this size).  The peak is that instruction's
     # rate on THIS chip, measured by the calibration kernel right behind the timed steps (blz_calib_mad_rate); the
     # constant of the builder's boxes (3.1e13, profiles/r02_mul_variants.txt) is kept beside it for comparison.
-    if CURVE in ("BLS381", "BLS377") and LOG_N >= 24:
+    if args.full and CURVE in ("BLS381", "BLS377") and LOG_N >= 24:
         occupied = -(-(255 if CURVE == "BLS381" else 253) // int(api["window_bits"]))
         if ranged:   # every window of a 64 / 128-bit range holds digits (the top one fewer: counted whole, an upper bound)
             occupied = -(-(min(lay["bit_hi"], 255 if CURVE == "BLS381" else 253) - lay["bit_lo"]) // int(api["window_bits"]))
@@ -438,27 +460,28 @@ def main():
         return line
 
     wd.fallback = make_line   # (from here on a hung extra leg costs the extras only)
-    if os.environ.get("BLAZE_BENCH_TEST_STALL_EXTRAS") == "1":   # (tests: an extra leg that never comes back)
-        wd.arm(2, "test stall in the extras")
-        time.sleep(3600)
 
-    # ---- everything below is an EXTRA leg (bench_extras.py): measured after the headline line is in hand, reported under its own key,
-    # never the headline value; a deadline that expires in one of them costs the remaining extras only (wd.fallback)
-    import types
+    # ---- everything below is an EXTRA leg (bench_extras.py, --full only): measured after the headline line is in hand, reported under
+    # its own key, never the headline value; a deadline that expires in one of them costs the remaining extras only (wd.fallback)
+    if args.full:
+        if os.environ.get("BLAZE_BENCH_TEST_STALL_EXTRAS") == "1":   # (tests: an extra leg that never comes back)
+            wd.arm(2, "test stall in the extras")
+            time.sleep(3600)
+        import types
 
-    ctx = types.SimpleNamespace(args=args, rank=rank, world=world, multi=multi, dist=dist, torch=torch, tdev=tdev, dev=dev, gather_dev=gather_dev, wd=wd,
-                                client=client, params=params, d_sc=d_sc, d_pts=d_pts, queue=queue, lay=lay, ranged=ranged, n=n, n_loc=n_loc, cid=cid, res=res,
-                                last_partial=last_partial, hbm_mode=hbm_mode, calib=calib, L=L, tf=tf, CURVE=CURVE, LOG_N=LOG_N, NTT_LOG=NTT_LOG,
-                                HBM_PEAK_GBS=HBM_PEAK_GBS, ntt=None)
-    native = extras.native_exchange(ctx)
-    table_rec = extras.window_table_leg(ctx)
-    alt_rec, hbm_flow = extras.multi_rank_legs(ctx)
-    hbm_flow_1, cfg2 = extras.reference_flows(ctx)
-    if hbm_flow_1 is not None:
-        hbm_flow = hbm_flow_1
-    cfg3, cfg4, lone_small = extras.configs_3_4_and_small(ctx)
-    ntt = ctx.ntt = extras.ntt_leg(ctx)
-    cpu, cpu_ref = extras.cpu_baselines(ctx)
+        ctx = types.SimpleNamespace(args=args, rank=rank, world=world, multi=multi, dist=dist, torch=torch, tdev=tdev, dev=dev, gather_dev=gather_dev, wd=wd,
+                                    client=client, params=params, d_sc=d_sc, d_pts=d_pts, queue=queue, lay=lay, ranged=ranged, n=n, n_loc=n_loc, cid=cid,
+                                    res=res, last_partial=last_partial, hbm_mode=hbm_mode, calib=calib, L=L, tf=tf, CURVE=CURVE, LOG_N=LOG_N,
+                                    NTT_LOG=NTT_LOG, HBM_PEAK_GBS=HBM_PEAK_GBS, ntt=None)
+        native = extras.native_exchange(ctx)
+        table_rec = extras.window_table_leg(ctx)
+        alt_rec, hbm_flow = extras.multi_rank_legs(ctx)
+        hbm_flow_1, cfg2 = extras.reference_flows(ctx)
+        if hbm_flow_1 is not None:
+            hbm_flow = hbm_flow_1
+        cfg3, cfg4, lone_small = extras.configs_3_4_and_small(ctx)
+        ntt = ctx.ntt = extras.ntt_leg(ctx)
+        cpu, cpu_ref = extras.cpu_baselines(ctx)
 
     if rank == 0:
         line = make_line()

@@ -595,7 +595,7 @@ def test_bench_sharded_path_two_ranks_one_gpu(gpu, shard):
     if shard != "auto":
         env["BLAZE_SHARD"] = shard       # "bits": two ranks split the scalars' bits of all the elements, whatever the planner thinks
     root = os.path.dirname(HERE)
-    common = ["--steps", "1", "--warmup", "0", "--no-ntt", "--no-cpu-baseline"]
+    common = ["--steps", "1", "--warmup", "0", "--full", "--no-ntt", "--no-cpu-baseline"]
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + common, env=env,
                          capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -639,7 +639,7 @@ def test_bench_eight_ranks_rehearsal_one_gpu(gpu, shard):
     if shard != "auto":
         env["BLAZE_SHARD"] = shard
     root = os.path.dirname(HERE)
-    common = ["--steps", "2", "--warmup", "1", "--no-ntt", "--no-cpu-baseline"]
+    common = ["--steps", "2", "--warmup", "1", "--full", "--no-ntt", "--no-cpu-baseline"]
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--no-extras"] + common, env=env,
                          capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -677,7 +677,7 @@ def test_bench_native_exchange_next_to_torch_process_group(gpu):
     env = dict(os.environ, BLAZE_BENCH_LOGN="18", BLAZE_BENCH_EMIT_RESULT="1", MASTER_ADDR="127.0.0.1",
                HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     root = os.path.dirname(HERE)
-    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--no-ntt", "--no-cpu-baseline", "--no-extras"]
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-ntt", "--no-cpu-baseline", "--no-extras"]
     plain = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, env=env, capture_output=True, text=True, timeout=600)
     assert plain.returncode == 0, plain.stderr[-2000:]
     forced = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
@@ -1445,7 +1445,7 @@ def test_bench_a_hung_extra_leg_costs_the_extras_only(gpu):
 
     env = dict(os.environ, BLAZE_BENCH_LOGN="16", BLAZE_BENCH_TEST_STALL_EXTRAS="1")
     root = os.path.dirname(HERE)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -1453,6 +1453,35 @@ def test_bench_a_hung_extra_leg_costs_the_extras_only(gpu):
     assert j["value"] > 0 and j["result_check"]["ok"] and j["roofline"]["kernel_ms"] > 0
     assert "test stall" in j["extras_aborted"] and j["window_table"] is None and j["ntt_2e27"] is None
     assert "DEADLINE" in r.stderr
+
+
+def test_bench_plain_run_and_dumped_outputs(gpu, tmp_path):
+    """A plain bench.py run times exactly --steps steps and prints the line without the legs behind --full (result check,
+    calibration, NTT, CPU baselines); --dump-outputs writes the last timed result, the same bytes a --full run checks against
+    the oracle."""
+    import subprocess
+    import sys
+
+    env = dict(os.environ, BLAZE_BENCH_LOGN="16", BLAZE_BENCH_EMIT_RESULT="1")
+    bench = os.path.join(os.path.dirname(HERE), "bench.py")
+    r = subprocess.run([sys.executable, bench, "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "plain")], env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and abs(j["value"] * j["ms_per_step"] / 1e3 - 1) < 1e-2
+    assert j["unit"] == "MSM/s" and j["higher_is_better"] is True and j["roofline"]["kernel_ms"] > 0
+    assert j["result_check"] is None and j["ntt_2e27"] is None and j["cpu_baseline"] is None and j["clock"]["mad_calibration"] is None
+    out = np.load(tmp_path / "plain" / "msm_result.npy")
+    assert out.dtype == np.float64 and out.shape == (3, 48)
+    assert bytes(out.astype(np.uint8).ravel()) == bytes.fromhex(j["result_hex"])
+    f = subprocess.run([sys.executable, bench, "--steps", "2", "--warmup", "1", "--full", "--no-ntt", "--no-cpu-baseline", "--no-extras",
+                        "--dump-outputs", str(tmp_path / "full")], env=env, capture_output=True, text=True, timeout=600)
+    assert f.returncode == 0, f.stderr[-2000:]
+    jf = json.loads([l for l in f.stdout.splitlines() if l.startswith("{")][-1])
+    assert jf["result_check"]["ok"] and jf["result_hex"] == j["result_hex"]
+    assert np.array_equal(np.load(tmp_path / "full" / "msm_result.npy"), out)
 
 
 def test_a_full_device_is_an_error_not_a_crash(gpu):
