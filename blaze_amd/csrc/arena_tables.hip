@@ -479,11 +479,12 @@ bool wants_table(const blz_msm* h) {
 // would otherwise flip the arithmetic - and with it the format of the extent's copy - from task to task).  BLAZE_MSM_PLAN
 // pc_repr=0|1 forces one (tests).
 //
-// The arithmetic is chosen PER TASK (task_repr_bn254pc below, from the path the task takes), and changed only while nothing of the
-// handle is in flight: the engine's shared workspace and the extent's Montgomery copy are in ONE format at a time, and a change
-// costs a device drain and a reconversion of the copy.  A task launched beside one in flight therefore keeps the arithmetic of
-// the one in flight - every path is correct on either arithmetic (same bytes: tests/test_gpu_msm_precompute.py), only the speed
-// differs - and the choice is made again by the first task that finds the handle idle.
+// The arithmetic is chosen PER TASK (task_repr_bn254pc below, from the path the task takes), and changed only while no engine slot of
+// the handle is taken (busy(): a task in flight, or one being fed piece by piece): the engine's shared workspace and the extent's
+// Montgomery copy are in ONE format at a time, and a change costs a device drain and a reconversion of the copy.  A task launched
+// beside one in flight therefore keeps the arithmetic of the one in flight - every path is correct on either arithmetic (same
+// bytes: tests/test_gpu_msm_precompute.py), only the speed differs - and the choice is made again by the first task that finds the
+// handle idle.
 int plan_repr_bn254(uint64_t nelem) {
     const int forced = plan_override("pc_repr", -1);
     if (forced == 0 || forced == 1) return forced;
@@ -491,16 +492,17 @@ int plan_repr_bn254(uint64_t nelem) {
 }
 
 void task_repr_bn254pc(blz_msm* h, bool on_plan, uint64_t checked_elems) {
-    if (h->curve != BLZ_BN254 || h->pf != BLZ_PRECOMPUTE_FACTOR || !h->in_flight.empty()) return;
+    if (h->curve != BLZ_BN254 || h->pf != BLZ_PRECOMPUTE_FACTOR || busy(h)) return;
     h->eng.repr = exp_knob("BLAZE_BN254_REPR", on_plan ? plan_repr_bn254(checked_elems) : 1) ? 1 : 0;
 }
 
 // Which task serves `n` elements whose bases sit in the arena at `pos`: a precompute handle on the checked-table plan whose
 // table is consistent sums 4n even bases over 64-bit chunks; a pf = 1 handle with a window table in place gathers from it;
-// everything else is the plain task over the Montgomery copy.  Resolves h->d_points_mont (shadow pointers are resolved when
+// everything else is the plain task over the Montgomery copy.  Resolves *pts (shadow pointers are resolved when
 // the task is launched, not when its data was staged: a load by another handle in between may have moved or re-converted
 // the extent).
-int resolve_arena_task(blz_msm* h, uint64_t pos, uint32_t n, bool allow_table, bool allow_plan, uint32_t* npts, int* sbits, int* table_c) {
+int resolve_arena_task(blz_msm* h, uint64_t pos, uint32_t n, bool allow_table, bool allow_plan, uint32_t* npts, int* sbits, int* table_c,
+                       const void** pts) {
     *npts = n * h->pf;
     *sbits = h->pf == 1 ? 256 : 32;
     *table_c = 0;
@@ -516,7 +518,7 @@ int resolve_arena_task(blz_msm* h, uint64_t pos, uint32_t n, bool allow_table, b
             const void* even = nullptr;
             BLZ_TRY(arena_points_mont(h, pos, n * 8, &even, true));
             if (even) {
-                h->d_points_mont = even;
+                *pts = even;
                 *npts = n * 4;
                 *sbits = 64;
                 h->pc_info[0] = 1;
@@ -532,10 +534,10 @@ int resolve_arena_task(blz_msm* h, uint64_t pos, uint32_t n, bool allow_table, b
     if (allow_table && wants_table(h)) {
         const void* tab = nullptr;
         BLZ_TRY(arena_points_table(h, pos, *npts, &tab, table_c, TABLE_CHUNKS_PER_TASK));
-        if (tab) h->d_points_mont = tab;
+        if (tab) *pts = tab;
         else *table_c = 0;
     }
-    if (!*table_c) BLZ_TRY(arena_points_mont(h, pos, *npts, &h->d_points_mont));
+    if (!*table_c) BLZ_TRY(arena_points_mont(h, pos, *npts, pts));
     return BLZ_OK;
 }
 

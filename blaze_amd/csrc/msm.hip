@@ -762,6 +762,7 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
     S.ranged = ranged;
     S.bit_lo = bit_lo;
     S.bit_hi = bit_hi;
+    S.repr = repr;
     S.slices = nslices;
     S.pts_per_slice = nslices > 1 ? per : npts;
     S.max_units = max_units;
@@ -883,6 +884,7 @@ int MsmEngine::accumulate_slice(int slot, int sl, const void* d_pts) {
     BLZ_TRY(use_device(device));
     if (slot < 0 || slot >= MSM_QUEUE_DEPTH || !slots[slot].open) return fail(BLZ_ERR_INVALID_PARAM, "slot %d has no task being enqueued", slot);
     MsmSlot& S = slots[slot];
+    if (S.repr != repr) return fail(BLZ_ERR_INVALID_PARAM, "the handle's arithmetic changed while task %d was being enqueued", slot);
     const MsmCurveOps* ops = ops_for(curve, repr);
     cur = slot;
     last_plan = S.plan;
@@ -903,6 +905,7 @@ int MsmEngine::end(int slot) {
     BLZ_TRY(use_device(device));
     if (slot < 0 || slot >= MSM_QUEUE_DEPTH || !slots[slot].open) return fail(BLZ_ERR_INVALID_PARAM, "slot %d has no task being enqueued", slot);
     MsmSlot& S = slots[slot];
+    if (S.repr != repr) return fail(BLZ_ERR_INVALID_PARAM, "the handle's arithmetic changed while task %d was being enqueued", slot);
     const MsmCurveOps* ops = ops_for(curve, repr);
     cur = slot;
     last_plan = S.plan;

@@ -156,7 +156,7 @@ int blz_msm_prepare_precompute_plan(blz_msm* h, uint32_t nof_elements, uint64_t 
     bool ok = false;
     uint64_t checked = nof_elements;
     BLZ_TRY(arena_precompute_check(h, hbm_addr + hbm_off, nof_elements, &ok, &checked));
-    if (ok && h->in_flight.empty()) {
+    if (ok && !busy(h)) {
         // the even-base copy too, so that the first task finds it in place
         task_repr_bn254pc(h, true, checked);
         const void* p = nullptr;
@@ -198,6 +198,8 @@ int blz_msm_initialize(blz_msm* h, uint32_t nof_elements, int has_hbm, uint64_t 
     if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
     BLZ_LIVE(h);
     (void)hbm_off;  // msm_api.rs:84: only hbm_point_addr.0 is programmed
+    if (h->feed.open)   // (the task being fed keeps the element count it was opened with)
+        return fail(BLZ_ERR_INVALID_PARAM, "initialize: the queued task has received %u of its %u elements", h->feed.received, h->feed.n);
     if (h->mem_type == BLZ_DMA && !has_hbm) {
         h->bases_from_hbm = false;  // BASES_SOURCE = 0 (msm_api.rs:75-81)
     } else {
@@ -215,32 +217,25 @@ int blz_msm_start_process(blz_msm* h) {
     if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
     BLZ_LIVE(h);
     if (!h->initialized) return fail(BLZ_ERR_INVALID_PARAM, "start_process before initialize");
-    if (h->armed && h->strm.open)
-        return fail(BLZ_ERR_INVALID_PARAM, "a task is already queued and has received %u of its %u elements", h->strm.received, h->strm.total);
-    if (h->armed) return fail(BLZ_ERR_INVALID_PARAM, "a task is already queued and waits for data");
-    h->armed = true;
+    blz_msm::Feed& F = h->feed;
+    if (F.open) return fail(BLZ_ERR_INVALID_PARAM, "a task is already queued and has received %u of its %u elements", F.received, F.n);
+    if (F.armed) return fail(BLZ_ERR_INVALID_PARAM, "a task is already queued and waits for data");
+    F.armed = true;
     h->task_label += 1;
-    if (h->data_ready && h->staged_n != h->nof_elements)
-        return fail(BLZ_ERR_INVALID_PARAM, "staged data has %u elements, task expects %u", h->staged_n, h->nof_elements);
+    if (F.ready && F.n != h->nof_elements) return fail(BLZ_ERR_INVALID_PARAM, "staged data has %u elements, task expects %u", F.n, h->nof_elements);
     return launch_if_ready(h);
 }
 
 int blz_msm_set_data(blz_msm* h, const uint8_t* points, size_t points_len, const uint8_t* scalars, size_t scalars_len,
                      uint32_t nof_elements, int has_hbm, uint64_t hbm_addr, uint64_t hbm_off) {
-    // with a task queued, fewer elements than the task still lacks = the next slice of it (msm_stage.hip stage_stream: the card
-    // counts what its FIFOs receive against NUMBER_OF_MSM_ELEMENTS, msm_api.rs:155-202); more is refused there
-    if (h && h->armed && (h->strm.open || nof_elements != h->nof_elements))
-        return stage_stream(h, points != nullptr, points, points_len, scalars, scalars_len, nof_elements, has_hbm, hbm_addr, hbm_off, false);
-    return stage_common(h, points != nullptr, points, points_len, scalars, scalars_len, nof_elements, has_hbm, hbm_addr,
-                        hbm_off, false);
+    // with a task queued, a slice of it (msm_stage.hip: the card counts what its FIFOs receive against NUMBER_OF_MSM_ELEMENTS,
+    // msm_api.rs:155-202); more than the task lacks is refused there
+    return stage(h, points, points_len, scalars, scalars_len, nof_elements, has_hbm, hbm_addr, hbm_off, false);
 }
 
 int blz_msm_set_data_device(blz_msm* h, const void* d_points, size_t points_len, const void* d_scalars,
                             size_t scalars_len, uint32_t nof_elements, int has_hbm, uint64_t hbm_addr, uint64_t hbm_off) {
-    if (h && h->armed && (h->strm.open || nof_elements != h->nof_elements))
-        return stage_stream(h, d_points != nullptr, d_points, points_len, d_scalars, scalars_len, nof_elements, has_hbm, hbm_addr, hbm_off, true);
-    return stage_common(h, d_points != nullptr, d_points, points_len, d_scalars, scalars_len, nof_elements, has_hbm,
-                        hbm_addr, hbm_off, true);
+    return stage(h, d_points, points_len, d_scalars, scalars_len, nof_elements, has_hbm, hbm_addr, hbm_off, true);
 }
 
 int blz_msm_wait_result(blz_msm* h) {
@@ -248,9 +243,9 @@ int blz_msm_wait_result(blz_msm* h) {
     BLZ_LIVE(h);
     if (h->in_flight.empty()) {
         if (!h->results.empty()) return BLZ_OK;  // RESULT_VALID already set
-        if (h->strm.open)
+        if (h->feed.open)
             return fail(BLZ_ERR_INVALID_PARAM, "wait_result: the queued task has received %u of its %u elements (the reference would spin forever)",
-                        h->strm.received, h->strm.total);
+                        h->feed.received, h->feed.n);
         return fail(BLZ_ERR_INVALID_PARAM, "wait_result with no task in flight (the reference would spin forever)");
     }
     // tasks complete in submission order: wait for the oldest, move its bytes to the result queue.  The wait is
@@ -327,8 +322,8 @@ int blz_msm_nof_elements(blz_msm* h, uint32_t* out) {
 }
 int blz_msm_stream_progress(blz_msm* h, uint32_t out[2]) {
     if (!h || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
-    out[0] = h->strm.open ? h->strm.received : 0u;
-    out[1] = h->armed ? h->nof_elements : 0u;
+    out[0] = h->feed.open ? h->feed.received : 0u;
+    out[1] = h->feed.armed ? h->nof_elements : 0u;
     return BLZ_OK;
 }
 int blz_msm_is_engine_ready(blz_msm* h, uint32_t* out) {
@@ -344,12 +339,11 @@ int blz_msm_reset(blz_msm* h) {
     // complete stays wedged and reset fails with Unknown again
     BLZ_TRY(sync_stream_bounded(h->copy_stream, "reset: copy stream"));
     BLZ_TRY(h->eng.sync_all());
-    stream_abandon(h);   // (a half-fed task goes with the reset)
+    feed_abandon(h);   // (a half-fed task goes with the reset, and so does the queued one)
+    h->feed.armed = false;
     h->wedged = false;
-    h->armed = h->data_ready = false;
     h->in_flight.clear();
     h->results.clear();
-    h->staged_n = 0;
     return BLZ_OK;
 }
 

@@ -75,6 +75,7 @@ struct MsmSlot {
     bool use_s3 = false, ranged = false;
     uint32_t npts = 0, pts_per_slice = 0;
     int sbits = 0, bit_lo = 0, bit_hi = 0;
+    int repr = 0;                  // the arithmetic begin() sized the task for (bucket_sums): accumulate_slice / end refuse another
     hipEvent_t task_inputs_event = nullptr;   // the caller's inputs_event, until it has been recorded
     // A piecewise task on an otherwise idle handle sorts piece k + 1 UNDERNEATH the accumulation of piece k, like a stream
     // of tasks does: the pieces alternate between this slot's SortBufs and the other slot's (which nobody uses while that

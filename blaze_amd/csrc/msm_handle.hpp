@@ -19,8 +19,6 @@ struct blz_msm {
     uint64_t hbm_addr = 0;
     bool initialized = false;
     // task / result queues (msm_hw_code.rs:19-25)
-    bool armed = false;        // a task was pushed and waits for its data
-    bool data_ready = false;   // set_data delivered a complete input
     struct Pending { int slot; uint32_t label; };
     std::deque<Pending> in_flight;   // pipelines enqueued, results not collected yet (<= MSM_QUEUE_DEPTH)
     uint32_t task_label = 0;
@@ -32,14 +30,8 @@ struct blz_msm {
     blz::DevBuf scalars_buf[2], points_raw[2], points_mont;
     hipEvent_t set_free[2] = {nullptr, nullptr};
     bool set_used[2] = {false, false};
-    int stage_idx = 0, staged_set = -1;
+    int stage_idx = 0;
     hipStream_t copy_stream = nullptr;  // host -> device staging: runs under the previous task's accumulation
-    const void* d_scalars = nullptr;
-    const void* d_points_mont = nullptr;
-    uint32_t staged_n = 0;
-    bool staged_from_arena = false;
-    bool staged_loaded_now = false;   // this set_data also loaded the bases (mode iii: points + hbm address)
-    uint64_t staged_arena_pos = 0;
     // Tasks whose points arrive over the link and are consumed piece by piece (DMA mode: one-call and streamed tasks): a piece's raw
     // points and their Montgomery copy live in a slot of a small ring, not in buffers of the whole task's size - 4 x (96 + 128) bytes
     // x the piece instead of 48 + 64 GiB for the reference's largest shape (whose allocation alone took the first task 4 s).  A
@@ -54,26 +46,30 @@ struct blz_msm {
         bool recorded[SLOTS] = {false, false, false, false};
         uint64_t next = 0;                    // pieces handed out so far: piece -> slot next % SLOTS
     } ring;
-    // A task fed by SEVERAL set_data calls (msm_stage.hip stage_stream): the card takes a task's scalars and points through FIFOs and
-    // counts elements against NUMBER_OF_MSM_ELEMENTS (msm_api.rs:155-202, msm_hw_code.rs:18-19), so any split of an armed task's
-    // bytes over calls is the same task.  SURVEY.md 8(b): {armed_n, received}, launch when received == armed_n.
-    struct Stream {
-        bool open = false;
+    // The task being fed (msm_stage.hip): the card takes a task's scalars and points through FIFOs and counts elements against
+    // NUMBER_OF_MSM_ELEMENTS (msm_api.rs:155-202, msm_hw_code.rs:18-19), so any split of an armed task's bytes over set_data calls
+    // is the same task.  SURVEY.md 8(b): {armed_n, received}, launch when received == armed_n.
+    struct Feed {
+        bool armed = false;        // start_process pushed a task that waits for its data
+        bool open = false;         // its first slice is in and its last is not: n, mode, set and the pieces are fixed
+        bool ready = false;        // the data is complete: launched whole once the task is armed (launch_if_ready)
         int mode = 0;              // 1 scalars only, bases in the arena; 2 points + scalars (DMA mode); 3 points into the arena + scalars
         bool src_device = false;   // the slices are device pointers (set_data_device)
-        uint32_t total = 0;        // elements of the armed task (initialize's nof_elements)
+        uint32_t n = 0;            // elements of the task: nof_elements when its first slice came (before start_process: that call's own)
         uint32_t received = 0;     // elements delivered so far
-        int set = -1;              // staging set the slices land in
-        int slot = -1;             // engine slot of a task enqueued piece by piece; -1: launched whole when the last slice is in
+        int set = -1;              // staging set the slices land in; -1: one call from device pointers, used in place
+        const void* d_scalars = nullptr;
+        uint64_t arena_pos = 0;    // modes 1 and 3: where the task's bases start
+        // a task enqueued piece by piece (slot >= 0; -1: launched whole when its data is complete)
+        int slot = -1;             // its engine slot
         uint32_t per = 0;          // points per piece
-        int pieces = 0, next_piece = 0;
         uint32_t ppe = 1;          // points per element as the engine counts them (1; 8; 4 on the checked-table plan)
-        uint32_t npts = 0, done_pts = 0;   // points of the task / handed to the engine so far
-        uint64_t ring_first = 0;   // mode 2 in pieces: ring piece number of the task's piece 0
+        uint32_t npts = 0;         // points of the task
         int sbits = 0;
         bool even = false;         // checked-table plan: pieces gather from the even-base copy
-        uint64_t arena_pos = 0;    // modes 1 and 3: where the task's bases start
-    } strm;
+        uint64_t ring_first = 0;   // mode 2: ring piece number of the task's piece 0
+        const void* mont = nullptr;   // modes 1 and 3: the extent's Montgomery copy (resolved again for every slice)
+    } feed;
     blz::MsmEngine eng;
     // a wait ran into its deadline (BLAZE_WAIT_TIMEOUT_MS): device work of this handle may never complete, so nothing
     // new is queued behind it; reset (which waits, bounded, for the streams to drain) or free are the ways out
@@ -121,6 +117,8 @@ namespace blz {
 
 inline size_t point_size(const blz_msm* h) { return blz_point_size(h->curve); }
 inline size_t result_size(const blz_msm* h) { return blz_result_size(h->curve); }
+// an engine slot of this handle is taken: a task is in flight, or the task being fed holds one
+inline bool busy(const blz_msm* h) { return !h->in_flight.empty() || h->feed.slot >= 0; }
 
 // ---- arena_tables.hip
 constexpr int TABLE_CHUNKS_PER_TASK = 4;           // ~22 ms on top of a 2^26 task's 117: 86 tasks until a 2^26 table is there
@@ -131,14 +129,13 @@ void task_repr_bn254pc(blz_msm* h, bool on_plan, uint64_t checked_elems);   // t
 int arena_points_mont(blz_msm* h, uint64_t pos, uint32_t npts, const void** out, bool even = false);
 int arena_precompute_check(blz_msm* h, uint64_t pos, uint32_t nelem, bool* ok, uint64_t* checked_elems = nullptr);
 int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out, int* c_out, int chunk_budget);
-int resolve_arena_task(blz_msm* h, uint64_t pos, uint32_t n, bool allow_table, bool allow_plan, uint32_t* npts, int* sbits, int* table_c);
+int resolve_arena_task(blz_msm* h, uint64_t pos, uint32_t n, bool allow_table, bool allow_plan, uint32_t* npts, int* sbits, int* table_c,
+                       const void** pts);
 // ---- msm_stage.hip
-int launch_if_ready(blz_msm* h);
-int stage_stream(blz_msm* h, bool have_points, const void* points, size_t points_len, const void* scalars, size_t scalars_len, uint32_t m,
-                 int has_hbm, uint64_t hbm_addr, uint64_t hbm_off, bool on_device);
-int ring_reserve(blz_msm* h, uint32_t piece_pts);   // the ring's slots hold pieces of piece_pts points
-void stream_abandon(blz_msm* h);   // give up a half-fed task (reset, a failed slice)
-int stage_common(blz_msm* h, bool have_points, const void* points, size_t points_len, const void* scalars, size_t scalars_len, uint32_t n,
-                 int has_hbm, uint64_t hbm_addr, uint64_t hbm_off, bool on_device);
+int launch_if_ready(blz_msm* h);   // the task is armed and its data complete: launch it whole
+// set_data / set_data_device: one slice of the armed task (all of it in one call), or data staged before start_process
+int stage(blz_msm* h, const void* points, size_t points_len, const void* scalars, size_t scalars_len, uint32_t m, int has_hbm,
+          uint64_t hbm_addr, uint64_t hbm_off, bool on_device);
+void feed_abandon(blz_msm* h);   // give up the task being fed (a failed slice, reset): its slot and data go, it stays armed
 
 }  // namespace blz

@@ -98,7 +98,8 @@ int blz_msm_start_process(blz_msm* h);
  * slice; points + scalars; points + hbm_point_addr: slice k's table is loaded right behind slice k - 1's, its address must say
  * so).  The task is handed to the device piece by piece while later slices are still with the host (the pieces of a one-call
  * DMA-mode task) and is complete with the slice that brings received to nof_elements; more than that is refused and changes
- * nothing, start_process / wait_result with a half-fed task are refused (a task already in flight can still be waited for),
+ * nothing, initialize / start_process / wait_result with a half-fed task are refused (its element count is the
+ * nof_elements it was armed with when its first slice came; a task already in flight can still be waited for),
  * blz_msm_reset drops it.  A slice that fails in transfer loses the stream: the task stays queued and may be sent again from
  * its first element.  Results are byte-identical to the one-call task's (tests/test_gpu_msm_stream.py).  The reference's
  * largest DMA-mode shape - tests/integration_msm.rs:386-467, 2^26 elements x 8 bases = a 48 GiB host vector - runs from host

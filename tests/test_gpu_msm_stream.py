@@ -1,4 +1,4 @@
-"""A task fed by SEVERAL set_data calls (include/blaze_hip.h "STREAMED TASKS"; blaze_amd/csrc/msm_stage.hip stage_stream).  The
+"""A task fed by SEVERAL set_data calls (include/blaze_hip.h "STREAMED TASKS"; blaze_amd/csrc/msm_stage.hip).  The
 reference writes its input to the card's FIFOs in 2048-element chunks (src/ingo_msm/msm_api.rs:155-202) and the card counts
 elements against NUMBER_OF_MSM_ELEMENTS (msm_hw_code.rs:18-19): however a queued task's bytes are split over calls, it is the
 same task.  SURVEY.md 8(b): {armed_n, received}, launch when received == armed_n."""
@@ -141,6 +141,16 @@ def test_stream_state_machine(gpu, orc):
     with pytest.raises(DriverClientError):
         cl.wait_result()
     assert run_msm(cl, pts, sc, n) == exp
+    # a half-fed task keeps the element count it was opened with: initialize is refused and changes nothing
+    cl.initialize(p); cl.start_process()
+    cl.set_data(MSMInput(pts[: 100 * ps], sc[: 3200], MSMParams(100, None)))
+    with pytest.raises(DriverClientError) as ei:
+        cl.initialize(MSMParams(2 * n, None))
+    assert ei.value.variant == "InvalidPrimitiveParam" and cl.stream_progress() == (100, n)
+    cl.set_data(MSMInput(pts[100 * ps: 3000 * ps], sc[3200: 3000 * 32], MSMParams(2900, None)))
+    cl.set_data(MSMInput(pts[3000 * ps:], sc[3000 * 32:], MSMParams(n - 3000, None)))
+    cl.wait_result()
+    assert cl.result().result == exp
     _feed(cl, pts, sc, n, 1, ps, [1, 4999])
     cl.wait_result()
     assert cl.result().result == exp
@@ -205,6 +215,32 @@ def test_streamed_precompute_plan_and_ranges(gpu, orc, monkeypatch):
     _feed(cl, None, sc, n, 1, 96, _cuts(rng, n, "random"), hbm=(0, 0))
     cl.wait_result()
     assert cl.result().result == exp
+    cl.close()
+    blaze_amd._lib.check(blaze_amd.lib().blz_arena_release(0))
+
+
+def test_plan_prepared_under_a_streamed_precompute_task(gpu, orc, monkeypatch):
+    """A BN254 precompute handle in DMA mode that opted in to the checked-table plan, with a consistent table in the arena: the plan
+    would take the reduced radix.  prepare_precompute_plan between two host slices of a task enqueued in pieces must leave the
+    arithmetic the task began with (its bucket sums were sized for it): the bytes of the oracle."""
+    monkeypatch.setenv("BLAZE_MSM_PIECES", "3")
+    curve, n, pf, ps = "BN254", 3000, 8, 64
+    pts, sc, exp = orc.input_generator(curve, n, pf, 77)
+    blaze_amd._lib.check(blaze_amd.lib().blz_arena_release(0))
+    cl = msm_client(curve, pf)
+    cl.set_precompute_plan(True)
+    cl.load_data_to_hbm(pts, 0, 0)
+    assert cl.prepare_precompute_plan(n, (0, 0))
+    assert run_msm(cl, pts, sc, n) == exp
+    cl.initialize(MSMParams(n, None)); cl.start_process()
+    half = 1500
+    cl.set_data(MSMInput(pts[: half * pf * ps], sc[: 32 * half], MSMParams(half, None)))
+    assert cl.stream_progress() == (half, n)
+    assert cl.prepare_precompute_plan(n, (0, 0))
+    cl.set_data(MSMInput(pts[half * pf * ps:], sc[32 * half:], MSMParams(n - half, None)))
+    cl.wait_result()
+    assert cl.result().result == exp
+    assert run_msm(cl, pts, sc, n) == exp
     cl.close()
     blaze_amd._lib.check(blaze_amd.lib().blz_arena_release(0))
 
