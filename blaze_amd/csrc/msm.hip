@@ -695,7 +695,7 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
                 : ranged    ? plan_for_range(npts, bit_lo, bit_hi)
                             : make_plan(npts, sbits, ebits, plan_override("c", 0));
     if (P.c == 0) return fail(BLZ_ERR_INVALID_PARAM, "no window plan for npts=%u sbits=%d%s", npts, sbits, table_c > 0 ? " (window table)" : "");
-    if (P.table && (sbits != 256 || !msm_sort3t_ok(P))) return fail(BLZ_ERR_INVALID_PARAM, "window-table task outside the sort's range (c=%d)", P.c);
+    if (P.table && !msm_sort3_ok(P, sbits)) return fail(BLZ_ERR_INVALID_PARAM, "window-table task outside the sort's range (c=%d)", P.c);
     P.L = (uint32_t)plan_override("L", (int)P.L);
     if (P.L < 1) P.L = 1;
     if (P.L > (uint32_t)MAX_L) P.L = MAX_L;
@@ -725,6 +725,11 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
     const MsmSlot& O = slots[(slot + 1) % MSM_QUEUE_DEPTH];
     bool s3 = P.table || (hide_env != 0 && nslices == 1 && msm_sort3_ok(P, sbits));   // (a table task has no other sort)
     bool fits = true;
+    // (a build whose register counts cannot be read is taken to fit; k_accumulate_cont shares k_accumulate's register cap)
+    auto sort_fits = [&](bool table) {
+        const int av = ops->accumulate_vgprs(), sv = msm_sort3_max_vgprs(table);
+        return !(av > 0 && sv > 0 && !sort_fits_beside(av, sv));
+    };
     if (s3 && hide_env == 1 && !P.table) {
         // the three-level sort gives one block a whole level-2 bin: fine for the near-uniform digits of real scalars, a
         // cliff for inputs that pile entries into a few buckets (the reference harness repeats a 256-point tile).  The
@@ -740,18 +745,15 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
         // the open (round 3 saw 211 VGPRs cost 4 ms per step before this check existed).
         // (the SIMD runs as many accumulation waves as their allocation admits: two of the reduced-radix kernels', three of
         // the 32-bit-limb kernel's, whose allocation is padded to 136 for exactly this purpose)
-        const int av = ops->accumulate_vgprs(), sv = P.table ? msm_sort3t_max_vgprs() : msm_sort3_max_vgprs();
-        if (av > 0 && sv > 0 && !sort_fits_beside(av, sv)) fits = false;
-        if (!fits && !P.table) s3 = false;
+        // A table plan's largest kernel (k3t_l3<true>: 78 VGPRs, allocated as 80) fits with nothing to spare: 2 x 200 + 80 = 480.
+        fits = sort_fits(P.table);
+        if (!fits && !P.table) s3 = false;   // (a table task has no other sort: it then sorts in the open)
     }
     bool hide = s3 && O.busy && hide_env != 0 && fits;
     // pieces of a task on an otherwise idle handle: piece k + 1 sorts underneath the accumulation of piece k (ping-pong over
     // the two slots' sort buffers); same conditions as hiding a task's sort
-    bool pingpong = false;
-    if (nslices > 1 && hide_env != 0 && !O.busy && !P.table && msm_sort3_ok(P, sbits) && !(recent_hot[0] || recent_hot[1])) {
-        const int av = ops->accumulate_vgprs(), sv = msm_sort3_max_vgprs();   // (k_accumulate_cont shares k_accumulate's register cap)
-        if (!(av > 0 && sv > 0 && !sort_fits_beside(av, sv))) pingpong = true;
-    }
+    const bool pingpong = nslices > 1 && hide_env != 0 && !O.busy && !P.table && msm_sort3_ok(P, sbits) && !(recent_hot[0] || recent_hot[1]) &&
+                          sort_fits(false);
     if (pingpong) { s3 = true; hide = true; }
 
     cur = slot;
@@ -840,7 +842,7 @@ int MsmEngine::sort_slice(int slot, int sl, const void* d_scalars, uint32_t np) 
     // a small task's whole sort stage - digits, bucket scan, entries, unit lists - is one block's work (msm_sort_tiny.hip)
     const bool tiny = !S.use_s3 && S.slices == 1 && msm_sort_tiny_ok(P, np, S.sbits);
     if (S.use_s3) {
-        BLZ_TRY(P.table ? msm_sort3t(E, sc_s, np) : msm_sort3(E, sc_s, np, S.sbits));   // count[] and entries[] in one go
+        BLZ_TRY(msm_sort3(E, sc_s, np, S.sbits));   // count[] and entries[] in one go
     } else if (tiny) {
         BLZ_TRY(msm_sort_tiny(E, sc_s, np, S.sbits, (uint32_t)S.max_units));
     } else {

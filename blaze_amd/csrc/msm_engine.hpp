@@ -178,14 +178,11 @@ size_t mont_point_bytes(int curve);  // stride of the Montgomery point array the
 // two-level LDS-privatised digit sort (msm_sort.hip): fills count[], then (after the scan) entries[]
 int msm_sort_lds(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits);
 // three-level, small-footprint digit sort built to run underneath another task's k_accumulate (msm_sort3.hip): fills
-// count[] and entries[] of the current slot's SortBufs on E.sort_st; msm_sort3_ok: does the plan qualify
+// count[] and entries[] of the current slot's SortBufs on E.sort_st.  One family of kernels for plain plans and for
+// window-table plans (P.table: shared bucket set, entries = point * W + window).  msm_sort3_ok: does the plan qualify
 bool msm_sort3_ok(const MsmPlan& P, int sbits);
-int msm_sort3_max_vgprs();   // the largest register count among the three-level sort's kernels (0 if unknown)
+int msm_sort3_max_vgprs(bool table);   // the largest register count among the kernels of that kind of plan (0 if unknown)
 int msm_sort3(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits);
-// the same sort for window-table plans (shared bucket set, entries = point * W + window)
-bool msm_sort3t_ok(const MsmPlan& P);
-int msm_sort3t_max_vgprs();
-int msm_sort3t(MsmEngine& E, const void* d_scalars, uint32_t npts);
 int msm_sort_lds_scatter(MsmEngine& E);
 // the whole sort stage of a small task (digits, bucket scan, entries, unit lists, stats) in one block (msm_sort_tiny.hip)
 bool msm_sort_tiny_ok(const MsmPlan& P, uint32_t npts, int sbits);

@@ -7,9 +7,13 @@
 // block produces pieces of one or two entries, the memory system drowns in lone stores, and the accumulation above it
 // slows down by more than the sort costs alone (round 2 measured exactly that: profiles/r02_sort_under_accumulate.txt).
 // Hence three levels of at most 256 / 128 / 128 ways, so that a block of 256 lanes with 12 - 16 entries per lane still
-// writes pieces of 24 - 32 entries, every kernel at <= 96 VGPRs and 256 threads, wave priority raised (at equal priority
-// the accumulation's older waves starve the sort's):
+// writes pieces of 24 - 32 entries, 256 threads per block, wave priority raised (at equal priority the accumulation's
+// older waves starve the sort's).  Registers as compiled for gfx950: the plain plan's kernels <= 72 VGPRs
+// (k3_l1_scatter 72, k3_l3 70), the table plan's <= 78 (k3t_l3<true> 78, k3_l1_scatter 72, k3t_l3<false> 54).  The sort
+// hides only while MsmEngine::begin()'s sort_fits_beside holds: 2 x 200 + 72 = 472 of the 480 registers a SIMD hands
+// out, and 2 x 200 + 80 (78 is allocated as 80) = 480 with nothing to spare; tests/test_isa_counts.py holds these bounds.
 //
+// ONE family of kernels, two geometries (S3Geom: plain window plans, S3TGeom: window-table plans).  Plain plan:
 //   bucket g (flat over the windows)  =  level-1 bin (g >> 14)  |  level-2 digit (7 bits)  |  level-3 digit (7 bits)
 //   k3_l1_count    scalars -> LDS histogram over the <= 2048 level-1 bins -> cnt1
 //   k3_l1_scatter  3072 scalars per block parked in LDS (lane-private, word-major: the block's register file stays
@@ -40,13 +44,78 @@ constexpr int S3_T3 = 28;                       // level 3: entries per lane hel
 constexpr uint32_t S3_R3 = S3_THREADS * S3_T3;  // ... so a level-2 bin of up to 7168 entries takes one pass (mean at 2^26: 5.8 K, sigma 76)
 constexpr uint32_t S3_MAXNB1 = 2048;            // level-1 bins in all (LDS histogram of k3_l1_count)
 constexpr uint32_t S3_CNT_PTS = 16384;          // points per block of k3_l1_count
+constexpr uint32_t S3T_IMG = 12288;             // entries of the table plan's final-level LDS image (dynamic LDS: 48 KiB)
 
+// ---------------------------------------------------------------------------------------------- the two geometries
+// A geometry is the kernel argument of the level-1 and level-2 kernels and says everything in which the two kinds of plan
+// differ: as constants for the plain plan (its kernels run under the headline's accumulation), as fields for the table plan.
+//
+// Plain plan: every window has its own width and its own buckets, hence its own run of level-1 bins (bucket >> 14); the
+// 14-bit remainder splits 7 | 7.  Level 2 needs nothing but the priority (L2).
 struct S3Geom {
     int W, prio;
     uint32_t NB1;
     uint8_t width[MSM_MAX_W];
     uint16_t bitoff[MSM_MAX_W];        // first scalar bit of window w
     uint16_t binoff1[MSM_MAX_W + 1];   // first level-1 bin of window w
+    static constexpr bool TABLE = false;
+    static constexpr uint32_t HIST1 = S3_MAXNB1;   // LDS histogram of k3_l1_count
+    using Win = int;                               // window counter of k3_l1_scatter
+    __device__ int cw(int w) const { return width[w]; }
+    __device__ uint32_t first_bin(int w) const { return binoff1[w]; }
+    __device__ static constexpr uint32_t shift1() { return S3_SH1; }
+    static constexpr uint32_t bits3() { return S3_SH2; }
+    // what an entry carries out of level 1: (index | sign : u32, remainder : u16)
+    __device__ static uint32_t index1(uint32_t p, uint32_t, uint32_t) { return p; }
+    __device__ static uint32_t rem1(uint32_t rem) { return rem; }
+    struct L2 {
+        int prio;
+        using Lo = uint8_t;                             // side array out of level 2: the final level's 7 bits
+        static constexpr uint32_t TAB2 = 128;           // LDS tables of level 2
+        static constexpr uint32_t KY_D = 8, KY_R = 16;  // ky = final-level bits | level-2 digit << KY_D | rank << KY_R
+        static constexpr uint32_t LO_MASK = 127u;
+        __device__ static constexpr uint32_t shift2() { return S3_SH2; }
+        __device__ static constexpr uint32_t bits2() { return S3_SH1 - S3_SH2; }
+        __device__ static uint32_t low2(uint32_t r, uint32_t) { return r & 127u; }
+        __device__ static uint32_t index2(uint32_t iw) { return iw; }
+    };
+    L2 l2() const { return L2{prio}; }
+};
+
+// Window-table plan (MsmPlan::table, msm_impl.hip.hpp k_build_window_table): W windows of c bits share ONE bucket set,
+// G = 2^(c-1) buckets, an entry carries (base * W + window) | sign.
+//   * every window scatters into the same 256 level-1 bins (bucket >> sh1, sh1 = c - 9), so the level-1 remainder is up
+//     to 17 bits wide: 16 travel in the u16 side array, the lowest one (xs = 1) in bit 30 of the index word (indices stay
+//     below 2^30: make_table_plan) and level 2 folds it back;
+//   * the split of the remainder between level 2 (b2 <= 8 bits) and the final level (b3 bits, one block per 2^b3 buckets) is
+//     chosen per task so that a final block holds about 6 K entries: wide windows have few entries per bucket (2^26 bases,
+//     c = 26: 20), and 128 buckets per block would leave the blocks with 2.5 K entries and 2^18 of them.
+struct S3TGeom {
+    int W, prio, c;
+    uint32_t sh1, b2, b3, xs, NB1;
+    static constexpr bool TABLE = true;
+    static constexpr uint32_t HIST1 = 256;
+    using Win = uint32_t;
+    __device__ int cw(int) const { return c; }
+    __device__ static constexpr uint32_t first_bin(int) { return 0; }
+    __device__ uint32_t shift1() const { return sh1; }
+    uint32_t bits3() const { return b3; }
+    // index word: (base * W + window) | remainder bit 0 at bit 30 when the remainder has 17 bits
+    __device__ uint32_t index1(uint32_t p, uint32_t w, uint32_t rem) const { return (p * (uint32_t)W + w) | (xs ? (rem & 1u) << 30 : 0u); }
+    __device__ uint32_t rem1(uint32_t rem) const { return rem >> xs; }
+    using L2 = S3TGeom;
+    using Lo = uint16_t;                                // the final level's b3 <= 10 bits
+    static constexpr uint32_t TAB2 = 256;
+    static constexpr uint32_t KY_D = 10, KY_R = 18;
+    static constexpr uint32_t LO_MASK = 0x3ffu;
+    __device__ uint32_t shift2() const { return b3 - xs; }   // the stored u16 is the remainder >> xs; its level-2 digit is the top b2 bits
+    __device__ uint32_t bits2() const { return b2; }
+    __device__ uint32_t low2(uint32_t r, uint32_t iw) const {
+        const uint32_t lomask = (1u << shift2()) - 1u;
+        return xs ? ((r & lomask) << 1) | ((iw >> 30) & 1u) : (r & lomask);
+    }
+    __device__ static uint32_t index2(uint32_t iw) { return iw & 0xbfffffffu; }
+    const L2& l2() const { return *this; }
 };
 
 // wave priority of the sort's kernels (s_setprio takes an immediate); BLAZE_SORT_PRIO = 0..3, default 3
@@ -55,7 +124,6 @@ __device__ __forceinline__ void s3_setprio(int p) {
     else if (p == 2) __builtin_amdgcn_s_setprio(2);
     else if (p == 1) __builtin_amdgcn_s_setprio(1);
 }
-#define S3_PRIO() s3_setprio(prio)
 
 __device__ __forceinline__ uint32_t s3_wave_incl_scan(uint32_t v) {
     for (int o = 1; o < 64; o <<= 1) {
@@ -77,14 +145,14 @@ __device__ __forceinline__ uint32_t s3_block_excl_scan(uint32_t v, uint32_t* wav
 
 // ---------------------------------------------------------------------------------------------- level 1
 // NW: 32-bit words per scalar - 8 (256-bit scalars), 1 (the 32-bit chunks of a precompute handle: pf = 8) or 2 (its 64-bit
-// chunks on the checked-table plan: arena_tables.hip)
-template <int NW>
-__global__ __launch_bounds__(S3_THREADS, 4) void k3_l1_count(const uint32_t* __restrict__ scalars, uint32_t npts, S3Geom g,
+// chunks on the checked-table plan: arena_tables.hip); a table plan is 256-bit only
+template <class Geom, int NW>
+__global__ __launch_bounds__(S3_THREADS, 4) void k3_l1_count(const uint32_t* __restrict__ scalars, uint32_t npts, Geom g,
                                                             uint32_t* __restrict__ cnt1) {
-    const int prio = g.prio;
-    S3_PRIO();
-    __shared__ uint32_t hist[S3_MAXNB1];
-    for (uint32_t i = threadIdx.x; i < g.NB1; i += S3_THREADS) hist[i] = 0;
+    s3_setprio(g.prio);
+    __shared__ uint32_t hist[Geom::HIST1];
+    if constexpr (Geom::HIST1 == S3_THREADS) hist[threadIdx.x] = 0;
+    else for (uint32_t i = threadIdx.x; i < g.NB1; i += S3_THREADS) hist[i] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * S3_CNT_PTS;
     uint32_t end = base + S3_CNT_PTS;
@@ -101,26 +169,28 @@ __global__ __launch_bounds__(S3_THREADS, 4) void k3_l1_count(const uint32_t* __r
             if (p0 + u * S3_THREADS >= end) break;
             uint32_t carry = 0;
             for (int w = 0; w < g.W; ++w) {
-                const int cw = g.width[w];
+                const int cw = g.cw(w);
                 const int d = sw[u].next(cw, (1u << cw) - 1u, 1u << (cw - 1), carry);
                 if (d != 0) {
                     const uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1u;
-                    atomicAdd(&hist[g.binoff1[w] + (b >> S3_SH1)], 1u);
+                    atomicAdd(&hist[g.first_bin(w) + (b >> g.shift1())], 1u);
                 }
             }
         }
     }
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < g.NB1; i += S3_THREADS) {
+    auto flush = [&](uint32_t i) {
         const uint32_t v = hist[i];
         if (v) atomicAdd(&cnt1[i], v);
-    }
+    };
+    if constexpr (Geom::HIST1 == S3_THREADS) { if (threadIdx.x < g.NB1) flush(threadIdx.x); }
+    else for (uint32_t i = threadIdx.x; i < g.NB1; i += S3_THREADS) flush(i);
 }
 
 // exclusive scan of n <= 2048 counters (one block): off[0..n], cur[i] = off[i]
 __global__ __launch_bounds__(S3_THREADS) void k3_scan_small(const uint32_t* __restrict__ cnt, uint32_t n, uint32_t* __restrict__ off,
                                                            uint32_t* __restrict__ cur, int prio) {
-    S3_PRIO();
+    s3_setprio(prio);
     __shared__ uint32_t wave_tot[4];
     uint32_t v[8], sum = 0;
     const uint32_t b0 = threadIdx.x * 8u;
@@ -142,12 +212,11 @@ __global__ __launch_bounds__(S3_THREADS) void k3_scan_small(const uint32_t* __re
     if (threadIdx.x == 0) off[n] = total;
 }
 
-template <int NW>
-__global__ __launch_bounds__(S3_THREADS, 4) void k3_l1_scatter(const uint32_t* __restrict__ scalars, uint32_t npts, S3Geom g,
+template <class Geom, int NW>
+__global__ __launch_bounds__(S3_THREADS, 4) void k3_l1_scatter(const uint32_t* __restrict__ scalars, uint32_t npts, Geom g,
                                                               uint32_t* __restrict__ cur1, uint32_t* __restrict__ o_idx,
                                                               uint16_t* __restrict__ o_rem) {
-    const int prio = g.prio;
-    S3_PRIO();
+    s3_setprio(g.prio);
     extern __shared__ __attribute__((aligned(16))) uint32_t sh[];
     uint32_t* sc = sh;                                          // [NW][S3_PB]: word j of the lane's scalar u at j * PB + u * 256 + tid
     uint2* stage = reinterpret_cast<uint2*>(sh + NW * S3_PB);   // [S3_PB]
@@ -180,13 +249,18 @@ __global__ __launch_bounds__(S3_THREADS, 4) void k3_l1_scatter(const uint32_t* _
         }
     }
     uint32_t carry = 0;   // bit u: the carry of the lane's scalar u into the next window
-    for (int w = 0; w < g.W; ++w) {
-        const uint32_t cw = g.width[w], off = g.bitoff[w];
-        const uint32_t nb = (uint32_t)g.binoff1[w + 1] - (uint32_t)g.binoff1[w];   // <= 256
+    // (the plain plan's arrays are read in place, not through accessors, and the counter keeps each plan's own type: either
+    // change moves the counter of the headline's kernel into a vector register - 72 -> 80 VGPRs)
+    using Win = typename Geom::Win;
+    for (Win w = 0; w < (Win)g.W; ++w) {
+        uint32_t cw, off, nb;   // the window's width, its first bit, its level-1 bins (<= 256)
+        if constexpr (Geom::TABLE) { cw = (uint32_t)g.c; off = w * cw; nb = g.NB1; }
+        else { cw = g.width[w]; off = g.bitoff[w]; nb = (uint32_t)g.binoff1[w + 1] - (uint32_t)g.binoff1[w]; }
+        const uint32_t sh1 = g.shift1(), lowmask = (1u << sh1) - 1u;
         const uint32_t j = off >> 5, shb = off & 31u, mask = (1u << cw) - 1u, half = 1u << (cw - 1);
-        if (tid < nb) hist[tid] = 0;
+        if (Geom::TABLE || tid < nb) hist[tid] = 0;   // (a table plan's windows all have the 256 bins)
         __syncthreads();
-        uint32_t key[S3_T], rk[S3_T];   // key = low 14 bits | bin << 14 | sign << 31;  rk = rank in the bin, ~0 = no entry
+        uint32_t key[S3_T], rk[S3_T];   // key = low sh1 bits | bin << sh1 | sign << 31;  rk = rank in the bin, ~0 = no entry
 #pragma unroll
         for (int u = 0; u < S3_T; ++u) {
             const uint32_t i = u * S3_THREADS + tid;
@@ -201,8 +275,8 @@ __global__ __launch_bounds__(S3_THREADS, 4) void k3_l1_scatter(const uint32_t* _
             key[u] = 0;
             if (d != 0 && base + i < npts) {
                 const uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1u;
-                const uint32_t bin = b >> S3_SH1;
-                key[u] = (b & 0x3fffu) | (bin << 14) | (d < 0 ? 0x80000000u : 0u);
+                const uint32_t bin = b >> sh1;
+                key[u] = (b & lowmask) | (bin << sh1) | (d < 0 ? 0x80000000u : 0u);
                 rk[u] = atomicAdd(&hist[bin], 1u);
             }
         }
@@ -213,15 +287,18 @@ __global__ __launch_bounds__(S3_THREADS, 4) void k3_l1_scatter(const uint32_t* _
             const uint32_t excl = s3_block_excl_scan(v, wave_tot, &total);
             if (tid < nb) {
                 lstart[tid] = excl;
-                gbase[tid] = v ? atomicAdd(&cur1[(uint32_t)g.binoff1[w] + tid], v) : 0u;
+                uint32_t ci;   // the bin's counter: a plain window's bins start at binoff1[w]
+                if constexpr (Geom::TABLE) ci = tid; else ci = (uint32_t)g.binoff1[w] + tid;
+                gbase[tid] = v ? atomicAdd(&cur1[ci], v) : 0u;
             }
             __syncthreads();
 #pragma unroll
             for (int u = 0; u < S3_T; ++u) {
                 if (rk[u] != ~0u) {
-                    const uint32_t bin = (key[u] >> 14) & 0x1ffu;
+                    const uint32_t bin = (key[u] >> sh1) & (Geom::TABLE ? 0xffu : 0x1ffu);
                     const uint32_t p = base + u * S3_THREADS + tid;
-                    stage[lstart[bin] + rk[u]] = make_uint2(p | (key[u] & 0x80000000u), (key[u] & 0x3fffu) | (bin << 16));
+                    const uint32_t rem = key[u] & lowmask;
+                    stage[lstart[bin] + rk[u]] = make_uint2((Geom::TABLE ? g.index1(p, (uint32_t)w, rem) : p) | (key[u] & 0x80000000u), g.rem1(rem) | (bin << 16));
                 }
             }
             __syncthreads();
@@ -241,7 +318,7 @@ __global__ __launch_bounds__(S3_THREADS, 4) void k3_l1_scatter(const uint32_t* _
 // bin k (off[k] .. off[k+1]) cut into ceil(size / slice) work items (k, piece); one block, no host round trip
 __global__ __launch_bounds__(S3_THREADS) void k3_slice_map(const uint32_t* __restrict__ off, uint32_t nbins, uint32_t slice,
                                                           uint2* __restrict__ map, uint32_t* __restrict__ nitems, int prio) {
-    S3_PRIO();
+    s3_setprio(prio);
     __shared__ uint32_t wave_tot[4];
     __shared__ uint32_t carry_sh;
     if (threadIdx.x == 0) carry_sh = 0;
@@ -263,7 +340,7 @@ __global__ __launch_bounds__(S3_THREADS) void k3_slice_map(const uint32_t* __res
 
 // three-kernel exclusive scan of n counters (n <= 2048 * 256): block sums, their scan, final
 __global__ __launch_bounds__(S3_THREADS) void k3_scan_a(const uint32_t* __restrict__ cnt, uint32_t n, uint32_t* __restrict__ bsum, int prio) {
-    S3_PRIO();
+    s3_setprio(prio);
     __shared__ uint32_t wave_tot[4];
     const uint32_t b0 = blockIdx.x * 2048u + threadIdx.x * 8u;
     uint32_t sum = 0;
@@ -274,7 +351,7 @@ __global__ __launch_bounds__(S3_THREADS) void k3_scan_a(const uint32_t* __restri
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 __global__ __launch_bounds__(S3_THREADS) void k3_scan_b(uint32_t* __restrict__ bsum, uint32_t nblocks, int prio) {   // nblocks <= 256
-    S3_PRIO();
+    s3_setprio(prio);
     __shared__ uint32_t wave_tot[4];
     const uint32_t v = threadIdx.x < nblocks ? bsum[threadIdx.x] : 0u;
     uint32_t total;
@@ -284,7 +361,7 @@ __global__ __launch_bounds__(S3_THREADS) void k3_scan_b(uint32_t* __restrict__ b
 }
 __global__ __launch_bounds__(S3_THREADS) void k3_scan_c(const uint32_t* __restrict__ cnt, uint32_t n, const uint32_t* __restrict__ bsum,
                                                        uint32_t* __restrict__ off, uint32_t* __restrict__ cur, int prio) {
-    S3_PRIO();
+    s3_setprio(prio);
     __shared__ uint32_t wave_tot[4];
     const uint32_t b0 = blockIdx.x * 2048u + threadIdx.x * 8u;
     uint32_t v[8], sum = 0;
@@ -318,15 +395,18 @@ __device__ __forceinline__ bool s3_item(const uint32_t* off1, const uint2* map, 
     return lo < hi;
 }
 
+// Geom: S3Geom::L2 or S3TGeom
+template <class Geom>
 __global__ __launch_bounds__(S3_THREADS, 4) void k3_l2_count(const uint16_t* __restrict__ rem, const uint32_t* __restrict__ off1,
                                                             const uint2* __restrict__ map, const uint32_t* __restrict__ nitems,
-                                                            uint32_t* __restrict__ cnt2, int prio) {
-    S3_PRIO();
-    __shared__ uint32_t hist[128];
+                                                            uint32_t* __restrict__ cnt2, Geom g) {
+    s3_setprio(g.prio);
+    __shared__ uint32_t hist[Geom::TAB2];
     uint32_t k, lo, hi;
     if (!s3_item(off1, map, nitems, blockIdx.x, S3_SLICE2, k, lo, hi)) return;
-    if (threadIdx.x < 128) hist[threadIdx.x] = 0;
+    if (Geom::TAB2 == S3_THREADS || threadIdx.x < Geom::TAB2) hist[threadIdx.x] = 0;
     __syncthreads();
+    const uint32_t sh = g.shift2();
     uint32_t r[S3_T2];
 #pragma unroll
     for (int t = 0; t < S3_T2; ++t) {
@@ -335,28 +415,31 @@ __global__ __launch_bounds__(S3_THREADS, 4) void k3_l2_count(const uint16_t* __r
     }
 #pragma unroll
     for (int t = 0; t < S3_T2; ++t)
-        if (r[t] != 0xffffffffu) atomicAdd(&hist[r[t] >> S3_SH2], 1u);
+        if (r[t] != 0xffffffffu) atomicAdd(&hist[r[t] >> sh], 1u);
     __syncthreads();
-    if (threadIdx.x < 128) {
+    if (threadIdx.x < (1u << g.bits2())) {
         const uint32_t v = hist[threadIdx.x];
-        if (v) atomicAdd(&cnt2[(k << 7) + threadIdx.x], v);
+        if (v) atomicAdd(&cnt2[(k << g.bits2()) + threadIdx.x], v);
     }
 }
 
+template <class Geom>
 __global__ __launch_bounds__(S3_THREADS, 4) void k3_l2_scatter(const uint32_t* __restrict__ i_idx, const uint16_t* __restrict__ i_rem,
                                                               const uint32_t* __restrict__ off1, const uint2* __restrict__ map,
                                                               const uint32_t* __restrict__ nitems, uint32_t* __restrict__ cur2,
-                                                              uint32_t* __restrict__ o_idx, uint8_t* __restrict__ o_lo, int prio) {
-    S3_PRIO();
+                                                              uint32_t* __restrict__ o_idx, typename Geom::Lo* __restrict__ o_lo, Geom g) {
+    s3_setprio(g.prio);
+    constexpr uint32_t TAB2 = Geom::TAB2, KY_D = Geom::KY_D, KY_R = Geom::KY_R;
     __shared__ uint2 stage[S3_SLICE2];
-    __shared__ uint32_t hist[128], lstart[128], gbase[128];
+    __shared__ uint32_t hist[TAB2], lstart[TAB2], gbase[TAB2];
     __shared__ uint32_t wave_tot[4];
     uint32_t k, lo, hi;
     if (!s3_item(off1, map, nitems, blockIdx.x, S3_SLICE2, k, lo, hi)) return;
     const uint32_t tid = threadIdx.x;
-    if (tid < 128) hist[tid] = 0;
+    if (TAB2 == S3_THREADS || tid < TAB2) hist[tid] = 0;
     __syncthreads();
-    uint32_t ex[S3_T2], ky[S3_T2];   // ky = low 7 bits | level-2 digit << 8 | rank << 16; ~0 = no entry
+    const uint32_t sh = g.shift2(), nb2 = 1u << g.bits2();
+    uint32_t ex[S3_T2], ky[S3_T2];   // ky = final-level bits | level-2 digit << KY_D | rank << KY_R; ~0 = no entry
 #pragma unroll
     for (int t = 0; t < S3_T2; ++t) {
         const uint32_t i = lo + t * S3_THREADS + tid;
@@ -364,48 +447,52 @@ __global__ __launch_bounds__(S3_THREADS, 4) void k3_l2_scatter(const uint32_t* _
         ex[t] = 0;
         if (i < hi) {
             const uint32_t r = i_rem[i];
-            ex[t] = i_idx[i];
-            const uint32_t h2 = r >> S3_SH2;
+            const uint32_t iw = i_idx[i];
+            const uint32_t h2 = r >> sh;
+            const uint32_t low = g.low2(r, iw);
+            ex[t] = g.index2(iw);
             const uint32_t rank = atomicAdd(&hist[h2], 1u);   // < 4096
-            ky[t] = (r & 127u) | (h2 << 8) | (rank << 16);
+            ky[t] = low | (h2 << KY_D) | (rank << KY_R);
         }
     }
     __syncthreads();
-    const uint32_t v = tid < 128 ? hist[tid] : 0u;
+    const uint32_t v = tid < nb2 ? hist[tid] : 0u;
     uint32_t total;
     const uint32_t excl = s3_block_excl_scan(v, wave_tot, &total);
-    if (tid < 128) {
+    if (tid < nb2) {
         lstart[tid] = excl;
-        gbase[tid] = v ? atomicAdd(&cur2[(k << 7) + tid], v) : 0u;
+        gbase[tid] = v ? atomicAdd(&cur2[(k << g.bits2()) + tid], v) : 0u;
     }
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < S3_T2; ++t) {
         if (ky[t] != 0xffffffffu) {
-            const uint32_t h2 = (ky[t] >> 8) & 127u;
-            stage[lstart[h2] + (ky[t] >> 16)] = make_uint2(ex[t], ky[t] & 0x7fffu);
+            const uint32_t h2 = (ky[t] >> KY_D) & (TAB2 - 1u);
+            stage[lstart[h2] + (ky[t] >> KY_R)] = make_uint2(ex[t], ky[t] & ((TAB2 << KY_D) - 1u));
         }
     }
     __syncthreads();
     for (uint32_t slot = tid; slot < total; slot += S3_THREADS) {
         const uint2 e = stage[slot];
-        const uint32_t h2 = (e.y >> 8) & 127u;
+        const uint32_t h2 = (e.y >> KY_D) & (TAB2 - 1u);
         const uint32_t dst = gbase[h2] + (slot - lstart[h2]);
         o_idx[dst] = e.x;
-        o_lo[dst] = (uint8_t)(e.y & 127u);
+        o_lo[dst] = (typename Geom::Lo)(e.y & Geom::LO_MASK);
     }
 }
 
 // ---------------------------------------------------------------------------------------------- level 3
-// one block per level-2 bin (128 consecutive buckets): bucket counts, then the bin's entries in bucket order.  The bin's
+// Two kernels by design, not by geometry: 128 buckets with one counter per thread and a static image (plain) against up
+// to 1024 with four per thread and a dynamic one (table), and a different answer to a bin beyond the registers.
+//
+// Plain: one block per level-2 bin (128 consecutive buckets): bucket counts, then the bin's entries in bucket order.  The bin's
 // run [off2[j], off2[j+1]) of entries[] is final already: buckets are laid out in order and a bin is a whole group of
 // them.  A bin of up to S3_R3 entries is read once (entries and ranks wait in registers while the counts are scanned),
-// placed in an LDS image of the run and leaves as one contiguous copy; a larger one (hot buckets: the reference
-// harness's repeated tile) is written entry by entry - correct, slow, and not what this path is chosen for.
+// placed in an LDS image of the run and leaves as one contiguous copy; a larger one is placed chunk by chunk.
 __global__ __launch_bounds__(S3_THREADS, 4) void k3_l3(const uint32_t* __restrict__ i_idx, const uint8_t* __restrict__ i_lo,
                                                       const uint32_t* __restrict__ off2, uint32_t* __restrict__ count,
                                                       uint32_t* __restrict__ entries, int prio) {
-    S3_PRIO();
+    s3_setprio(prio);
     __shared__ uint32_t out[S3_R3];
     __shared__ uint32_t hist[128], cursor[128];
     __shared__ uint32_t wave_tot[4];
@@ -506,333 +593,16 @@ __global__ __launch_bounds__(S3_THREADS, 4) void k3_l3(const uint32_t* __restric
     }
 }
 
-// ---------------------------------------------------------------------------------------------- host
-bool msm_sort3_ok(const MsmPlan& P, int sbits) {
-    if ((sbits != 256 && sbits != 64 && sbits != 32) || P.W < 1) return false;
-    for (int w = 0; w < P.W; ++w)
-        if (P.width[w] < S3_SH1 + 1 || P.width[w] > 23) return false;   // every window a whole number of level-1 bins, <= 256 of them
-    if ((P.G >> S3_SH1) > S3_MAXNB1 || (P.G & ((1u << S3_SH1) - 1u))) return false;
-    if ((P.G >> S3_SH2) > 2048u * 256u) return false;
-    return true;
-}
-
-int msm_sort3_max_vgprs() {
-    static int cached = -1;
-    if (cached >= 0) return cached;
-    int mx = 0;
-    const void* ks[] = {(const void*)k3_l1_count<8>, (const void*)k3_l1_scatter<8>, (const void*)k3_l1_count<1>, (const void*)k3_l1_scatter<1>,
-                        (const void*)k3_l1_count<2>, (const void*)k3_l1_scatter<2>, (const void*)k3_l2_count, (const void*)k3_l2_scatter, (const void*)k3_l3};
-    for (const void* k : ks) {
-        hipFuncAttributes a;
-        if (hipFuncGetAttributes(&a, k) != hipSuccess) {
-            (void)hipGetLastError();
-            return cached = 0;
-        }
-        if (a.numRegs > mx) mx = a.numRegs;
-    }
-    return cached = mx;
-}
-
-int msm_sort3(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits) {
-    const MsmPlan& P = E.last_plan;
-    hipStream_t st = E.sort_st;
-    MsmEngine::SortBufs& B = E.sb();
-    S3Geom g;
-    g.W = P.W;
-    g.prio = exp_knob("BLAZE_SORT_PRIO", 3);
-    g.NB1 = (uint32_t)(P.G >> S3_SH1);
-    uint32_t bit = 0;
-    for (int w = 0; w < P.W; ++w) {
-        g.width[w] = P.width[w];
-        g.bitoff[w] = (uint16_t)bit;
-        g.binoff1[w] = (uint16_t)(P.boff[w] >> S3_SH1);
-        bit += P.width[w];
-    }
-    g.binoff1[P.W] = (uint16_t)(P.boff[P.W] >> S3_SH1);
-    const uint32_t NB1 = g.NB1, NB2 = (uint32_t)(P.G >> S3_SH2);
-    const uint64_t max_entries = (uint64_t)npts * P.W;
-    const uint32_t max_items = (uint32_t)(max_entries / S3_SLICE2) + NB1 + 1;
-    const uint32_t nsb = (NB2 + 2047u) / 2048u;
-    // tables: cnt1 | off1 (+1) | cur1 | cnt2 | off2 (+1) | cur2 | bsum (257) | nitems (1, padded) | map (uint2 per item)
-    const size_t tab_dw = (size_t)3 * (NB1 + 2) + (size_t)3 * (NB2 + 2) + 260 + 4 + 2 * ((size_t)max_items + 2);
-    BLZ_TRY(E.sort3_tabs.reserve(tab_dw * 4));
-    uint32_t* cnt1 = E.sort3_tabs.as<uint32_t>();
-    uint32_t* off1 = cnt1 + NB1 + 2;
-    uint32_t* cur1 = off1 + NB1 + 2;
-    uint32_t* cnt2 = cur1 + NB1 + 2;
-    uint32_t* off2 = cnt2 + NB2 + 2;
-    uint32_t* cur2 = off2 + NB2 + 2;
-    uint32_t* bsum = cur2 + NB2 + 2;
-    uint32_t* nitems = bsum + 260;
-    uint2* map = reinterpret_cast<uint2*>(nitems + 4);
-    BLZ_TRY(E.inter.reserve(max_entries * 6 + 64));
-    BLZ_TRY(E.inter2.reserve(max_entries * 5 + 64));
-    uint32_t* i1_idx = E.inter.as<uint32_t>();
-    uint16_t* i1_rem = reinterpret_cast<uint16_t*>(i1_idx + max_entries);
-    uint32_t* i2_idx = E.inter2.as<uint32_t>();
-    uint8_t* i2_lo = reinterpret_cast<uint8_t*>(i2_idx + max_entries);
-    const uint32_t* sc = (const uint32_t*)d_scalars;
-    const dim3 blk(S3_THREADS);
-
-    BLZ_HIP(hipMemsetAsync(cnt1, 0, (size_t)(NB1 + 2) * 4, st), BLZ_ERR_UNKNOWN);
-    BLZ_HIP(hipMemsetAsync(cnt2, 0, (size_t)(NB2 + 2) * 4, st), BLZ_ERR_UNKNOWN);
-    BLZ_SW_DISPATCH(sbits, hipLaunchKernelGGL(k3_l1_count<SW>, dim3((npts + S3_CNT_PTS - 1) / S3_CNT_PTS), blk, 0, st, sc, npts, g, cnt1));
-    hipLaunchKernelGGL(k3_scan_small, dim3(1), blk, 0, st, cnt1, NB1, off1, cur1, g.prio);
-    BLZ_SW_DISPATCH(sbits, {
-        const size_t lds1 = (size_t)((SW + 2) * S3_PB + 3 * 256) * 4;
-        BLZ_TRY(ensure_dynamic_lds((const void*)k3_l1_scatter<SW>, (int)lds1));
-        hipLaunchKernelGGL(k3_l1_scatter<SW>, dim3((npts + S3_PB - 1) / S3_PB), blk, lds1, st, sc, npts, g, cur1, i1_idx, i1_rem);
-    });
-    hipLaunchKernelGGL(k3_slice_map, dim3(1), blk, 0, st, off1, NB1, S3_SLICE2, map, nitems, g.prio);
-    hipLaunchKernelGGL(k3_l2_count, dim3(max_items), blk, 0, st, i1_rem, off1, map, nitems, cnt2, g.prio);
-    hipLaunchKernelGGL(k3_scan_a, dim3(nsb), blk, 0, st, cnt2, NB2, bsum, g.prio);
-    hipLaunchKernelGGL(k3_scan_b, dim3(1), blk, 0, st, bsum, nsb, g.prio);
-    hipLaunchKernelGGL(k3_scan_c, dim3(nsb), blk, 0, st, cnt2, NB2, bsum, off2, cur2, g.prio);
-    hipLaunchKernelGGL(k3_l2_scatter, dim3(max_items), blk, 0, st, i1_idx, i1_rem, off1, map, nitems, cur2, i2_idx, i2_lo, g.prio);
-    hipLaunchKernelGGL(k3_l3, dim3(NB2), blk, 0, st, i2_idx, i2_lo, off2, B.count.as<uint32_t>(), B.entries.as<uint32_t>(), g.prio);
-    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
-    return BLZ_OK;
-}
-
-// ================================================================================================ window-table tasks
-// The same three levels for plans whose windows share ONE bucket set (MsmPlan::table, msm_impl.hip.hpp k_build_window_table): W windows of c bits,
-// G = 2^(c-1) buckets, an entry carries (base * W + window) | sign.  What changes against the kernels above:
-//   * every window scatters into the same <= 256 level-1 bins (bucket >> sh1, sh1 = c - 9), so the level-1 remainder is up
-//     to 17 bits wide: 16 travel in the u16 side array, the lowest one (xs = 1) in bit 30 of the index word (indices stay
-//     below 2^30: make_table_plan);
-//   * the split of the remainder between level 2 (b2 <= 8 bits) and the final level (b3 bits, one block per 2^b3 buckets) is
-//     chosen per task so that a final block holds about 6 K entries: wide windows have few entries per bucket (2^26 bases,
-//     c = 26: 20), and 128 buckets per block would leave the blocks with 2.5 K entries and 2^18 of them;
-//   * the final level keeps bins of up to S3_R3 entries in registers as above; a larger one (c = 26: 512 buckets, 10 K
-//     entries) is counted and placed in two passes over an LDS image of the run.
-struct S3TGeom {
-    int W, prio, c;
-    uint32_t sh1, b2, b3, xs, NB1;
-};
-constexpr uint32_t S3T_IMG = 12288;   // entries of the final level's LDS image (dynamic LDS: 48 KiB)
-
-__global__ __launch_bounds__(S3_THREADS, 4) void k3t_l1_count(const uint32_t* __restrict__ scalars, uint32_t npts, S3TGeom g,
-                                                             uint32_t* __restrict__ cnt1) {
-    const int prio = g.prio;
-    S3_PRIO();
-    __shared__ uint32_t hist[256];
-    hist[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * S3_CNT_PTS;
-    uint32_t end = base + S3_CNT_PTS;
-    if (end > npts) end = npts;
-    const int cw = g.c;
-    for (uint32_t p0 = base + threadIdx.x; p0 < end; p0 += 4 * S3_THREADS) {
-        ScalarWords<8> sw[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const uint32_t p = p0 + u * S3_THREADS;
-            sw[u].load(scalars, p < end ? p : p0);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (p0 + u * S3_THREADS >= end) break;
-            uint32_t carry = 0;
-            for (int w = 0; w < g.W; ++w) {
-                const int d = sw[u].next(cw, (1u << cw) - 1u, 1u << (cw - 1), carry);
-                if (d != 0) {
-                    const uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1u;
-                    atomicAdd(&hist[b >> g.sh1], 1u);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < g.NB1) {
-        const uint32_t v = hist[threadIdx.x];
-        if (v) atomicAdd(&cnt1[threadIdx.x], v);
-    }
-}
-
-__global__ __launch_bounds__(S3_THREADS, 4) void k3t_l1_scatter(const uint32_t* __restrict__ scalars, uint32_t npts, S3TGeom g,
-                                                               uint32_t* __restrict__ cur1, uint32_t* __restrict__ o_idx,
-                                                               uint16_t* __restrict__ o_rem) {
-    const int prio = g.prio;
-    S3_PRIO();
-    extern __shared__ __attribute__((aligned(16))) uint32_t sh[];
-    uint32_t* sc = sh;                                          // [8][S3_PB]: word j of the lane's scalar u at j * PB + u * 256 + tid
-    uint2* stage = reinterpret_cast<uint2*>(sh + 8 * S3_PB);    // [S3_PB]
-    uint32_t* hist = sh + 10 * S3_PB;                           // [256]
-    uint32_t* lstart = hist + 256;
-    uint32_t* gbase = lstart + 256;
-    __shared__ uint32_t wave_tot[4];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t base = blockIdx.x * (uint32_t)S3_PB;
-#pragma unroll
-    for (int u = 0; u < S3_T; ++u) {
-        const uint32_t p = base + u * S3_THREADS + tid;
-        uint4 a = make_uint4(0, 0, 0, 0), b = make_uint4(0, 0, 0, 0);
-        if (p < npts) {
-            const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * (size_t)p;
-            a = q[0];
-            b = q[1];
-        }
-        const uint32_t i = u * S3_THREADS + tid;
-        sc[0 * S3_PB + i] = a.x; sc[1 * S3_PB + i] = a.y; sc[2 * S3_PB + i] = a.z; sc[3 * S3_PB + i] = a.w;
-        sc[4 * S3_PB + i] = b.x; sc[5 * S3_PB + i] = b.y; sc[6 * S3_PB + i] = b.z; sc[7 * S3_PB + i] = b.w;
-    }
-    const uint32_t cw = (uint32_t)g.c, mask = (1u << cw) - 1u, half = 1u << (cw - 1);
-    const uint32_t nb = g.NB1, sh1 = g.sh1, lowmask = (1u << sh1) - 1u, W = (uint32_t)g.W;
-    uint32_t carry = 0;   // bit u: the carry of the lane's scalar u into the next window
-    for (uint32_t w = 0; w < W; ++w) {
-        const uint32_t off = w * cw;
-        const uint32_t j = off >> 5, shb = off & 31u;
-        hist[tid] = 0;
-        __syncthreads();
-        uint32_t key[S3_T], rk[S3_T];   // key = low sh1 bits | bin << sh1 | sign << 31;  rk = rank in the bin, ~0 = no entry
-#pragma unroll
-        for (int u = 0; u < S3_T; ++u) {
-            const uint32_t i = u * S3_THREADS + tid;
-            const uint32_t lo = j < 8 ? sc[j * S3_PB + i] : 0u;
-            const uint32_t hi = j + 1 < 8 ? sc[(j + 1) * S3_PB + i] : 0u;
-            const uint32_t raw = (shb ? __builtin_amdgcn_alignbit(hi, lo, shb) : lo) & mask;
-            const uint32_t v = raw + ((carry >> u) & 1u);
-            int d;
-            if (v > half) { d = (int)v - (int)(half << 1); carry |= 1u << u; }
-            else { d = (int)v; carry &= ~(1u << u); }
-            rk[u] = ~0u;
-            key[u] = 0;
-            if (d != 0 && base + i < npts) {
-                const uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1u;
-                const uint32_t bin = b >> sh1;
-                key[u] = (b & lowmask) | (bin << sh1) | (d < 0 ? 0x80000000u : 0u);
-                rk[u] = atomicAdd(&hist[bin], 1u);
-            }
-        }
-        __syncthreads();
-        {
-            const uint32_t v = tid < nb ? hist[tid] : 0u;
-            uint32_t total;
-            const uint32_t excl = s3_block_excl_scan(v, wave_tot, &total);
-            if (tid < nb) {
-                lstart[tid] = excl;
-                gbase[tid] = v ? atomicAdd(&cur1[tid], v) : 0u;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < S3_T; ++u) {
-                if (rk[u] != ~0u) {
-                    const uint32_t bin = (key[u] >> sh1) & 0xffu;
-                    const uint32_t p = base + u * S3_THREADS + tid;
-                    const uint32_t rem = key[u] & lowmask;
-                    // index word: (base * W + window) | remainder bit 0 at bit 30 when the remainder has 17 bits | sign
-                    const uint32_t iw = (p * W + w) | (g.xs ? (rem & 1u) << 30 : 0u) | (key[u] & 0x80000000u);
-                    stage[lstart[bin] + rk[u]] = make_uint2(iw, (rem >> g.xs) | (bin << 16));
-                }
-            }
-            __syncthreads();
-            for (uint32_t slot = tid; slot < total; slot += S3_THREADS) {
-                const uint2 e = stage[slot];
-                const uint32_t bin = e.y >> 16;
-                const uint32_t dst = gbase[bin] + (slot - lstart[bin]);
-                o_idx[dst] = e.x;
-                o_rem[dst] = (uint16_t)e.y;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// level 2: the stored u16 is the remainder >> xs; its level-2 digit is the top b2 bits
-__global__ __launch_bounds__(S3_THREADS, 4) void k3t_l2_count(const uint16_t* __restrict__ rem, const uint32_t* __restrict__ off1,
-                                                             const uint2* __restrict__ map, const uint32_t* __restrict__ nitems,
-                                                             uint32_t* __restrict__ cnt2, S3TGeom g) {
-    const int prio = g.prio;
-    S3_PRIO();
-    __shared__ uint32_t hist[256];
-    uint32_t k, lo, hi;
-    if (!s3_item(off1, map, nitems, blockIdx.x, S3_SLICE2, k, lo, hi)) return;
-    hist[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t sh = g.b3 - g.xs;
-    uint32_t r[S3_T2];
-#pragma unroll
-    for (int t = 0; t < S3_T2; ++t) {
-        const uint32_t i = lo + t * S3_THREADS + threadIdx.x;
-        r[t] = i < hi ? rem[i] : 0xffffffffu;
-    }
-#pragma unroll
-    for (int t = 0; t < S3_T2; ++t)
-        if (r[t] != 0xffffffffu) atomicAdd(&hist[r[t] >> sh], 1u);
-    __syncthreads();
-    if (threadIdx.x < (1u << g.b2)) {
-        const uint32_t v = hist[threadIdx.x];
-        if (v) atomicAdd(&cnt2[(k << g.b2) + threadIdx.x], v);
-    }
-}
-
-__global__ __launch_bounds__(S3_THREADS, 4) void k3t_l2_scatter(const uint32_t* __restrict__ i_idx, const uint16_t* __restrict__ i_rem,
-                                                               const uint32_t* __restrict__ off1, const uint2* __restrict__ map,
-                                                               const uint32_t* __restrict__ nitems, uint32_t* __restrict__ cur2,
-                                                               uint32_t* __restrict__ o_idx, uint16_t* __restrict__ o_lo, S3TGeom g) {
-    const int prio = g.prio;
-    S3_PRIO();
-    __shared__ uint2 stage[S3_SLICE2];
-    __shared__ uint32_t hist[256], lstart[256], gbase[256];
-    __shared__ uint32_t wave_tot[4];
-    uint32_t k, lo, hi;
-    if (!s3_item(off1, map, nitems, blockIdx.x, S3_SLICE2, k, lo, hi)) return;
-    const uint32_t tid = threadIdx.x;
-    hist[tid] = 0;
-    __syncthreads();
-    const uint32_t sh = g.b3 - g.xs, lomask = (1u << sh) - 1u, nb2 = 1u << g.b2;
-    uint32_t ex[S3_T2], ky[S3_T2];   // ky = final-level bucket (b3 <= 10 bits) | level-2 digit << 10 | rank << 18; ~0 = no entry
-#pragma unroll
-    for (int t = 0; t < S3_T2; ++t) {
-        const uint32_t i = lo + t * S3_THREADS + tid;
-        ky[t] = 0xffffffffu;
-        ex[t] = 0;
-        if (i < hi) {
-            const uint32_t r = i_rem[i];
-            const uint32_t iw = i_idx[i];
-            const uint32_t h2 = r >> sh;
-            const uint32_t low = g.xs ? ((r & lomask) << 1) | ((iw >> 30) & 1u) : (r & lomask);
-            ex[t] = iw & 0xbfffffffu;
-            const uint32_t rank = atomicAdd(&hist[h2], 1u);   // < 4096
-            ky[t] = low | (h2 << 10) | (rank << 18);
-        }
-    }
-    __syncthreads();
-    const uint32_t v = tid < nb2 ? hist[tid] : 0u;
-    uint32_t total;
-    const uint32_t excl = s3_block_excl_scan(v, wave_tot, &total);
-    if (tid < nb2) {
-        lstart[tid] = excl;
-        gbase[tid] = v ? atomicAdd(&cur2[(k << g.b2) + tid], v) : 0u;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < S3_T2; ++t) {
-        if (ky[t] != 0xffffffffu) {
-            const uint32_t h2 = (ky[t] >> 10) & 0xffu;
-            stage[lstart[h2] + (ky[t] >> 18)] = make_uint2(ex[t], ky[t] & 0x3ffffu);
-        }
-    }
-    __syncthreads();
-    for (uint32_t slot = tid; slot < total; slot += S3_THREADS) {
-        const uint2 e = stage[slot];
-        const uint32_t h2 = (e.y >> 10) & 0xffu;
-        const uint32_t dst = gbase[h2] + (slot - lstart[h2]);
-        o_idx[dst] = e.x;
-        o_lo[dst] = (uint16_t)(e.y & 0x3ffu);
-    }
-}
-
-// final level: one block per level-2 bin = 2^b3 consecutive buckets (b3 <= 10).  Two builds, chosen by the task's mean bin:
+// Table: one block per level-2 bin = 2^b3 consecutive buckets (b3 <= 10).  Two builds, chosen by the task's mean bin:
 // REGS keeps a bin of up to S3_R3 entries in registers between the count and the placement (one pass over the bin, as
-// k3_l3 above; 70 VGPRs); the other one reads the bin twice - count, then place into the LDS image - and holds nothing
-// (bins of ~10 K entries: c = 26).  Both fall back to entry-by-entry placement for a bin beyond their capacity (hot buckets).
+// k3_l3 above; 78 VGPRs); the other one reads the bin twice - count, then place into the LDS image - and holds nothing
+// (bins of ~10 K entries: c = 26; 54 VGPRs).  Both fall back to entry-by-entry placement for a bin beyond their capacity
+// (hot buckets).
 template <bool REGS>
 __global__ __launch_bounds__(S3_THREADS, 4) void k3t_l3(const uint32_t* __restrict__ i_idx, const uint16_t* __restrict__ i_lo,
                                                        const uint32_t* __restrict__ off2, uint32_t* __restrict__ count,
                                                        uint32_t* __restrict__ entries, S3TGeom g, uint32_t img) {
-    const int prio = g.prio;
-    S3_PRIO();
+    s3_setprio(g.prio);
     extern __shared__ __attribute__((aligned(16))) uint32_t out[];   // [img]
     __shared__ uint32_t hist[1024], cursor[1024];
     __shared__ uint32_t wave_tot[4];
@@ -902,6 +672,23 @@ __global__ __launch_bounds__(S3_THREADS, 4) void k3t_l3(const uint32_t* __restri
     }
 }
 
+// ---------------------------------------------------------------------------------------------- host
+static S3Geom s3_geometry(const MsmPlan& P) {
+    S3Geom g;
+    g.W = P.W;
+    g.prio = exp_knob("BLAZE_SORT_PRIO", 3);
+    g.NB1 = (uint32_t)(P.G >> S3_SH1);
+    uint32_t bit = 0;
+    for (int w = 0; w < P.W; ++w) {
+        g.width[w] = P.width[w];
+        g.bitoff[w] = (uint16_t)bit;
+        g.binoff1[w] = (uint16_t)(P.boff[w] >> S3_SH1);
+        bit += P.width[w];
+    }
+    g.binoff1[P.W] = (uint16_t)(P.boff[P.W] >> S3_SH1);
+    return g;
+}
+
 static S3TGeom s3t_geometry(const MsmPlan& P, uint32_t npts) {
     S3TGeom g;
     g.W = P.W;
@@ -922,40 +709,74 @@ static S3TGeom s3t_geometry(const MsmPlan& P, uint32_t npts) {
     return g;
 }
 
-bool msm_sort3t_ok(const MsmPlan& P) {
-    if (!P.table || P.sbits < 1 || P.sbits > 256 || P.c < 16 || P.c > 26 || P.W * P.c < P.sbits + 1) return false;
-    if ((uint64_t)P.npts * P.W >= (1ull << 30)) return false;
-    const S3TGeom g = s3t_geometry(P, P.npts);
-    return g.NB1 <= 256 && g.b2 <= 8 && g.b3 >= 1 && g.b3 <= 10 && g.xs <= 1 && g.b3 > g.xs;
+bool msm_sort3_ok(const MsmPlan& P, int sbits) {
+    if (P.table) {
+        if (sbits != 256 || P.sbits < 1 || P.sbits > 256 || P.c < 16 || P.c > 26 || P.W * P.c < P.sbits + 1) return false;
+        if ((uint64_t)P.npts * P.W >= (1ull << 30)) return false;
+        const S3TGeom g = s3t_geometry(P, P.npts);
+        return g.NB1 <= 256 && g.b2 <= 8 && g.b3 >= 1 && g.b3 <= 10 && g.xs <= 1 && g.b3 > g.xs;
+    }
+    if ((sbits != 256 && sbits != 64 && sbits != 32) || P.W < 1) return false;
+    for (int w = 0; w < P.W; ++w)
+        if (P.width[w] < S3_SH1 + 1 || P.width[w] > 23) return false;   // every window a whole number of level-1 bins, <= 256 of them
+    if ((P.G >> S3_SH1) > S3_MAXNB1 || (P.G & ((1u << S3_SH1) - 1u))) return false;
+    if ((P.G >> S3_SH2) > 2048u * 256u) return false;
+    return true;
 }
 
-int msm_sort3t_max_vgprs() {
-    static int cached = -1;
-    if (cached >= 0) return cached;
+int msm_sort3_max_vgprs(bool table) {
+    using L2 = S3Geom::L2;
+    static const void* const plain_ks[] = {(const void*)k3_l1_count<S3Geom, 8>, (const void*)k3_l1_scatter<S3Geom, 8>,
+                                           (const void*)k3_l1_count<S3Geom, 1>, (const void*)k3_l1_scatter<S3Geom, 1>,
+                                           (const void*)k3_l1_count<S3Geom, 2>, (const void*)k3_l1_scatter<S3Geom, 2>,
+                                           (const void*)k3_l2_count<L2>, (const void*)k3_l2_scatter<L2>, (const void*)k3_l3};
+    static const void* const table_ks[] = {(const void*)k3_l1_count<S3TGeom, 8>, (const void*)k3_l1_scatter<S3TGeom, 8>,
+                                           (const void*)k3_l2_count<S3TGeom>, (const void*)k3_l2_scatter<S3TGeom>,
+                                           (const void*)k3t_l3<true>, (const void*)k3t_l3<false>};
+    static int cached[2] = {-1, -1};
+    int& c = cached[table ? 1 : 0];
+    if (c >= 0) return c;
+    const void* const* ks = table ? table_ks : plain_ks;
+    const size_t n = table ? sizeof(table_ks) / sizeof(*table_ks) : sizeof(plain_ks) / sizeof(*plain_ks);
     int mx = 0;
-    const void* ks[] = {(const void*)k3t_l1_count, (const void*)k3t_l1_scatter, (const void*)k3t_l2_count, (const void*)k3t_l2_scatter,
-                        (const void*)k3t_l3<true>, (const void*)k3t_l3<false>};
-    for (const void* k : ks) {
+    for (size_t i = 0; i < n; ++i) {
         hipFuncAttributes a;
-        if (hipFuncGetAttributes(&a, k) != hipSuccess) {
+        if (hipFuncGetAttributes(&a, ks[i]) != hipSuccess) {
             (void)hipGetLastError();
-            return cached = 0;
+            return c = 0;
         }
         if (a.numRegs > mx) mx = a.numRegs;
     }
-    return cached = mx;
+    return c = mx;
 }
 
-int msm_sort3t(MsmEngine& E, const void* d_scalars, uint32_t npts) {
+// level 1 of a task: count, scan of the bins, scatter
+template <class Geom, int NW>
+static int s3_level1(hipStream_t st, const uint32_t* sc, uint32_t npts, const Geom& g, uint32_t* cnt1, uint32_t* off1, uint32_t* cur1,
+                     uint32_t* i1_idx, uint16_t* i1_rem) {
+    const dim3 blk(S3_THREADS);
+    const size_t lds1 = (size_t)((NW + 2) * S3_PB + 3 * 256) * 4;
+    hipLaunchKernelGGL((k3_l1_count<Geom, NW>), dim3((npts + S3_CNT_PTS - 1) / S3_CNT_PTS), blk, 0, st, sc, npts, g, cnt1);
+    hipLaunchKernelGGL(k3_scan_small, dim3(1), blk, 0, st, cnt1, g.NB1, off1, cur1, g.prio);
+    BLZ_TRY(ensure_dynamic_lds((const void*)k3_l1_scatter<Geom, NW>, (int)lds1));
+    hipLaunchKernelGGL((k3_l1_scatter<Geom, NW>), dim3((npts + S3_PB - 1) / S3_PB), blk, lds1, st, sc, npts, g, cur1, i1_idx, i1_rem);
+    return BLZ_OK;
+}
+
+// geometry -> tables -> launches, for either kind of plan
+template <class Geom>
+static int s3_enqueue(MsmEngine& E, const Geom& g, const void* d_scalars, uint32_t npts, int sbits) {
+    using L2 = typename Geom::L2;
+    using Lo = typename L2::Lo;
     const MsmPlan& P = E.last_plan;
     hipStream_t st = E.sort_st;
     MsmEngine::SortBufs& B = E.sb();
-    const S3TGeom g = s3t_geometry(P, P.npts);
-    const uint32_t NB1 = g.NB1, NB2 = (uint32_t)(P.G >> g.b3);
+    const uint32_t NB1 = g.NB1, NB2 = (uint32_t)(P.G >> g.bits3());
     const uint64_t max_entries = (uint64_t)npts * P.W;
     const uint32_t max_items = (uint32_t)(max_entries / S3_SLICE2) + NB1 + 1;
     const uint32_t nsb = (NB2 + 2047u) / 2048u;
-    if (nsb > 256) return fail(BLZ_ERR_UNKNOWN, "window-table sort: %u final-level bins exceed the scan's range", NB2);
+    if (Geom::TABLE && nsb > 256) return fail(BLZ_ERR_UNKNOWN, "window-table sort: %u final-level bins exceed the scan's range", NB2);
+    // tables: cnt1 | off1 (+1) | cur1 | cnt2 | off2 (+1) | cur2 | bsum (257) | nitems (1, padded) | map (uint2 per item)
     const size_t tab_dw = (size_t)3 * (NB1 + 2) + (size_t)3 * (NB2 + 2) + 260 + 4 + 2 * ((size_t)max_items + 2);
     BLZ_TRY(E.sort3_tabs.reserve(tab_dw * 4));
     uint32_t* cnt1 = E.sort3_tabs.as<uint32_t>();
@@ -968,40 +789,48 @@ int msm_sort3t(MsmEngine& E, const void* d_scalars, uint32_t npts) {
     uint32_t* nitems = bsum + 260;
     uint2* map = reinterpret_cast<uint2*>(nitems + 4);
     BLZ_TRY(E.inter.reserve(max_entries * 6 + 64));
-    BLZ_TRY(E.inter2.reserve(max_entries * 6 + 64));
+    BLZ_TRY(E.inter2.reserve(max_entries * (4 + sizeof(Lo)) + 64));
     uint32_t* i1_idx = E.inter.as<uint32_t>();
     uint16_t* i1_rem = reinterpret_cast<uint16_t*>(i1_idx + max_entries);
     uint32_t* i2_idx = E.inter2.as<uint32_t>();
-    uint16_t* i2_lo = reinterpret_cast<uint16_t*>(i2_idx + max_entries);
+    Lo* i2_lo = reinterpret_cast<Lo*>(i2_idx + max_entries);
+    uint32_t* count = B.count.as<uint32_t>();
+    uint32_t* entries = B.entries.as<uint32_t>();
     const uint32_t* sc = (const uint32_t*)d_scalars;
     const dim3 blk(S3_THREADS);
-    // LDS image of a final-level bin: the register path's 7168 entries unless the mean bin is larger than that
-    const double mean_bin = (double)max_entries / (double)(NB2 ? NB2 : 1);
-    const bool big_bins = mean_bin * 1.1 > (double)S3_R3;
-    const uint32_t img = big_bins ? S3T_IMG : S3_R3;
+    const L2 g2 = g.l2();
 
     BLZ_HIP(hipMemsetAsync(cnt1, 0, (size_t)(NB1 + 2) * 4, st), BLZ_ERR_UNKNOWN);
     BLZ_HIP(hipMemsetAsync(cnt2, 0, (size_t)(NB2 + 2) * 4, st), BLZ_ERR_UNKNOWN);
-    hipLaunchKernelGGL(k3t_l1_count, dim3((npts + S3_CNT_PTS - 1) / S3_CNT_PTS), blk, 0, st, sc, npts, g, cnt1);
-    hipLaunchKernelGGL(k3_scan_small, dim3(1), blk, 0, st, cnt1, NB1, off1, cur1, g.prio);
-    const size_t lds1 = (size_t)(10 * S3_PB + 3 * 256) * 4;
-    BLZ_TRY(ensure_dynamic_lds((const void*)k3t_l1_scatter, (int)lds1));
-    hipLaunchKernelGGL(k3t_l1_scatter, dim3((npts + S3_PB - 1) / S3_PB), blk, lds1, st, sc, npts, g, cur1, i1_idx, i1_rem);
+    if constexpr (Geom::TABLE) {   // (256-bit scalars only: begin() refuses anything else)
+        BLZ_TRY((s3_level1<Geom, 8>(st, sc, npts, g, cnt1, off1, cur1, i1_idx, i1_rem)));
+    } else {
+        BLZ_SW_DISPATCH(sbits, BLZ_TRY((s3_level1<Geom, SW>(st, sc, npts, g, cnt1, off1, cur1, i1_idx, i1_rem))));
+    }
     hipLaunchKernelGGL(k3_slice_map, dim3(1), blk, 0, st, off1, NB1, S3_SLICE2, map, nitems, g.prio);
-    hipLaunchKernelGGL(k3t_l2_count, dim3(max_items), blk, 0, st, i1_rem, off1, map, nitems, cnt2, g);
+    hipLaunchKernelGGL(k3_l2_count<L2>, dim3(max_items), blk, 0, st, i1_rem, off1, map, nitems, cnt2, g2);
     hipLaunchKernelGGL(k3_scan_a, dim3(nsb), blk, 0, st, cnt2, NB2, bsum, g.prio);
     hipLaunchKernelGGL(k3_scan_b, dim3(1), blk, 0, st, bsum, nsb, g.prio);
     hipLaunchKernelGGL(k3_scan_c, dim3(nsb), blk, 0, st, cnt2, NB2, bsum, off2, cur2, g.prio);
-    hipLaunchKernelGGL(k3t_l2_scatter, dim3(max_items), blk, 0, st, i1_idx, i1_rem, off1, map, nitems, cur2, i2_idx, i2_lo, g);
-    if (big_bins) {
-        BLZ_TRY(ensure_dynamic_lds((const void*)k3t_l3<false>, (int)(img * 4)));
-        hipLaunchKernelGGL(k3t_l3<false>, dim3(NB2), blk, (size_t)img * 4, st, i2_idx, i2_lo, off2, B.count.as<uint32_t>(), B.entries.as<uint32_t>(), g, img);
+    hipLaunchKernelGGL(k3_l2_scatter<L2>, dim3(max_items), blk, 0, st, i1_idx, i1_rem, off1, map, nitems, cur2, i2_idx, i2_lo, g2);
+    if constexpr (Geom::TABLE) {
+        // LDS image of a final-level bin: the register path's 7168 entries unless the mean bin is larger than that
+        const double mean_bin = (double)max_entries / (double)(NB2 ? NB2 : 1);
+        const bool big_bins = mean_bin * 1.1 > (double)S3_R3;
+        const uint32_t img = big_bins ? S3T_IMG : S3_R3;
+        auto l3 = big_bins ? k3t_l3<false> : k3t_l3<true>;
+        BLZ_TRY(ensure_dynamic_lds((const void*)l3, (int)(img * 4)));
+        hipLaunchKernelGGL(l3, dim3(NB2), blk, (size_t)img * 4, st, i2_idx, i2_lo, off2, count, entries, g, img);
     } else {
-        BLZ_TRY(ensure_dynamic_lds((const void*)k3t_l3<true>, (int)(img * 4)));
-        hipLaunchKernelGGL(k3t_l3<true>, dim3(NB2), blk, (size_t)img * 4, st, i2_idx, i2_lo, off2, B.count.as<uint32_t>(), B.entries.as<uint32_t>(), g, img);
+        hipLaunchKernelGGL(k3_l3, dim3(NB2), blk, 0, st, i2_idx, i2_lo, off2, count, entries, g.prio);
     }
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     return BLZ_OK;
+}
+
+int msm_sort3(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits) {
+    const MsmPlan& P = E.last_plan;
+    return P.table ? s3_enqueue(E, s3t_geometry(P, P.npts), d_scalars, npts, sbits) : s3_enqueue(E, s3_geometry(P), d_scalars, npts, sbits);
 }
 
 }  // namespace blz

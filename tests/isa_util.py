@@ -11,11 +11,11 @@ MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
 def tools_available() -> bool:
-    return all(os.path.exists(os.path.join(LLVM, t)) for t in ("llvm-objcopy", "llvm-objdump", "clang-offload-bundler"))
+    return all(os.path.exists(os.path.join(LLVM, t)) for t in ("llvm-objcopy", "llvm-objdump", "llvm-readelf", "clang-offload-bundler"))
 
 
-def disassemble_library(lib_path: str) -> str:
-    """Concatenated `llvm-objdump -d` text of every gfx950 code object in the library."""
+def disassemble_library(lib_path: str, tool: str = "llvm-objdump", flag: str = "-d") -> str:
+    """Concatenated `llvm-objdump -d` text (or another LLVM tool's output) of every gfx950 code object in the library."""
     out = []
     with tempfile.TemporaryDirectory() as td:
         fat = os.path.join(td, "fat.bin")
@@ -31,8 +31,15 @@ def disassemble_library(lib_path: str) -> str:
                                 "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], capture_output=True)
             if r.returncode != 0 or not os.path.exists(co) or os.path.getsize(co) == 0:
                 continue
-            out.append(subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", co], capture_output=True, text=True).stdout)
+            out.append(subprocess.run([os.path.join(LLVM, tool), flag, co], capture_output=True, text=True).stdout)
     return "\n".join(out)
+
+
+def kernel_vgprs(lib_path: str) -> dict:
+    """{mangled kernel name: .vgpr_count} from the metadata notes of every gfx950 code object in the library."""
+    notes = disassemble_library(lib_path, "llvm-readelf", "--notes")
+    # (a kernel's map is sorted by key: .name comes before .vgpr_count, and no other key of the map ends in 'name')
+    return {n: int(v) for n, v in re.findall(r"^\s+\.name:\s+(\S+)\n(?:(?!\s+\.name:).*\n)*?\s+\.vgpr_count:\s+(\d+)", notes, re.M)}
 
 
 def function_instructions(text: str, mangled: str):
