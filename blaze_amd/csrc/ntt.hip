@@ -9,6 +9,8 @@
 //   pass 3: A-point NTTs over i0 (contiguous), written to the natural address k2 + C k1 + CB k0
 // A pass stages a tile of COLS adjacent columns x radix rows in LDS (COLS*32 B contiguous per row
 // access), runs the radix-2 stages there and applies the inter-pass twiddle on the way out.
+// A handle with a coset shift g (blz_ntt_set_coset) computes X[k] = sum_i x[i] g^i w^(ik) - or the exact inverse - in the same three
+// launches: the powers of g ride on the passes' own factors (ntt_engine.hpp NttCoset).
 // Data stay in plain canonical form; only twiddles are in Montgomery form (mont_mul(x, tR) = x t),
 // so there is no conversion pass.  Algorithmic traffic 2 x 4 GiB; this 3-pass form moves 3x that.
 #include <atomic>
@@ -78,6 +80,13 @@ struct blz_ntt {
     DevBuf buf[2], scratch, tables, tables_rr, table_b;
     NttTables T{};
     NttTablesRR TR{};
+    // blz_ntt_set_coset: the shift in force (1 = the plain transform), its tables (allocated by the first shift that is not 1)
+    bool coset = false;
+    uint8_t shift[32] = {1};
+    DevBuf tables_cs;
+    NttCoset CS{};
+    bool cs_wire = false;       // the 512-point kernel is the wire pass of a forward handle: CS.tG exists
+    uint32_t* cs_stage = nullptr;   // device: s | the caller's shift | the check's flag
     bool in_flight = false;
     int in_flight_buf = -1;   // buffer under transform while in_flight
     float last_ms = 0.f;
@@ -195,7 +204,7 @@ int ntt_setup(blz_ntt* h) {
 }
 
 int launch_pass(blz_ntt* h, int pass, const void* in, void* out) {
-    return h->ops->pass(pass, h->stream, in, out, h->geom, h->T, h->TR, h->cols_log[pass - 1], h->force_generic);
+    return h->ops->pass(pass, h->stream, in, out, h->geom, h->T, h->TR, h->cols_log[pass - 1], h->force_generic, h->coset ? &h->CS : nullptr);
 }
 
 }  // namespace
@@ -266,7 +275,7 @@ void blz_ntt_free(blz_ntt* h) {
         delete h;
         return;
     }
-    h->buf[0].release(); h->buf[1].release(); h->scratch.release(); h->tables.release(); h->tables_rr.release(); h->table_b.release();
+    h->buf[0].release(); h->buf[1].release(); h->scratch.release(); h->tables.release(); h->tables_rr.release(); h->table_b.release(); h->tables_cs.release();
     for (auto& e : h->xchg_ev)
         if (e) (void)hipEventDestroy(e);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -525,15 +534,87 @@ int blz_ntt_exchange(blz_ntt* h, size_t buf, const uint8_t* next_in, size_t in_l
     return BLZ_OK;
 }
 
-// out = {device bytes this handle holds (two transform buffers, scratch, twiddle and factor tables), 1 when pass 2 READS its
+// out = {device bytes this handle holds (two transform buffers, scratch, twiddle and factor tables, a coset handle's tables), 1 when pass 2 READS its
 // boundary factors from the per-element table (2^27 transforms with memory for it) / 0 when it steps them, 1 when pass 1 reads the
 // column-independent boundary table, log_size}
 int blz_ntt_info(blz_ntt* h, uint64_t out[4]) {
     if (!h || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
-    out[0] = (uint64_t)(h->buf[0].cap + h->buf[1].cap + h->scratch.cap + h->tables.cap + h->tables_rr.cap + h->table_b.cap);
+    out[0] = (uint64_t)(h->buf[0].cap + h->buf[1].cap + h->scratch.cap + h->tables.cap + h->tables_rr.cap + h->table_b.cap + h->tables_cs.cap);
     out[1] = h->TR.tB ? 1u : 0u;
     out[2] = h->TR.tA ? 1u : 0u;
     out[3] = (uint64_t)h->logn;
+    return BLZ_OK;
+}
+
+// Coset transforms (include/blaze_hip.h).  The shift is checked on the device (k_ntt_cs_base) BEFORE any table is touched; the
+// tables that carry it - NttCoset's, and pass 2's ts2 / tB where that pass owes a part of it (ntt_engine.hpp) - are rebuilt on the
+// compute stream, which is idle: a transform in flight refuses the call.
+static int ntt_coset_carve(blz_ntt* h) {
+    if (h->tables_cs.p) return BLZ_OK;
+    NttCoset probe{};
+    h->cs_wire = h->ops->coset_plan(h->geom, h->inverse, h->force_generic, probe);
+    BLZ_TRY(h->tables_cs.reserve(NTT_CS_SMALL_BYTES + (h->cs_wire ? NTT_CS_WIRE_BYTES : 0), true));
+    uint32_t* p = h->tables_cs.as<uint32_t>();
+    h->CS.d0 = p; p += 2 * 512 * 8;   // (an inverse handle's: with n^-1, then the pure powers)
+    h->CS.d1 = p; p += 512 * 8;
+    h->CS.d2 = p; p += 512 * 8;
+    h->CS.u0 = p; p += 512 * NTT_RR_ENTRY_DWORDS;
+    h->CS.u1 = p; p += 512 * NTT_RR_ENTRY_DWORDS;
+    h->CS.u2 = p; p += 512 * NTT_RR_ENTRY_DWORDS;
+    h->CS.finr = p; p += 512 * NTT_RR_ENTRY_DWORDS;
+    h->cs_stage = p; p += 4 * 8;
+    h->CS.tG = h->cs_wire ? p : nullptr;
+    return BLZ_OK;
+}
+
+int blz_ntt_set_coset(blz_ntt* h, const uint8_t* shift) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    BLZ_NTT_LIVE(h);
+    if (h->in_flight) return fail(BLZ_ERR_INVALID_PARAM, "a transform is running (its kernels read the tables); call wait_result first");
+    static const uint8_t one[32] = {1};
+    const bool plain = !shift || memcmp(shift, one, 32) == 0;
+    BLZ_TRY(use_device(h->device));
+    if (plain) {
+        if (!h->coset) return BLZ_OK;
+        if (h->CS.mode[1] == 2) {
+            BLZ_TRY(h->ops->coset_unfold(h->stream, h->T, h->TR, h->geom));
+            BLZ_NTT_WAIT(h, sync_stream_bounded(h->stream, "set_coset: the plain transform's tables"));
+        }
+        h->coset = false;
+        memcpy(h->shift, one, 32);
+        return BLZ_OK;
+    }
+    const bool fresh = !h->tables_cs.p;
+    BLZ_TRY(ntt_coset_carve(h));
+    uint32_t* const d_s = h->cs_stage;
+    uint32_t* const d_shift = h->cs_stage + 8;
+    uint32_t* const d_flag = h->cs_stage + 16;
+    BLZ_HIP(hipMemsetAsync(d_flag, 0, 4, h->stream), BLZ_ERR_UNKNOWN);
+    BLZ_HIP(hipMemcpyAsync(d_shift, shift, 32, hipMemcpyHostToDevice, h->stream), BLZ_ERR_WRITE);
+    BLZ_TRY(h->ops->coset_check(h->stream, d_shift, d_s, d_flag, h->inverse));
+    BLZ_NTT_WAIT(h, sync_stream_bounded(h->stream, "set_coset: shift check"));
+    uint32_t bad = 0;
+    BLZ_HIP(hipMemcpy(&bad, d_flag, 4, hipMemcpyDeviceToHost), BLZ_ERR_READ);
+    if (bad) {
+        if (fresh) {   // a refused call changes nothing: not the bytes blz_ntt_info reports either
+            h->tables_cs.release();
+            h->CS = NttCoset{};
+            h->cs_stage = nullptr;
+        }
+        return fail(BLZ_ERR_INVALID_PARAM, "the coset shift is not a non-zero canonical element of the field (0 < shift < r)");
+    }
+    (void)h->ops->coset_plan(h->geom, h->inverse, h->force_generic, h->CS);
+    BLZ_TRY(h->ops->coset_tables(h->stream, h->T, h->TR, h->geom, h->CS, d_s));
+    BLZ_NTT_WAIT(h, sync_stream_bounded(h->stream, "set_coset: tables"));
+    h->coset = true;
+    memcpy(h->shift, shift, 32);
+    return BLZ_OK;
+}
+
+int blz_ntt_get_coset(blz_ntt* h, uint8_t out[32]) {
+    if (!h || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    BLZ_NTT_LIVE(h);
+    memcpy(out, h->shift, 32);
     return BLZ_OK;
 }
 

@@ -26,8 +26,10 @@ struct NttTablesRR {
     uint32_t* fin;   // closing factor of the last pass: n^-1 R_rr (inverse) or nullptr (forward: no product)
     uint32_t* tA;    // w^(A e), e < 2^18 (n / 512 entries, 10 MiB), or nullptr: the boundary factor after pass 1 that
                      // does not depend on the column, read instead of stepped (2^27 transforms only; ntt_rr.hip.hpp)
-    uint32_t* ts2;   // w^(64 C i0), i0 < 512: the step of pass 2's boundary factor along a lane's rows (one per column)
-    uint32_t* tB;    // pass 2's boundary factor of EVERY element, w^((C k1 + k2) i0) R_rr mod m as 8 words at the element's own index
+    uint32_t* ts2;   // w^(64 C i0), i0 < 512: the step of pass 2's boundary factor along a lane's rows (one per column); times
+                     // s^(64 C) on an inverse coset handle whose pass 2 carries a part of the shift (NttCoset below)
+    uint32_t* tB;    // pass 2's boundary factor of EVERY element, w^((C k1 + k2) i0) R_rr mod m (times the part of a coset handle's shift
+                     // that pass 2 carries) as 8 words, in the order pass 2 consumes them
                      // (n x 32 bytes: 4 GiB at 2^27), or nullptr: stepped along the lane's rows (ntt_rr.hip.hpp)
     uint32_t swz;    // 0: plain tile order; 1 + s: pass 1 walks its tiles in the channel-spreading order with 2^s adjacent column
                      // groups back to back (2^27 transforms; ntt_rr.hip.hpp)
@@ -36,6 +38,28 @@ constexpr size_t NTT_RR_BOUNDARY_ENTRIES = (size_t)1 << 18;
 constexpr size_t NTT_RR_ENTRY_DWORDS = 10;
 constexpr size_t NTT_RR_TABLE_BYTES = (4 * 512 * 2 + 3 * 512 + 1) * NTT_RR_ENTRY_DWORDS * 4;   // 4 Shoup tables (wpass x 3, ts2: 2 entries' worth each), 3 Montgomery, fin
 constexpr size_t NTT_RR_BOUNDARY_BYTES = NTT_RR_BOUNDARY_ENTRIES * 2 * NTT_RR_ENTRY_DWORDS * 4;   // tA, Shoup entries
+
+// Tables of a coset handle (blz_ntt_set_coset): powers of s = g (forward) or g^-1 (inverse).  With i = i0 + A i1 + AB i2 and
+// k = k2 + C k1 + CB k0 (ntt.hip):
+//   forward  X[k] = sum_i x[i] g^i w^(i k): the wire pass multiplies the element as loaded.  Where that pass is the radix-2-in-LDS
+//            kernel it takes the whole g^i (d0 d1 d2); where it is the 512-point kernel it takes ONE Shoup entry, tG: g^(i0 + A i1)
+//            at 2^18 (pass 2: the whole factor) and g^(A (i1 + B i2)) at 2^27 (pass 1), where the rest, g^i0 - constant along the
+//            indices passes 1 and 2 transform over - joins pass 2's boundary factor (its start value, or the table tB);
+//   inverse  x[k] = g^-k n^-1 sum_i X[i] w^(-i k): the last pass closes with a product anyway.  The radix-2-in-LDS kernel takes
+//            n^-1 s^k there (d0 carries n^-1); the 512-point kernel takes n^-1 s^(CB k0) by output row (finr), and s^(k2 + C k1) -
+//            constant along the index pass 3 transforms over - joins pass 2's boundary factor (start value and step ts2, or tB).
+struct NttCoset {
+    uint32_t *d0, *d1, *d2;   // 32-bit Montgomery: s^e = d0[e & 511] d1[(e >> 9) & 511] d2[e >> 18]  (inverse: d0 carries n^-1)
+    uint32_t *u0, *u1, *u2;   // the same three powers (no n^-1) in the reduced radix, Montgomery R_rr
+    uint32_t* tG;             // Shoup entries, 2^18: s^(e << gshift), e = (logical index) >> gshift; or nullptr
+    uint32_t* finr;           // n^-1 s^(CB k0), k0 < 512, Montgomery R_rr (inverse)
+    int gshift;               // 0 at 2^18, logA at 2^27
+    int inverse;
+    int mode[3];              // per pass: 0 the plain kernel, 1 product on the element as loaded, 2 pass 2 with the folded boundary
+                              // factor, 3 the closing product of an inverse transform
+};
+constexpr size_t NTT_CS_SMALL_BYTES = (size_t)(4 * 512 * 8 + 4 * 512 * NTT_RR_ENTRY_DWORDS + 4 * 8) * 4;   // d0 (x 2: with / without n^-1), d1, d2; u0..u2, finr; the set-up's words (s, the caller's shift, the check's flag)
+constexpr size_t NTT_CS_WIRE_BYTES = NTT_RR_BOUNDARY_BYTES;   // tG
 
 struct NttGeom {
     int logA, logB, logC, logn;
@@ -52,8 +76,18 @@ struct NttFieldOps {
     // canonical field element, 2 it is not a primitive 2^logn-th root of unity
     int (*setup)(hipStream_t st, NttTables& T, NttTablesRR& TR, const NttGeom& g, int inverse, const uint32_t* user_root, uint32_t* flag);
     // one of the three passes; cols_log is the tile width of the radix-2-in-LDS kernel
+    // cs: the coset tables of a handle with a shift in force (its mode[] selects the kernels), or nullptr: the plain transform
     int (*pass)(int pass, hipStream_t st, const void* in, void* out, const NttGeom& g, const NttTables& T, const NttTablesRR& TR,
-                int cols_log, bool force_generic);
+                int cols_log, bool force_generic, const NttCoset* cs);
+    // which pass carries which part of the shift (cs.mode, cs.gshift, cs.inverse); true when the 512-point kernel's wire pass
+    // needs tG
+    bool (*coset_plan)(const NttGeom& g, int inverse, bool force_generic, NttCoset& cs);
+    // the shift (8 words at d_shift) checked (*flag: 1 = not in (0, r)) and turned into s at d_s; nothing else is written
+    int (*coset_check)(hipStream_t st, const uint32_t* d_shift, uint32_t* d_s, uint32_t* flag, int inverse);
+    // every table of cs from s, and pass 2's folded factors (ts2, tB) where cs.mode says so
+    int (*coset_tables)(hipStream_t st, const NttTables& T, const NttTablesRR& TR, const NttGeom& g, const NttCoset& cs, const uint32_t* d_s);
+    // ts2 and tB of the plain transform again
+    int (*coset_unfold)(hipStream_t st, const NttTables& T, const NttTablesRR& TR, const NttGeom& g);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

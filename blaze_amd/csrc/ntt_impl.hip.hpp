@@ -140,9 +140,21 @@ BLZ_DEV uint32_t ntt_rs(uint32_t cols) { return cols * 8u + 8u; }
 //   after pass 2: x(i0, k1, k2) *= w^(C i0 k1)             step along i0: w^(C k1)
 // so a lane that owns a few adjacent columns of one row derives its twiddles by repeated
 // multiplication from one table look-up.
-template <class Fr, int PASS>
-__global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
-                                                          NttGeom g, NttTables T, int cols_log) {
+// CS: the coset variants (NttCoset; k_ntt_pass_cs below), 0 = the plain transform.  1: the wire pass of a forward coset
+// transform, every element as loaded times s^(its logical index); 3: the last pass of an inverse one, the closing factor is
+// n^-1 s^(the output's logical index).
+template <class E>
+BLZ_DEV void cs_pow(E& r, const NttCoset& cs, uint32_t e) {
+    E a, b;
+    fp_load(r, cs.d0 + (size_t)(e & 511u) * 8);
+    uint32_t e1 = (e >> 9) & 511u, e2 = e >> 18;
+    if (e1) { fp_load(a, cs.d1 + (size_t)e1 * 8); fp_mul(r, r, a); }
+    if (e2) { fp_load(b, cs.d2 + (size_t)e2 * 8); fp_mul(r, r, b); }
+}
+template <class Fr, int PASS, int CS>
+BLZ_DEV void ntt_pass_body(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, const NttGeom& g, const NttTables& T,
+                           int cols_log, const NttCoset& cs) {
+    static_assert(CS == 0 || CS == 1 || (CS == 3 && PASS == 3), "no such coset variant");
     using E = Fp<Fr>;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int lr = PASS == 1 ? g.logC : PASS == 2 ? g.logB : g.logA;  // log radix of this pass
@@ -182,9 +194,15 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const uint32_t* __rest
         else { col = e & (COLS - 1); row = e >> cols_log; }         // contiguous along cols
         E x;
         uint64_t iaddr = in_base + row * in_rstride + col * in_cstride;
+        [[maybe_unused]] const uint64_t logical = iaddr;
         if (PASS == g.wire_pass && g.brin) iaddr = __brevll(iaddr) >> (64 - g.logn);   // the caller's buffer is in bit-reversed order
         fp_load(x, in + iaddr * 8);
         if (PASS == g.wire_pass) NttOps<E>::wire_in(x);
+        if constexpr (CS == 1) {
+            E f;
+            cs_pow(f, cs, (uint32_t)logical);
+            NttOps<E>::mul(x, x, f);
+        }
         uint32_t rrow = lr ? (__brev(row) >> (32 - lr)) : 0;
         lds_store(lds, rrow * RS + col * 8, x);
     }
@@ -242,9 +260,10 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const uint32_t* __rest
             uint64_t oaddr;
             if (PASS == 3) {
                 // element (k0 = row, k1 = fixed, k2 = col_base + col) -> natural address k2 + C k1 + CB k0
-                if (T.ninv) { E s; fp_load(s, T.ninv); NttOps<E>::mul(x, x, s); }  // inverse transform: * n^-1
-                NttOps<E>::canon(x);                                               // the wire format is canonical
                 oaddr = (col_base + col0 + j) + (uint64_t)C * fixed + (uint64_t)C * B * row;
+                if constexpr (CS == 3) { E s; cs_pow(s, cs, (uint32_t)oaddr); NttOps<E>::mul(x, x, s); }   // * n^-1 s^k
+                else if (T.ninv) { E s; fp_load(s, T.ninv); NttOps<E>::mul(x, x, s); }  // inverse transform: * n^-1
+                NttOps<E>::canon(x);                                               // the wire format is canonical
                 if (g.brout) oaddr = __brevll(oaddr) >> (64 - g.logn);
             } else {
                 if (tw) {
@@ -256,6 +275,38 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const uint32_t* __rest
             fp_store(out + oaddr * 8, x);
         }
     }
+}
+
+template <class Fr, int PASS>
+__global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                          NttGeom g, NttTables T, int cols_log) {
+    ntt_pass_body<Fr, PASS, 0>(in, out, g, T, cols_log, NttCoset{});
+}
+template <class Fr, int PASS, int CS>
+__global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass_cs(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                             NttGeom g, NttTables T, int cols_log, NttCoset cs) {
+    ntt_pass_body<Fr, PASS, CS>(in, out, g, T, cols_log, cs);
+}
+
+// A coset handle's shift, checked like the caller's root (k_ntt_root): *flag = 1 unless 0 < shift < r; s = the shift (forward) or
+// its inverse (inverse handles), Montgomery form.  Nothing but *flag is written for a refused value.
+template <class Fr>
+__global__ void k_ntt_cs_base(uint32_t* s_out, uint32_t* flag, const uint32_t* shift, int inverse) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    using E = Fp<Fr>;
+    E x;
+    fp_load(x, shift);
+    bool lt = false, nz = false;   // x < m, x != 0
+    for (int i = Fr::N - 1; i >= 0; --i) nz = nz || x.v[i] != 0;
+    for (int i = Fr::N - 1; i >= 0; --i) {
+        if (x.v[i] != Fr::MOD[i]) { lt = x.v[i] < Fr::MOD[i]; break; }
+    }
+    if (!lt || !nz) { *flag = 1u; return; }
+    E s;
+    fp_to_mont(s, x);
+    if (inverse) { E si; fp_inv(si, s); s = si; }
+    fp_reduce(s);
+    fp_store(s_out, s);
 }
 
 
@@ -298,15 +349,53 @@ int ntt_setup_t(hipStream_t st, NttTables& T, NttTablesRR& TR, const NttGeom& g,
     return BLZ_OK;
 }
 
+// does pass `pass` run the 512-point kernel?
+inline bool ntt_pass_is_512(int pass, const NttGeom& g, bool force_generic) {
+    const int lr = pass == 1 ? g.logC : pass == 2 ? g.logB : g.logA;
+    const int cols_avail = pass == 3 ? g.logC : g.logA;  // extent of the tile's column index
+    return lr == 9 && cols_avail >= NR_COLS_LOG && !force_generic;
+}
+
+template <class Fr, int PASS, int CS>
+int ntt_launch_512_cs(hipStream_t st, const void* in, void* out, const NttGeom& g, const NttTablesRR& TR, const NttCoset& cs,
+                      unsigned tiles, size_t lds) {
+    BLZ_TRY(ensure_dynamic_lds((const void*)k_ntt512_rr_cs<Fr, PASS, CS>, 160 * 1024));
+    hipLaunchKernelGGL((k_ntt512_rr_cs<Fr, PASS, CS>), dim3(tiles), dim3(NR_THREADS), lds, st, (const uint32_t*)in, (uint32_t*)out, g, TR, cs);
+    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
+    return BLZ_OK;
+}
+template <class Fr, int PASS, int CS>
+int ntt_launch_pass_cs(hipStream_t st, const void* in, void* out, const NttGeom& g, const NttTables& T, int cl, const NttCoset& cs,
+                       unsigned tiles, size_t lds) {
+    BLZ_TRY(ensure_dynamic_lds((const void*)k_ntt_pass_cs<Fr, PASS, CS>, 160 * 1024));
+    hipLaunchKernelGGL((k_ntt_pass_cs<Fr, PASS, CS>), dim3(tiles), dim3(NTT_THREADS), lds, st, (const uint32_t*)in, (uint32_t*)out, g, T, cl, cs);
+    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
+    return BLZ_OK;
+}
+
 template <class Fr, int PASS>
 int ntt_pass_t(hipStream_t st, const void* in, void* out, const NttGeom& g, const NttTables& T, const NttTablesRR& TR, int cl,
-               bool force_generic) {
+               bool force_generic, const NttCoset* cs) {
     int lr = PASS == 1 ? g.logC : PASS == 2 ? g.logB : g.logA;
-    const int cols_avail = PASS == 3 ? g.logC : g.logA;  // extent of the tile's column index
-    if (lr == 9 && cols_avail >= NR_COLS_LOG && !force_generic) {
+    const int mode = cs ? cs->mode[PASS - 1] : 0;   // what this pass owes of a coset handle's shift (NttCoset)
+    if (ntt_pass_is_512(PASS, g, force_generic)) {
         // the tile goes through the LDS in two halves: 256 rows x 4 columns x 40 bytes
         const size_t ldsr = (size_t)256 * NR_COLS * rr_stride<typename Fr::RR>() * 4;
         const uint64_t tilesr = (1ull << g.logn) >> (9 + NR_COLS_LOG);
+        if constexpr (PASS != 3) {
+            if (mode == 1) {
+                if (!cs->tG) return fail(BLZ_ERR_UNKNOWN, "coset NTT: no wire-pass table");
+                return ntt_launch_512_cs<Fr, PASS, 1>(st, in, out, g, TR, *cs, (unsigned)tilesr, ldsr);
+            }
+        }
+        if constexpr (PASS == 2) {
+            if (mode == 2 && !TR.tB) return ntt_launch_512_cs<Fr, 2, 2>(st, in, out, g, TR, *cs, (unsigned)tilesr, ldsr);
+            // (with the table tB the handle folded the shift into its entries: the plain kernel)
+        }
+        if constexpr (PASS == 3) {
+            if (mode == 3) return ntt_launch_512_cs<Fr, 3, 3>(st, in, out, g, TR, *cs, (unsigned)tilesr, ldsr);
+        }
+        if (mode != 0 && !(PASS == 2 && mode == 2)) return fail(BLZ_ERR_UNKNOWN, "coset NTT: no 512-point kernel for mode %d of pass %d", mode, PASS);
         if (PASS == 2 && TR.tB) {
             BLZ_TRY(ensure_dynamic_lds((const void*)k_ntt512_rr<Fr, 2, true>, 160 * 1024));
             hipLaunchKernelGGL((k_ntt512_rr<Fr, 2, true>), dim3((unsigned)tilesr), dim3(NR_THREADS), ldsr, st, (const uint32_t*)in,
@@ -321,6 +410,11 @@ int ntt_pass_t(hipStream_t st, const void* in, void* out, const NttGeom& g, cons
     }
     size_t lds = ((size_t)4 << lr) * (((size_t)8 << cl) + 8);  // rows x (COLS*8 + 8) dwords
     uint64_t tiles = (1ull << g.logn) >> (lr + cl);
+    if (mode == 1) return ntt_launch_pass_cs<Fr, PASS, 1>(st, in, out, g, T, cl, *cs, (unsigned)tiles, lds);
+    if constexpr (PASS == 3) {
+        if (mode == 3) return ntt_launch_pass_cs<Fr, 3, 3>(st, in, out, g, T, cl, *cs, (unsigned)tiles, lds);
+    }
+    if (mode != 0) return fail(BLZ_ERR_UNKNOWN, "coset NTT: no kernel for mode %d of pass %d", mode, PASS);
     BLZ_TRY(ensure_dynamic_lds((const void*)k_ntt_pass<Fr, PASS>, 160 * 1024));
     hipLaunchKernelGGL((k_ntt_pass<Fr, PASS>), dim3((unsigned)tiles), dim3(NTT_THREADS), lds, st, (const uint32_t*)in,
                        (uint32_t*)out, g, T, cl);
@@ -330,12 +424,80 @@ int ntt_pass_t(hipStream_t st, const void* in, void* out, const NttGeom& g, cons
 
 template <class Fr>
 int ntt_pass_dispatch(int pass, hipStream_t st, const void* in, void* out, const NttGeom& g, const NttTables& T,
-                      const NttTablesRR& TR, int cl, bool force_generic) {
+                      const NttTablesRR& TR, int cl, bool force_generic, const NttCoset* cs) {
     switch (pass) {
-        case 1: return ntt_pass_t<Fr, 1>(st, in, out, g, T, TR, cl, force_generic);
-        case 2: return ntt_pass_t<Fr, 2>(st, in, out, g, T, TR, cl, force_generic);
-        default: return ntt_pass_t<Fr, 3>(st, in, out, g, T, TR, cl, force_generic);
+        case 1: return ntt_pass_t<Fr, 1>(st, in, out, g, T, TR, cl, force_generic, cs);
+        case 2: return ntt_pass_t<Fr, 2>(st, in, out, g, T, TR, cl, force_generic, cs);
+        default: return ntt_pass_t<Fr, 3>(st, in, out, g, T, TR, cl, force_generic, cs);
     }
+}
+
+// ---- coset handles (NttCoset, ntt_engine.hpp)
+inline bool ntt_coset_plan(const NttGeom& g, int inverse, bool force_generic, NttCoset& cs) {
+    cs.mode[0] = cs.mode[1] = cs.mode[2] = 0;
+    cs.inverse = inverse;
+    cs.gshift = 0;
+    if (!inverse) {
+        const int wp = g.wire_pass;
+        cs.mode[wp - 1] = 1;
+        if (!ntt_pass_is_512(wp, g, force_generic)) return false;   // the radix-2-in-LDS kernel multiplies by the whole s^i
+        if (wp == 1) {   // 2^27: tG holds s^(A (i1 + B i2)); s^i0 joins pass 2's boundary factor
+            cs.gshift = g.logA;
+            cs.mode[1] = 2;
+        }
+        return true;     // (wp == 2, 2^18: tG holds the whole s^(i0 + A i1))
+    }
+    cs.mode[2] = 3;
+    if (ntt_pass_is_512(3, g, force_generic)) cs.mode[1] = 2;   // finr takes n^-1 s^(CB k0), pass 2 (512-point as well: logn >= 20) the rest
+    return false;
+}
+template <class Fr>
+int ntt_coset_check_t(hipStream_t st, const uint32_t* d_shift, uint32_t* d_s, uint32_t* flag, int inverse) {
+    hipLaunchKernelGGL(k_ntt_cs_base<Fr>, dim3(1), dim3(64), 0, st, d_s, flag, d_shift, inverse);
+    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
+    return BLZ_OK;
+}
+// ts2 and tB, with the part of the shift pass 2 owes (cs, mode[1] == 2) or plain (cs == nullptr)
+template <class Fr>
+int ntt_fold_tables_t(hipStream_t st, const NttTables& T, const NttTablesRR& TR, const NttGeom& g, const NttCoset* cs, const uint32_t* d_s) {
+    const uint64_t n = 1ull << g.logn;
+    if (cs && cs->inverse)   // w^(64 C i0) s^(64 C): the step of s^(C k1 + k2) along a lane's rows rides on the step of w's power
+        hipLaunchKernelGGL((k_ntt_cs_table<Fr, 2>), dim3(2), dim3(256), 0, st, TR.ts2, 512u, (const uint32_t*)T.wbase, (uint64_t)64 << g.logC,
+                           d_s, (uint64_t)0, (uint64_t)64 << g.logC, (const uint32_t*)nullptr);
+    else
+        hipLaunchKernelGGL((k_ntt_table_rr_pow<Fr, true>), dim3(2), dim3(256), 0, st, TR.ts2, 512u, (const uint32_t*)T.wbase, (uint64_t)64 << g.logC);
+    if (TR.tB) {
+        if (cs) hipLaunchKernelGGL(k_ntt_table_b_cs<Fr>, dim3((unsigned)(n / 256)), dim3(256), 0, st, TR.tB, g, TR, *cs);
+        else hipLaunchKernelGGL(k_ntt_table_b<Fr>, dim3((unsigned)(n / 256)), dim3(256), 0, st, TR.tB, g, TR);
+    }
+    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
+    return BLZ_OK;
+}
+template <class Fr>
+int ntt_coset_tables_t(hipStream_t st, const NttTables& T, const NttTablesRR& TR, const NttGeom& g, const NttCoset& cs, const uint32_t* d_s) {
+    const uint32_t* none = nullptr;
+    uint32_t* d0p = cs.inverse ? cs.d0 + 512 * 8 : cs.d0;   // the pure powers (an inverse handle's d0 carries n^-1; they follow it)
+    hipLaunchKernelGGL((k_ntt_cs_table<Fr, 0>), dim3(2), dim3(256), 0, st, d0p, 512u, none, (uint64_t)0, d_s, (uint64_t)1, (uint64_t)0, none);
+    if (cs.inverse)
+        hipLaunchKernelGGL((k_ntt_cs_table<Fr, 0>), dim3(2), dim3(256), 0, st, cs.d0, 512u, none, (uint64_t)0, d_s, (uint64_t)1, (uint64_t)0, (const uint32_t*)T.ninv);
+    hipLaunchKernelGGL((k_ntt_cs_table<Fr, 0>), dim3(2), dim3(256), 0, st, cs.d1, 512u, none, (uint64_t)0, d_s, (uint64_t)512, (uint64_t)0, none);
+    hipLaunchKernelGGL((k_ntt_cs_table<Fr, 0>), dim3(2), dim3(256), 0, st, cs.d2, 512u, none, (uint64_t)0, d_s, (uint64_t)1 << 18, (uint64_t)0, none);
+    hipLaunchKernelGGL(k_ntt_table_to_rr<Fr>, dim3(2), dim3(256), 0, st, (const uint32_t*)d0p, cs.u0, 512);
+    hipLaunchKernelGGL(k_ntt_table_to_rr<Fr>, dim3(2), dim3(256), 0, st, (const uint32_t*)cs.d1, cs.u1, 512);
+    hipLaunchKernelGGL(k_ntt_table_to_rr<Fr>, dim3(2), dim3(256), 0, st, (const uint32_t*)cs.d2, cs.u2, 512);
+    if (cs.inverse)   // n^-1 s^(CB k0)
+        hipLaunchKernelGGL((k_ntt_cs_table<Fr, 1>), dim3(2), dim3(256), 0, st, cs.finr, 512u, none, (uint64_t)0, d_s, (uint64_t)1 << (g.logC + g.logB),
+                           (uint64_t)0, (const uint32_t*)T.ninv);
+    if (cs.tG)
+        hipLaunchKernelGGL((k_ntt_cs_table<Fr, 2>), dim3((unsigned)(NTT_RR_BOUNDARY_ENTRIES / 256)), dim3(256), 0, st, cs.tG, (uint32_t)NTT_RR_BOUNDARY_ENTRIES,
+                           none, (uint64_t)0, d_s, (uint64_t)1 << cs.gshift, (uint64_t)0, none);
+    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
+    if (cs.mode[1] == 2) BLZ_TRY(ntt_fold_tables_t<Fr>(st, T, TR, g, &cs, d_s));   // (after u0 / u1 / u2: same stream)
+    return BLZ_OK;
+}
+template <class Fr>
+int ntt_coset_unfold_t(hipStream_t st, const NttTables& T, const NttTablesRR& TR, const NttGeom& g) {
+    return ntt_fold_tables_t<Fr>(st, T, TR, g, nullptr, nullptr);
 }
 
 template <class Fr>
@@ -344,6 +506,10 @@ NttFieldOps make_ntt_ops() {
     o.two_adicity = Fr::TWO_ADICITY;
     o.setup = &ntt_setup_t<Fr>;
     o.pass = &ntt_pass_dispatch<Fr>;
+    o.coset_plan = &ntt_coset_plan;
+    o.coset_check = &ntt_coset_check_t<Fr>;
+    o.coset_tables = &ntt_coset_tables_t<Fr>;
+    o.coset_unfold = &ntt_coset_unfold_t<Fr>;
     return o;
 }
 

@@ -292,6 +292,51 @@ __global__ void k_ntt_table_rr_pow(uint32_t* __restrict__ out, uint32_t count, c
     }
 }
 
+// Tables of a coset handle: out[j] = w^(j mw) s^(j ms + c) [times *scale], w = *wbase (or absent), s = *sbase, all 32-bit
+// Montgomery.  FORM 0: 8 words, 32-bit Montgomery; 1: reduced radix, Montgomery R_rr; 2: a Shoup entry.
+template <class Fr>
+BLZ_DEV void fp_pow64(Fp<Fr>& acc, const Fp<Fr>& b, uint64_t e) {
+    fp_one(acc);
+    for (int i = 63; i >= 0; --i) {
+        fp_sqr(acc, acc);
+        if ((e >> i) & 1) fp_mul(acc, acc, b);
+    }
+}
+template <class Fr, int FORM>
+__global__ void k_ntt_cs_table(uint32_t* __restrict__ out, uint32_t count, const uint32_t* __restrict__ wbase, uint64_t mw,
+                               const uint32_t* __restrict__ sbase, uint64_t ms, uint64_t c, const uint32_t* __restrict__ scale) {
+    using Q = typename Fr::RR;
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    Fp<Fr> b, acc;
+    fp_load(b, sbase);
+    fp_pow64(acc, b, (uint64_t)j * ms + c);
+    if (wbase) {
+        Fp<Fr> t;
+        fp_load(b, wbase);
+        fp_pow64(t, b, (uint64_t)j * mw);
+        fp_mul(acc, acc, t);
+    }
+    if (scale) {
+        fp_load(b, scale);
+        fp_mul(acc, acc, b);
+    }
+    fp_reduce(acc);
+    if constexpr (FORM == 0) {
+        fp_store(out + (size_t)j * 8, acc);
+    } else {
+        Frr<Q, 1, 2> r;
+        rr_from_mont32_words<Q>(r, acc.v);
+        if constexpr (FORM == 2) {
+            RRShoup<Q> t;
+            rr_shoup_from_mont<Q>(t, r);
+            rr_store_shoup<Q>(out + (size_t)j * rr_shoup_stride<Q>(), t);
+        } else {
+            rr_store(out + (size_t)j * rr_stride<Q>(), rr_canon(r));
+        }
+    }
+}
+
 // w^e for e < 2^27 from the three 512-entry tables
 template <class Q>
 BLZ_DEV void tw_pow_rr(Frr<Q, 1, 2>& r, const NttTablesRR& T, uint32_t e) {
@@ -307,8 +352,20 @@ BLZ_DEV void tw_pow_rr(Frr<Q, 1, 2>& r, const NttTablesRR& T, uint32_t e) {
 // canonical Montgomery form packed in 32 bytes, IN THE ORDER PASS 2 CONSUMES THEM: entry ((tile 8 + K) 256 + thread) is the
 // factor of output K of that lane of that tile, so a wave reads 2 KiB in one piece per output and the table streams through once
 // (at the element's own index - rows 16 KiB apart, 128 bytes each, like the data - the pass gained 8 % instead of 14 %)
-template <class Fr>
-__global__ void k_ntt_table_b(uint32_t* __restrict__ out, NttGeom g, NttTablesRR T) {
+// s^e for e < 2^27 from a coset handle's three 512-entry tables
+template <class Q>
+BLZ_DEV void cs_pow_rr(Frr<Q, 1, 2>& r, const NttCoset& cs, uint32_t e) {
+    constexpr uint32_t ES = rr_stride<Q>();
+    Frr<Q, 1, 1> a;
+    rr_load(r, cs.u0 + (size_t)(e & 511u) * ES);
+    const uint32_t e1 = (e >> 9) & 511u, e2 = e >> 18;
+    if (e1) { rr_load(a, cs.u1 + (size_t)e1 * ES); rr_mul(r, r, a); }
+    if (e2) { rr_load(a, cs.u2 + (size_t)e2 * ES); rr_mul(r, r, a); }
+}
+
+// CS: the entry also carries the part of a coset handle's shift that pass 2 owes (NttCoset: s^i0 forward, s^(C k1 + k2) inverse)
+template <class Fr, bool CS>
+BLZ_DEV void ntt_table_b_entry(uint32_t* __restrict__ out, const NttGeom& g, const NttTablesRR& T, const NttCoset& cs) {
     using Q = typename Fr::RR;
     const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >> g.logn) return;
@@ -321,9 +378,22 @@ __global__ void k_ntt_table_b(uint32_t* __restrict__ out, NttGeom g, NttTablesRR
     const uint32_t k1 = (n2 >> 3) + 8u * (n2 & 7u) + 64u * K;   // the lane's output row (k_ntt512_rr: kb + 64 K)
     Frr<Q, 1, 2> w;
     tw_pow_rr<Q>(w, T, ((k1 << g.logC) + k2) * i0);
+    if constexpr (CS) {
+        Frr<Q, 1, 2> f;
+        cs_pow_rr<Q>(f, cs, cs.inverse ? (k1 << g.logC) + k2 : i0);
+        rr_mul(w, w, f);
+    }
     Fp<Fr> y;
     rr_to_words<Q>(y.v, rr_canon(w));
     fp_store(out + idx * 8, y);
+}
+template <class Fr>
+__global__ void k_ntt_table_b(uint32_t* __restrict__ out, NttGeom g, NttTablesRR T) {
+    ntt_table_b_entry<Fr, false>(out, g, T, NttCoset{});
+}
+template <class Fr>
+__global__ void k_ntt_table_b_cs(uint32_t* __restrict__ out, NttGeom g, NttTablesRR T, NttCoset cs) {
+    ntt_table_b_entry<Fr, true>(out, g, T, cs);
 }
 
 // the boundary table tA (2^18 entries, read once per element after pass 1) as Shoup entries (20 MiB) or Montgomery ones
@@ -354,9 +424,14 @@ constexpr int NR_THREADS = 64 * NR_COLS;
 // outputs K = 0..3 first and K = 4..7 second: the consumers of an output K of the first exchange are the lanes with
 // k1 = K - waves 0 and 1 for the first half, waves 2 and 3 for the second - and of the second exchange the lanes with
 // k1' = K of the same wave.  Costs: three more block barriers and four outputs kept in registers across a half.
-template <class Fr, int PASS, bool TABB = false>   // TABB: pass 2 reads its boundary factors from the per-element table tB
-__global__ __launch_bounds__(NR_THREADS, ((BLZ_NTT_OCC4 >> (PASS - 1)) & 1) ? 4 : 3) void k_ntt512_rr(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, NttGeom g,
-                                                            NttTablesRR T) {
+// CS: the coset variants (NttCoset; k_ntt512_rr_cs below), 0 = the plain transform.  1: this instantiation is the wire pass of a
+// forward coset transform and multiplies every element as loaded by its Shoup entry of tG; 2: pass 2, its stepped boundary factor
+// starts from the folded value (one per-lane product; the step is ts2's, which the handle rebuilt); 3: pass 3 of an inverse coset
+// transform, the closing factor is read by output row.
+template <class Fr, int PASS, bool TABB, int CS>
+BLZ_DEV void ntt512_rr_body(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, const NttGeom& g, const NttTablesRR& T,
+                            const NttCoset& cs) {
+    static_assert(CS == 0 || (CS == 1 && PASS != 3 && !TABB) || (CS == 2 && PASS == 2 && !TABB) || (CS == 3 && PASS == 3), "no such coset variant");
     using Q = typename Fr::RR;
     constexpr uint32_t ES = rr_stride<Q>();  // element stride in LDS and in the tables (dwords)
     constexpr uint32_t RS = NR_COLS * ES;    // tile row stride in dwords (40: the 32-bit kernel's 4 x 8 + 8)
@@ -422,16 +497,25 @@ __global__ __launch_bounds__(NR_THREADS, ((BLZ_NTT_OCC4 >> (PASS - 1)) & 1) ? 4 
     // they are < 2m.
     constexpr int BR[8] = {0, 4, 2, 6, 1, 5, 3, 7};
     constexpr int VIN1 = 1 << (32 * Q::N32 + 1 - Q::BITS);   // 2^256 < VIN1 m: 4 (BLS12-381), 8 (BN254), 16 (BLS12-377)
-    Frr<Q, 1, VIN1> a1[8];
+    std::conditional_t<CS == 1, Frr<Q, 1, 2>, Frr<Q, 1, VIN1>> a1[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const uint32_t row = 64u * BR[j] + n2;
         Fp<Fr> x;
         uint64_t iaddr = in_base + row * in_rstride + col * in_cstride;
+        [[maybe_unused]] const uint64_t logical = iaddr;   // the power of a coset's shift follows the element, not the buffer position
         if (PASS == g.wire_pass && g.brin) iaddr = __brevll(iaddr) >> (64 - g.logn);   // the caller's buffer is in bit-reversed order
         if constexpr (((BLZ_NTT_NT >> (2 * (PASS - 1))) & 1) != 0) fp_load_nt(x, in + iaddr * 8);
         else fp_load(x, in + iaddr * 8);
-        rr_from_words<Q>(a1[j], x.v);
+        if constexpr (CS == 1) {
+            Frr<Q, 1, VIN1> xw;
+            rr_from_words<Q>(xw, x.v);
+            RRShoup<Q> gs;
+            rr_load_shoup<Q>(gs, cs.tG + (size_t)(logical >> cs.gshift) * rr_shoup_stride<Q>());
+            rr_mul_n(a1[j], xw, gs);   // (any 256-bit word is < R_rr: the Shoup product brings it below 2m)
+        } else {
+            rr_from_words<Q>(a1[j], x.v);
+        }
     }
     auto o1 = dft8_rr<Q>(a1, w1, w2, w3);
     const uint32_t k1 = n2 >> 3, n2p = n2 & 7u;
@@ -536,14 +620,26 @@ __global__ __launch_bounds__(NR_THREADS, ((BLZ_NTT_OCC4 >> (PASS - 1)) & 1) ? 4 
             const uint64_t i0 = col_base + col;
             tw_pow_rr<Q>(w, T, (uint32_t)((((uint64_t)kb << g.logC) + (split ? fixed : 0)) * i0));
             rr_load_shoup<Q>(step_s, T.ts2 + (size_t)i0 * ES2);   // w^(64 C i0): a Shoup entry - w (Montgomery form) times a plain constant stays in Montgomery form
+            if constexpr (CS == 2) {
+                // forward: s^i0, the same for all of the lane's rows; inverse: s^(C k1 + k2), whose step s^(64 C) is in ts2's entries
+                W f;
+                cs_pow_rr<Q>(f, cs, cs.inverse ? (uint32_t)(((uint64_t)kb << g.logC) + fixed) : (uint32_t)i0);
+                rr_mul(w, w, f);
+            }
         }
+    } else if constexpr (CS == 3) {
+        // (the closing factor n^-1 s^(CB row) is read per output below)
     } else if (T.fin) {
         rr_load(w, T.fin);   // inverse transform: n^-1; a forward transform closes with the product-free reduction
     }
     BLZ_RR_FOR8(o3, {
         const uint32_t row = kb + 64u * K;
         W t;
-        if (PASS == 3 && !T.fin) {
+        if constexpr (CS == 3) {
+            W f;
+            rr_load(f, cs.finr + (size_t)row * ES);
+            rr_mul_n(t, X, f);
+        } else if (PASS == 3 && !T.fin) {
             t = rr_reduce2m(X);
         } else if (PASS == 1 && split) {   // w^(A i1 k2), read from the boundary table
             if constexpr (NTT_TA_SHOUP) {
@@ -581,6 +677,19 @@ __global__ __launch_bounds__(NR_THREADS, ((BLZ_NTT_OCC4 >> (PASS - 1)) & 1) ? 4 
         if constexpr (((BLZ_NTT_NT >> (2 * (PASS - 1) + 1)) & 1) != 0) fp_store_nt(out + oaddr * 8, y);
         else fp_store(out + oaddr * 8, y);
     })
+}
+
+template <class Fr, int PASS, bool TABB = false>   // TABB: pass 2 reads its boundary factors from the per-element table tB
+__global__ __launch_bounds__(NR_THREADS, ((BLZ_NTT_OCC4 >> (PASS - 1)) & 1) ? 4 : 3) void k_ntt512_rr(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, NttGeom g,
+                                                            NttTablesRR T) {
+    ntt512_rr_body<Fr, PASS, TABB, 0>(in, out, g, T, NttCoset{});
+}
+// the coset variants: CS says what this instantiation adds (ntt512_rr_body), at compile time - its static instruction count is
+// the count it executes.  (Pass 2 with the table tB has none: the handle folds the shift into the table's entries.)
+template <class Fr, int PASS, int CS>
+__global__ __launch_bounds__(NR_THREADS, ((BLZ_NTT_OCC4 >> (PASS - 1)) & 1) ? 4 : 3) void k_ntt512_rr_cs(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, NttGeom g,
+                                                               NttTablesRR T, NttCoset cs) {
+    ntt512_rr_body<Fr, PASS, false, CS>(in, out, g, T, cs);
 }
 
 }  // namespace blz

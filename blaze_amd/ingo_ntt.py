@@ -126,6 +126,26 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
     def reset(self) -> None:
         check(lib().blz_ntt_reset(self._h))
 
+    def set_coset(self, shift: Optional[int]) -> None:
+        """Transforms started from now on run on the coset shift * <w> (include/blaze_hip.h blz_ntt_set_coset): a forward client
+        computes X[k] = sum_i x[i] shift^i w^(i k), an inverse one its exact inverse; None or 1: the plain transform again.
+        0 < shift < r, checked on the device."""
+        if shift is None:
+            check(lib().blz_ntt_set_coset(self._h, None))
+            return
+        s = int(shift)
+        if s < 0 or s >> 256:
+            raise ValueError("the coset shift is a field element: 0 < shift < r")
+        check(lib().blz_ntt_set_coset(self._h, s.to_bytes(32, "little")))
+
+    @property
+    def coset(self) -> int:
+        """The shift in force; 1 when the client runs the plain transform."""
+        out = bytearray(32)
+        p, _, _k = buf_ptr(out)
+        check(lib().blz_ntt_get_coset(self._h, p))
+        return int.from_bytes(out, "little")
+
     # NTTBanks::preprocess / postprocess (ntt_data.rs:80-156) on device buffers
     def banks_preprocess(self, d_in: DeviceBuffer, d_banks: DeviceBuffer) -> None:
         check(lib().blz_ntt_banks_preprocess_device(self._h, d_in.ptr, d_banks.ptr))

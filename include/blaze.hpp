@@ -239,6 +239,14 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
         out.resize(nbytes_);
         check(blz_ntt_exchange(h_, buf, next.data(), next.size(), out.data(), out.size()));
     }
+    // transforms started from now on run on the coset shift * <w> (blaze_hip.h blz_ntt_set_coset): shift = 32 canonical
+    // little-endian bytes, 0 < shift < r; nullptr (or 1) = the plain transform again
+    void set_coset(const uint8_t* shift) { check(blz_ntt_set_coset(h_, shift)); }
+    std::array<uint8_t, 32> coset() {
+        std::array<uint8_t, 32> v{};
+        check(blz_ntt_get_coset(h_, v.data()));
+        return v;
+    }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

@@ -355,6 +355,20 @@ int blz_ntt_new_ex2(int device_id, int field, int log_size, int inverse, uint32_
 #define BLZ_NTT_BITREV_INPUT 4u
 #define BLZ_NTT_BITREV_OUTPUT 8u
 int blz_ntt_new_ex3(int device_id, int field, int log_size, uint32_t flags, const uint8_t* root, blz_ntt** out);
+/* Coset transforms.  shift = 32 bytes, canonical little-endian, a field element g with 0 < g < r;
+ * NULL (or g = 1) = the plain transform again.
+ *   handle without BLZ_NTT_INVERSE:  X[k] = sum_i x[i] g^i w^(i k)       (evaluate on the coset g<w>)
+ *   handle with    BLZ_NTT_INVERSE:  x[i] = g^(-i) n^-1 sum_k X[k] w^(-i k)   (its exact inverse)
+ * i and k are LOGICAL indices: with BLZ_NTT_BITREV_INPUT / _OUTPUT the buffers are permuted as before,
+ * the power of g follows the element, not the buffer position.  w is the handle's root (default or
+ * the caller's).  Fused into the transform's passes: no pass over the data and no launch is added.
+ * Blocking; rebuilds only the tables that carry g (among them, at 2^27, pass 2's per-element factor table
+ * where the handle has one); leaves both transform buffers' contents alone; holds for transforms started
+ * after it returns and across blz_ntt_reset.  BLZ_ERR_INVALID_PARAM, changing nothing: null handle, shift = 0,
+ * shift >= r (checked on the device), a transform in flight on the handle. */
+int blz_ntt_set_coset(blz_ntt* h, const uint8_t* shift);
+/* the shift in force: 32 bytes, the element 1 when the handle runs the plain transform */
+int blz_ntt_get_coset(blz_ntt* h, uint8_t out[32]);
 /* out = {device bytes the handle holds (two transform buffers + scratch + twiddle / factor tables), 1 if pass 2 reads the
  * per-element factor table / 0 if it steps its factors, 1 if pass 1 reads the column-independent boundary table, log_size} */
 int blz_ntt_info(blz_ntt* h, uint64_t out[4]);

@@ -114,6 +114,21 @@ impl NTTClient {
         Ok(v)
     }
 
+    /// Transforms started from now on run on the coset `shift * <w>`: a forward client computes X[k] = sum_i x[i] shift^i w^(i k),
+    /// an inverse one its exact inverse.  `shift` = 32 canonical little-endian bytes, 0 < shift < r (checked on the device);
+    /// `None` (or 1) = the plain transform again.  Fused into the transform's passes (blaze_hip.h blz_ntt_set_coset).
+    pub fn set_coset(&self, shift: Option<&[u8; 32]>) -> Result<()> {
+        let sp = shift.map_or(std::ptr::null(), |s| s.as_ptr());
+        check(unsafe { blz_ntt_set_coset(self.h, sp) })
+    }
+
+    /// The shift in force; the element 1 when the client runs the plain transform.
+    pub fn coset(&self) -> Result<[u8; 32]> {
+        let mut v = [0u8; 32];
+        check(unsafe { blz_ntt_get_coset(self.h, v.as_mut_ptr()) })?;
+        Ok(v)
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
