@@ -107,6 +107,25 @@ _SIGS = {
     "blz_ntt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blz_ntt_banks_preprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
     "blz_ntt_banks_postprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
+    "blz_poseidon_new": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "blz_poseidon_free": (None, [C.c_void_p]),
+    "blz_poseidon_loaded_binary_parameters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "blz_poseidon_initialize": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_char_p]),
+    "blz_poseidon_check_words": (C.c_int, [C.c_int, C.c_int, _u8p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "blz_poseidon_initialize_words": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, _u8p, C.c_size_t]),
+    "blz_poseidon_set_data": (C.c_int, [C.c_void_p, _u8p, C.c_size_t]),
+    "blz_poseidon_set_data_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "blz_poseidon_wait_result": (C.c_int, [C.c_void_p]),
+    "blz_poseidon_num_pending_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "blz_poseidon_raw_results": (C.c_int, [C.c_void_p, C.c_uint32, _u8p, C.c_size_t]),
+    "blz_poseidon_result": (C.c_int, [C.c_void_p, C.c_uint32, _u8p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "blz_poseidon_tree_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "blz_poseidon_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "blz_poseidon_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "blz_poseidon_set_round_plan": (C.c_int, [C.c_void_p, C.c_int]),
+    "blz_poseidon_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "blz_poseidon_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "blz_poseidon_reset": (C.c_int, [C.c_void_p]),
     "blz_device_malloc": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
     "blz_device_free": (C.c_int, [C.c_int, C.c_void_p]),
     "blz_host_malloc": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -127,6 +146,9 @@ _AUX_SIGS = {
     "blz_test_stall_release": (C.c_int, [C.c_void_p]),
     "blz_test_field_op": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u8p, _u8p, _u8p, C.c_size_t]),
     "blz_test_ec_op": (C.c_int, [C.c_int, C.c_int, C.c_int, _u8p, _u8p, _u8p, _u8p, _u8p, C.c_size_t]),
+    "blz_test_poseidon_permute": (C.c_int, [C.c_int, C.c_int, _u8p, C.c_size_t, C.c_int, _u8p, _u8p, C.c_size_t]),
+    "blz_test_poseidon_hash": (C.c_int, [C.c_int, C.c_int, _u8p, C.c_size_t, C.c_int, _u8p, _u8p, C.c_size_t]),
+    "blz_test_poseidon_tree_check": (C.c_int, [C.c_int, C.c_int, _u8p, C.c_size_t, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 AUX_EXPORTED_SYMBOLS = tuple(_AUX_SIGS)
 

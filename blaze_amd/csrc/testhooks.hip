@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "ec_rr.hip.hpp"
 #include "ec_row.hip.hpp"
+#include "poseidon_engine.hpp"
 
 namespace blz {
 
@@ -304,6 +305,201 @@ int test_ec_t(int op, const uint8_t* p, const uint8_t* q, const uint8_t* fl, uin
     return BLZ_OK;
 }
 
+
+// ---- Poseidon: the DEFINITION kernel (include/blaze_hip_aux.h).  One lane per state, the dense textbook rounds on the 8 x 32-bit
+// Montgomery arithmetic of field.hip.hpp: it shares neither the representation nor the schedule of the product path
+// (poseidon_impl.hip.hpp), and is slow on purpose.  Constants arrive as canonical words and are converted by k_test_pos_mont.
+template <class P>
+__global__ __launch_bounds__(64) void k_test_pos_mont(const uint32_t* words, uint32_t* out, uint32_t n) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    Fp<P> x;
+    fp_load(x, words + (size_t)i * P::N);
+    fp_to_mont(x, x);
+    fp_store(out + (size_t)i * P::N, x);
+}
+// any 256-bit word -> its residue, Montgomery form
+template <class P>
+BLZ_DEV void pos_def_load(Fp<P>& x, const uint32_t* p) {
+    fp_load(x, p);
+    for (int k = 0; k < 16; ++k) fp_csub_const<P, P::MOD>(x);   // 2^256 / r < 14 for the three scalar fields
+    fp_to_mont(x, x);
+}
+// consts: tag | t (rf + rp) round constants | t t matrix entries, Montgomery form
+template <class P>
+BLZ_DEV void pos_def_permute(Fp<P> (&s)[16], const uint32_t* consts, int t, int rf, int rp) {
+    const uint32_t* rc = consts + P::N;
+    const uint32_t* mds = rc + (size_t)t * (rf + rp) * P::N;
+    for (int r = 0; r < rf + rp; ++r) {
+        const bool full = r < rf / 2 || r >= rf / 2 + rp;
+        for (int i = 0; i < t; ++i) {
+            Fp<P> c;
+            fp_load(c, rc + ((size_t)r * t + i) * P::N);
+            fp_add(s[i], s[i], c);
+            if (full || i == 0) {
+                Fp<P> x2, x4;
+                fp_mul(x2, s[i], s[i]);
+                fp_mul(x4, x2, x2);
+                fp_mul(s[i], x4, s[i]);
+            }
+        }
+        Fp<P> nw[16];
+        for (int i = 0; i < t; ++i) {
+            Fp<P> acc;
+            fp_zero(acc);
+            for (int j = 0; j < t; ++j) {
+                Fp<P> m, pr;
+                fp_load(m, mds + ((size_t)i * t + j) * P::N);
+                fp_mul(pr, m, s[j]);
+                fp_add(acc, acc, pr);
+            }
+            nw[i] = acc;
+        }
+        for (int i = 0; i < t; ++i) s[i] = nw[i];
+    }
+}
+template <class P>
+__global__ __launch_bounds__(64) void k_test_pos_permute(const uint32_t* consts, int t, int rf, int rp, const uint32_t* in, uint32_t* out, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    Fp<P> s[16];
+    for (int k = 0; k < t; ++k) pos_def_load(s[k], in + (i * t + k) * P::N);
+    pos_def_permute<P>(s, consts, t, rf, rp);
+    for (int k = 0; k < t; ++k) {
+        Fp<P> o;
+        fp_from_mont(o, s[k]);
+        fp_store(out + (i * t + k) * P::N, o);
+    }
+}
+// every node of one layer re-hashed from its children and compared with its record (digest, hash_id, layer_id): res[0] += nodes
+// looked at, res[1] += nodes that differ.  child: the 32-byte words of the layer's inputs, `cstride` dwords apart (8: the element
+// FIFO; 16: the digests inside the records of the layer below).
+template <class P>
+__global__ __launch_bounds__(64) void k_test_pos_check_layer(const uint32_t* consts, int t, int rf, int rp, const uint32_t* child, uint32_t cstride,
+                                                             const uint32_t* rec, uint64_t n, uint32_t layer, unsigned long long* res) {
+    const uint64_t i = (uint64_t)blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    Fp<P> s[16];
+    fp_load(s[0], consts);   // the tag
+    for (int k = 1; k < t; ++k) pos_def_load(s[k], child + (i * (uint64_t)(t - 1) + (k - 1)) * cstride);
+    pos_def_permute<P>(s, consts, t, rf, rp);
+    Fp<P> o;
+    fp_from_mont(o, s[1]);
+    const uint32_t* r = rec + i * 16u;
+    bool same = true;
+    for (int k = 0; k < P::N; ++k) same = same && r[k] == o.v[k];
+    const uint64_t tagw = (i & 0x3fffffffull) | ((uint64_t)layer << 30);
+    same = same && r[8] == (uint32_t)tagw && r[9] == (uint32_t)(tagw >> 32);
+    for (int k = 10; k < 16; ++k) same = same && r[k] == 0u;
+    atomicAdd(&res[0], 1ull);
+    if (!same) atomicAdd(&res[1], 1ull);
+}
+
+// the product path's kernel of width t on n independent inputs (device pointers): what the tree's layers run.  Blocking.
+static int poseidon_hash_batch(int device_id, int field, const uint8_t* words, size_t len, int t, const void* d_in, void* d_out, uint64_t n) {
+    const PoseidonFieldOps* ops = poseidon_ops_for(field);
+    if (!ops) return fail(BLZ_ERR_INVALID_PARAM, "unknown field %d", field);
+    if (!words || !d_in || !d_out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    if (t < POS_T_MIN || t > POS_T_MAX) return fail(BLZ_ERR_INVALID_PARAM, "width %d out of range", t);
+    PoseidonStream ps;
+    BLZ_TRY(poseidon_parse(field, 1u << t, words, len, ps));
+    BLZ_TRY(use_device(device_id));
+    DevBuf raw, consts;
+    PoseidonWidth w[POS_T_MAX + 1];
+    int rc = poseidon_upload(ops, nullptr, ps, words, raw, consts, w);
+    if (rc == BLZ_OK) {
+        PoseidonJob job;
+        job.in = (const uint32_t*)d_in;
+        job.dig = (uint32_t*)d_out;
+        job.n = n;
+        rc = ops->hash(nullptr, w[t], job);
+    }
+    if (rc == BLZ_OK) rc = sync_stream_bounded(nullptr, "Poseidon hash batch");
+    raw.release();
+    consts.release();
+    return rc;
+}
+
+
+// the word stream's block of width t (already checked by blz_poseidon_check_words): word indices
+struct PosDefBlock { int t = 0, rf = 0, rp = 0; size_t tag = 0, count = 0; };
+static bool pos_def_find(const uint8_t* words, size_t len, int t, PosDefBlock& out) {
+    auto small = [&](size_t i) { uint32_t v; memcpy(&v, words + 32 * i, 4); return v; };
+    const size_t n = len / 32;
+    const uint32_t K = small(2);
+    size_t pos = 3;
+    for (uint32_t k = 0; k < K && pos + 5 <= n; ++k) {
+        const uint32_t bt = small(pos), rf = small(pos + 2), rp = small(pos + 3);
+        const size_t count = 1 + (size_t)bt * (rf + rp) + (size_t)bt * bt;
+        if ((int)bt == t) {
+            out.t = t; out.rf = (int)rf; out.rp = (int)rp; out.tag = pos + 4; out.count = count;
+            return true;
+        }
+        pos += 4 + count;
+    }
+    return false;
+}
+// the block's constants on the device, Montgomery form (tag | rc | mds)
+template <class P>
+int pos_def_consts(Tmp& tmp, const uint8_t* words, const PosDefBlock& b, uint32_t** d_consts) {
+    void *raw, *mont;
+    BLZ_TRY(tmp.alloc(&raw, b.count * 32));
+    BLZ_TRY(tmp.alloc(&mont, b.count * 32));
+    BLZ_HIP(hipMemcpy(raw, words + b.tag * 32, b.count * 32, hipMemcpyHostToDevice), BLZ_ERR_WRITE);
+    hipLaunchKernelGGL(k_test_pos_mont<P>, dim3((unsigned)((b.count + 63) / 64)), dim3(64), 0, 0, (const uint32_t*)raw, (uint32_t*)mont, (uint32_t)b.count);
+    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
+    *d_consts = (uint32_t*)mont;
+    return BLZ_OK;
+}
+template <class P>
+int test_pos_permute_t(const uint8_t* words, const PosDefBlock& b, const uint8_t* in, uint8_t* out, uint64_t n) {
+    Tmp tmp;
+    uint32_t* consts = nullptr;
+    BLZ_TRY(pos_def_consts<P>(tmp, words, b, &consts));
+    const size_t bytes = (size_t)n * b.t * 32;
+    void *din, *dout;
+    BLZ_TRY(tmp.alloc(&din, bytes)); BLZ_TRY(tmp.alloc(&dout, bytes));
+    BLZ_HIP(hipMemcpy(din, in, bytes, hipMemcpyHostToDevice), BLZ_ERR_WRITE);
+    hipLaunchKernelGGL(k_test_pos_permute<P>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, (const uint32_t*)consts, b.t, b.rf, b.rp,
+                       (const uint32_t*)din, (uint32_t*)dout, n);
+    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
+    BLZ_TRY(sync_stream_bounded(nullptr, "Poseidon definition kernel"));
+    BLZ_HIP(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost), BLZ_ERR_READ);
+    return BLZ_OK;
+}
+template <class P>
+int test_pos_tree_check_t(const uint8_t* words, size_t len, int tree_mode, uint32_t height, const void* d_input, const void* d_records, uint64_t out[2]) {
+    Tmp tmp;
+    PosDefBlock b9, b12;
+    if (!pos_def_find(words, len, 9, b9) || (tree_mode == BLZ_TREE_C && !pos_def_find(words, len, 12, b12))) return fail(BLZ_ERR_INVALID_PARAM, "width missing");
+    uint32_t *c9 = nullptr, *c12 = nullptr;
+    BLZ_TRY(pos_def_consts<P>(tmp, words, b9, &c9));
+    if (tree_mode == BLZ_TREE_C) BLZ_TRY(pos_def_consts<P>(tmp, words, b12, &c12));
+    void* res;
+    BLZ_TRY(tmp.alloc(&res, 16));
+    BLZ_HIP(hipMemset(res, 0, 16), BLZ_ERR_UNKNOWN);
+    const uint32_t* rec = (const uint32_t*)d_records;
+    const uint32_t* below = (const uint32_t*)d_input;   // the inputs of the layer being checked
+    uint32_t bstride = 8;
+    for (uint32_t l = tree_mode == BLZ_TREE_C ? 0u : 1u; l < height; ++l) {
+        const uint64_t n = 1ull << (3 * (height - 1 - l));
+        const bool base = l == 0;
+        const PosDefBlock& b = base ? b12 : b9;
+        hipLaunchKernelGGL(k_test_pos_check_layer<P>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, (const uint32_t*)(base ? c12 : c9), b.t, b.rf, b.rp,
+                           below, bstride, rec, n, l, (unsigned long long*)res);
+        BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
+        BLZ_TRY(sync_stream_bounded(nullptr, "Poseidon tree check"));   // (layer by layer: each wait stays well inside its deadline)
+        below = rec;
+        bstride = 16;
+        rec += n * 16u;
+    }
+    unsigned long long r[2];
+    BLZ_HIP(hipMemcpy(r, res, 16, hipMemcpyDeviceToHost), BLZ_ERR_READ);
+    out[0] = r[0];
+    out[1] = r[1];
+    return BLZ_OK;
+}
+
 }  // namespace blz
 
 using namespace blz;
@@ -339,6 +535,51 @@ int blz_test_ec_op(int device_id, int curve, int op, const uint8_t* p, const uin
         case BLZ_BN254: return test_ec_t<Fq_BN254>(op, p, q, inf_flags, out, out_inf, n);
     }
     return fail(BLZ_ERR_INVALID_PARAM, "unknown curve %d", curve);
+}
+
+int blz_test_poseidon_permute(int device_id, int field, const uint8_t* words, size_t len, int t, const uint8_t* states_in, uint8_t* states_out, size_t n) {
+    if (!words || !states_in || !states_out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    if (t < 2 || t > 16) return fail(BLZ_ERR_INVALID_PARAM, "width %d out of range", t);
+    PoseidonStream checked;   // (the load-time checks; the block itself is looked up by this file's own reader)
+    BLZ_TRY(poseidon_parse(field, 1u << t, words, len, checked));
+    PosDefBlock b;
+    if (!pos_def_find(words, len, t, b)) return fail(BLZ_ERR_INVALID_PARAM, "the stream has no block of width %d", t);
+    BLZ_TRY(use_device(device_id));
+    if (n == 0) return BLZ_OK;
+    switch (field) {
+        case BLZ_BLS377: return test_pos_permute_t<Fr_BLS377>(words, b, states_in, states_out, n);
+        case BLZ_BLS381: return test_pos_permute_t<Fr_BLS381>(words, b, states_in, states_out, n);
+        case BLZ_BN254: return test_pos_permute_t<Fr_BN254>(words, b, states_in, states_out, n);
+    }
+    return fail(BLZ_ERR_INVALID_PARAM, "unknown field %d", field);
+}
+
+int blz_test_poseidon_hash(int device_id, int field, const uint8_t* words, size_t len, int t, const uint8_t* inputs, uint8_t* digests, size_t n) {
+    if (!words || !inputs || !digests) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    if (t < 2 || t > 16) return fail(BLZ_ERR_INVALID_PARAM, "width %d out of range", t);
+    BLZ_TRY(use_device(device_id));
+    if (n == 0) return BLZ_OK;
+    Tmp tmp;
+    void *din, *dout;
+    BLZ_TRY(tmp.alloc(&din, n * (size_t)(t - 1) * 32)); BLZ_TRY(tmp.alloc(&dout, n * 32));
+    BLZ_HIP(hipMemcpy(din, inputs, n * (size_t)(t - 1) * 32, hipMemcpyHostToDevice), BLZ_ERR_WRITE);
+    BLZ_TRY(poseidon_hash_batch(device_id, field, words, len, t, din, dout, n));
+    BLZ_HIP(hipMemcpy(digests, dout, n * 32, hipMemcpyDeviceToHost), BLZ_ERR_READ);
+    return BLZ_OK;
+}
+
+int blz_test_poseidon_tree_check(int device_id, int field, const uint8_t* words, size_t len, int tree_mode, uint32_t tree_height, const void* d_input,
+                                 const void* d_records, uint64_t out[2]) {
+    if (!words || !d_input || !d_records || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    if (tree_height < 1 || tree_height > 11) return fail(BLZ_ERR_INVALID_PARAM, "tree height out of range");
+    BLZ_TRY(blz_poseidon_check_words(field, tree_mode, words, len, nullptr));
+    BLZ_TRY(use_device(device_id));
+    switch (field) {
+        case BLZ_BLS377: return test_pos_tree_check_t<Fr_BLS377>(words, len, tree_mode, tree_height, d_input, d_records, out);
+        case BLZ_BLS381: return test_pos_tree_check_t<Fr_BLS381>(words, len, tree_mode, tree_height, d_input, d_records, out);
+        case BLZ_BN254: return test_pos_tree_check_t<Fr_BN254>(words, len, tree_mode, tree_height, d_input, d_records, out);
+    }
+    return fail(BLZ_ERR_INVALID_PARAM, "unknown field %d", field);
 }
 
 }  // extern "C"

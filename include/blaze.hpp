@@ -3,6 +3,7 @@
 //   src/driver_client/dclient.rs:28-46   trait DriverPrimitive<T,P,I,O>
 //   src/ingo_msm/msm_api.rs:8-331        MSMClient, MSMInit, MSMParams, MSMInput, MSMResult
 //   src/ingo_ntt/ntt_api.rs:8-125        NTTClient, NTT, NttInit, NTTInput
+//   src/ingo_hash/poseidon_api.rs:11-278 PoseidonClient, Hash, TreeMode, PoseidonInitializeParameters, PoseidonResult
 //   src/error.rs:6-32                    DriverClientError
 // Header-only; link with -lblaze_hip.  Errors are thrown as DriverClientError (the reference returns
 // Result<_, DriverClientError>; its panics on bad mode combinations become InvalidPrimitiveParam).
@@ -253,6 +254,83 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
         check(blz_ntt_info(h_, v.data()));
         return v;
     }
+};
+
+// ---------------------------------------------------------------- Poseidon tree (src/ingo_hash)
+enum class Hash { Poseidon };                                      // poseidon_api.rs:11-13
+enum class TreeMode { TreeC = 0, TreeD = 1 };                      // utils.rs:18-30
+inline uint32_t num_of_elements_oct_tree(uint32_t h) { uint32_t s = 0; for (uint32_t i = 0; i < h; ++i) s += 1u << (3 * (h - i - 1)); return s; }  // utils.rs:2-10
+inline uint32_t num_of_elements_in_base_layer(uint32_t h) { return 1u << (3 * (h - 1)); }                                                          // utils.rs:12-14
+struct PoseidonInitializeParameters { uint32_t tree_height; TreeMode tree_mode; std::string instruction_path; };   // poseidon_api.rs:19-24
+struct PoseidonResult {                                                                                             // poseidon_api.rs:26-30
+    std::array<uint8_t, 32> hash_byte;
+    uint32_t hash_id, layer_id;
+    // poseidon_api.rs:42-71: 64 bytes per record; hash_id in bits 0-29, layer_id in bits 30-39 of the second half
+    static std::vector<PoseidonResult> parse_poseidon_hash_results(const std::vector<uint8_t>& data) {
+        std::vector<PoseidonResult> out;
+        for (size_t k = 0; k + 64 <= data.size(); k += 64) {
+            PoseidonResult r{};
+            for (int i = 0; i < 32; ++i) r.hash_byte[i] = data[k + i];
+            const uint8_t* d = data.data() + k + 32;
+            r.hash_id = (uint32_t(d[0]) | uint32_t(d[1]) << 8 | uint32_t(d[2]) << 16 | uint32_t(d[3]) << 24) & 0x3fffffffu;
+            r.layer_id = (uint32_t(d[3]) | uint32_t(d[4]) << 8) >> 6;
+            out.push_back(r);
+        }
+        return out;
+    }
+};
+
+// The hash is the caller's: the instruction CSV carries the Poseidon instance (blaze_hip.h "THE INSTRUCTION STREAM").
+class PoseidonClient : public DriverPrimitive<Hash, PoseidonInitializeParameters, std::vector<uint8_t>, std::vector<PoseidonResult>> {
+    blz_poseidon* h_ = nullptr;
+
+   public:
+    DriverClient dclient;
+    // poseidon_api.rs:77-79; `field` (a Curve: the scalar field of that curve) has no reference counterpart
+    PoseidonClient(Hash, DriverClient dclient_, Curve field = Curve::BLS381) : dclient(dclient_) { check(blz_poseidon_new(dclient.id, int(field), &h_)); }
+    ~PoseidonClient() override { blz_poseidon_free(h_); }
+    PoseidonClient(const PoseidonClient&) = delete;
+    PoseidonClient& operator=(const PoseidonClient&) = delete;
+
+    std::vector<uint32_t> loaded_binary_parameters() const override {                                         // :81-94
+        uint32_t v[2];
+        check(blz_poseidon_loaded_binary_parameters(h_, v));
+        return {v[0], v[1]};
+    }
+    void initialize(const PoseidonInitializeParameters& p) override {                                         // :96-111
+        check(blz_poseidon_initialize(h_, p.tree_height, int(p.tree_mode), p.instruction_path.c_str()));
+    }
+    void set_data(const std::vector<uint8_t>& input) override { check(blz_poseidon_set_data(h_, input.data(), input.size())); }   // :117-122
+    void start_process(std::optional<size_t> = std::nullopt) override { throw std::logic_error("todo!() in the reference (poseidon_api.rs:113-115)"); }
+    void wait_result() override { check(blz_poseidon_wait_result(h_)); }       // todo!() in the reference; here: everything fed so far is hashed
+    std::optional<std::vector<PoseidonResult>> result(std::optional<size_t> expected = std::nullopt) override {   // :128-145, bounded
+        std::vector<uint8_t> raw(64 * expected.value());
+        uint32_t n = 0;
+        check(blz_poseidon_result(h_, uint32_t(expected.value()), raw.data(), raw.size(), &n));
+        raw.resize(64 * size_t(n));
+        return PoseidonResult::parse_poseidon_hash_results(raw);
+    }
+    uint32_t get_num_of_pending_results() {                                                                    // :156-161
+        uint32_t v = 0;
+        check(blz_poseidon_num_pending_results(h_, &v));
+        return v;
+    }
+    std::vector<uint8_t> get_raw_results(uint32_t num_of_results) {                                            // :191-196
+        std::vector<uint8_t> raw(64 * size_t(num_of_results));
+        check(blz_poseidon_raw_results(h_, num_of_results, raw.data(), raw.size()));
+        return raw;
+    }
+    std::array<uint32_t, 4> counters() {
+        std::array<uint32_t, 4> v{};
+        check(blz_poseidon_counters(h_, v.data()));
+        return v;
+    }
+    uint32_t get_last_element_sent_to_ring() { return counters()[0]; }                                         // :149-154
+    uint32_t get_last_hash_sent_to_host() { return counters()[1]; }                                            // :198-203
+    void initialize_words(uint32_t tree_height, TreeMode mode, const std::vector<uint8_t>& words) {
+        check(blz_poseidon_initialize_words(h_, tree_height, int(mode), words.data(), words.size()));
+    }
+    void reset() { check(blz_poseidon_reset(h_)); }
 };
 
 }  // namespace ingo_blaze

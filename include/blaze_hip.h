@@ -1,7 +1,7 @@
-/* libblaze_hip - MI355X (gfx950) device path for blaze's MSM / NTT primitives.
+/* libblaze_hip - MI355X (gfx950) device path for blaze's MSM / NTT / Poseidon-tree primitives.
  *
  * C ABI cut at the DriverPrimitive method level: one function per trait method per primitive
- * (reference trait: src/driver_client/dclient.rs:28-46).  Each entry cites the reference
+ * (reference trait: src/driver_client/dclient.rs:28-46; the three primitives: MSMClient, NTTClient, PoseidonClient).  Each entry cites the reference
  * interface it replaces.  Plain pointers and sizes only; the callee borrows host pointers for the
  * duration of the call; the caller provides output buffers.  A handle is not thread-safe; distinct
  * handles are independent (own stream and workspace).  Nothing here ever falls back to a CPU path:
@@ -29,7 +29,7 @@ enum blz_error {
     BLZ_ERR_HBICAP_NOT_READY = 3,    /* HBICAPNotReady: never produced (no bitstream to load)        */
     BLZ_ERR_INVALID_PARAM = 4,       /* InvalidPrimitiveParam: bad mode combination / sizes / state  */
     BLZ_ERR_CSV = 5,                 /* CsvError: never produced                                     */
-    BLZ_ERR_LOAD_FAILED = 6,         /* LoadFailed{path}: librccl.so.1 could not be loaded (comm API) */
+    BLZ_ERR_LOAD_FAILED = 6,         /* LoadFailed{path}: librccl.so.1 (comm API) / a Poseidon instruction file could not be loaded */
     BLZ_ERR_FILE = 7,                /* FileError: device could not be opened (no GPU / bad ordinal) */
     BLZ_ERR_UNKNOWN = 8              /* Unknown: kernel launch / runtime failure                     */
 };
@@ -44,6 +44,7 @@ enum blz_mem { BLZ_HBM = 0, BLZ_DMA = 1 };
 
 typedef struct blz_msm blz_msm;
 typedef struct blz_ntt blz_ntt;
+typedef struct blz_poseidon blz_poseidon;
 
 const char* blz_last_error_message(void);
 /* number of usable HIP devices (0 when there is none); never fails */
@@ -404,6 +405,101 @@ int blz_ntt_last_kernel_ms(blz_ntt* h, float* out);
  * scale the group count (n >> 18, at least 1). */
 int blz_ntt_banks_preprocess_device(blz_ntt* h, const void* d_in, void* d_banks);
 int blz_ntt_banks_postprocess_device(blz_ntt* h, const void* d_banks, void* d_out);
+
+/* ------------------------------------------------------------------ Poseidon octal Merkle tree (src/ingo_hash/poseidon_api.rs)
+ *
+ * THE HASH.  The reference does not define it: the permutation reaches the card as a CSV "instruction set" that does not ship.
+ * As with the NTT's convention, it is the CALLER's: the word stream handed over at initialize carries the Poseidon instance.
+ * Everything the reference does pin - call sequence, element FIFO, 11 elements per base node and arity 8 above
+ * (tests/integration_poseidon.rs:109-116, 151-155), node count, the 64-byte record (poseidon_api.rs:42-71) - is kept exactly.
+ *   Field: the scalar field of `field` (enum blz_curve); the reference's TEST_SCALAR is a BLS12-381 Fr element.
+ *   Permutation of width t, textbook Poseidon, S-box x^5: R_F / 2 full rounds, R_P partial rounds, R_F / 2 full rounds; every
+ *     round is: add the round's t constants -> S-box (all t elements in a full round, element 0 only in a partial one) ->
+ *     multiply the state by the t x t MDS matrix M, new_i = sum_j M[i][j] s_j.  This dense form is the definition.
+ *   Fixed-arity hash H_t(x_1 .. x_(t-1)): state = [tag_t, x_1, .., x_(t-1)], one permutation, digest = state[1].
+ *   Tree of height h >= 1, layers 0 .. h - 1, layer l has 8^(h-1-l) nodes.
+ *     BLZ_TREE_C (start layer 0): the input is a FIFO of 11 x 8^(h-1) elements; base node j = H_12(elements 11 j .. 11 j + 10);
+ *       node i of layer l >= 1 = H_9(nodes 8 i .. 8 i + 7 of layer l - 1).  One record per node: (8^h - 1) / 7, 585 at h = 4.
+ *     BLZ_TREE_D (start layer 1): the reference only writes the register.  THIS BUILD'S READING: the 8^(h-1) input elements ARE
+ *       layer 0; records exist for layers 1 .. h - 1 only.
+ *   Record, 64 bytes (PoseidonResult::parse_poseidon_hash_results): bytes 0-31 the digest, canonical little-endian; bytes 32-63 a
+ *     256-bit little-endian word with hash_id (index inside the layer) in bits 0-29, layer_id in bits 30-39, zero above.
+ *     Hence h <= 11; a larger height, or a tree whose buffers do not fit the device, is InvalidPrimitiveParam.
+ *   Input elements >= r are taken as their residue (the NTT's rule).
+ * PARITY WITH ANY OUTSIDE POSEIDON (Filecoin's neptune, circomlib ...) IS NOT PINNED: what is pinned is the definition above,
+ * by an independent textbook implementation in tests/poseidon_ref.py.
+ *
+ * THE INSTRUCTION STREAM.  load_instructions (poseidon_api.rs:205-243) reads a CSV whose first line is a header and sends, per
+ * record, the LAST column and then the SECOND-TO-LAST as 32-byte little-endian words.  This build gives that word stream a
+ * meaning (the FPGA's microcode cannot be ours):
+ *   magic ("BLZPOSEIDON01" as ASCII bytes = a little-endian integer: a CSV made for the card is refused, not misread), field,
+ *   K, then K blocks of:  t, alpha (must be 5), R_F, R_P, tag_t, t (R_F + R_P) round constants in round order, t^2 MDS entries
+ *   row-major;  an odd word count is padded with one zero word.
+ * Checked at load: every word < r, R_F even, 2 <= t <= 16, no width twice, the block lengths add up, the widths the tree mode
+ * needs are present (TreeC 9 and 12, TreeD 9).  Any failure is LoadFailed (poseidon_api.rs:100-103) and leaves the handle as it
+ * was.  tools/poseidon_params.py writes such a CSV.
+ *
+ * ROUNDS.  This build runs the dense rounds of the definition.  The optimised partial rounds (sparse matrices) are not built:
+ * blz_poseidon_info reports 0 for them, blz_poseidon_set_round_plan accepts both settings and changes nothing. */
+enum blz_tree_mode { BLZ_TREE_C = 0, BLZ_TREE_D = 1 };   /* src/ingo_hash/utils.rs:18-30 */
+
+/* DriverClient::new + PoseidonClient::new(Hash::Poseidon, dclient) (poseidon_api.rs:77-79); field = enum blz_curve */
+int blz_poseidon_new(int device_id, int field, blz_poseidon** out);
+void blz_poseidon_free(blz_poseidon* h);
+/* PoseidonClient::loaded_binary_parameters (poseidon_api.rs:81-94): [image_id, image_parameters]; word 1 decodes with
+ * PoseidonImageParametrs (:256-271): is_stub 0, number_of_cores = min(compute units, 255) */
+int blz_poseidon_loaded_binary_parameters(blz_poseidon* h, uint32_t out[2]);
+/* PoseidonClient::initialize(PoseidonInitializeParameters{tree_height, tree_mode, instruction_path}) (poseidon_api.rs:96-111):
+ * reset, load the instruction set, height, start layer.  Allocates the tree's buffers: inputs of one tree + every layer (32 B
+ * per node) + records (64 B per node); TreeC at h = 8 holds 738 MB of input.  A call that passes the checks (arguments, stream, memory
+ * estimate) and then fails in an allocation or a transfer leaves the handle UNINITIALISED: the earlier tree's buffers are gone by then. */
+int blz_poseidon_initialize(blz_poseidon* h, uint32_t tree_height, int tree_mode, const char* instruction_path);
+/* The load-time checks alone, host side, no device (like blz_msm_plan): out (nullable) = {blocks, bit mask of the widths,
+ * 1 if every width admits the optimised partial rounds (always 0: not built), words consumed}. */
+int blz_poseidon_check_words(int field, int tree_mode, const uint8_t* words, size_t len, uint32_t out[4]);
+/* initialize with the word stream from memory (len bytes = len / 32 words) */
+int blz_poseidon_initialize_words(blz_poseidon* h, uint32_t tree_height, int tree_mode, const uint8_t* words, size_t len);
+/* PoseidonClient::set_data(&[u8]) (poseidon_api.rs:117-122): elements into the FIFO.  len a multiple of 32: len / 32 elements;
+ * 0 < len < 32 (host memory only): ONE element, zero-extended - the reference's tests write 4-byte and to_bytes_le() buffers, one
+ * element per call, and test_sanity_check expects the element counter to go up by one per call; anything else, or a call before
+ * initialize, is InvalidPrimitiveParam.  Blocking like the other set_datas (the buffer is free on return).
+ * The FIFO is a stream: nodes are hashed as soon as a worthwhile batch (1024) of complete inputs exists, and always when the tree's
+ * last element arrives; an upper node when its eight children are.  Records become pending in an unspecified order, every node
+ * exactly once and never before its children.  After a tree's last element the next element starts the next tree, ids from
+ * zero (the card runs continuously); records of the finished tree that nobody has read stay pending.  A tree whose whole input
+ * arrives in one call takes ONE kernel launch per layer. */
+int blz_poseidon_set_data(blz_poseidon* h, const uint8_t* data, size_t len);
+int blz_poseidon_set_data_device(blz_poseidon* h, const void* d_data, size_t len);
+/* PoseidonClient::wait_result is todo!() in the reference (poseidon_api.rs:124-126).  Here: when it returns, every node whose
+ * inputs have arrived has been hashed and its record is pending.  Bounded (BLAZE_WAIT_TIMEOUT_MS, reset-only rule as above). */
+int blz_poseidon_wait_result(blz_poseidon* h);
+/* PoseidonClient::get_num_of_pending_results (poseidon_api.rs:156-161) */
+int blz_poseidon_num_pending_results(blz_poseidon* h, uint32_t* out);
+/* PoseidonClient::get_raw_results(n) (poseidon_api.rs:191-196): pops n (<= pending) records, 64 n bytes */
+int blz_poseidon_raw_results(blz_poseidon* h, uint32_t n, uint8_t* out, size_t cap);
+/* PoseidonClient::result(Some(expected)) (poseidon_api.rs:128-145): pops up to `expected` records, *n says how many.  Bounded where
+ * the reference spins: everything the elements fed so far can produce is hashed first; if that is fewer than `expected` records
+ * the call returns them (the reference would poll for ever). */
+int blz_poseidon_result(blz_poseidon* h, uint32_t expected, uint8_t* out, size_t cap, uint32_t* n);
+/* every record of the finished tree in (layer, id) order, device to device; pops them.  Needs a finished tree none of whose records
+ * has been read and no older records pending.  No reference counterpart (see blz_msm_set_data_device). */
+int blz_poseidon_tree_device(blz_poseidon* h, void* d_out, size_t cap);
+/* out = {elements accepted since initialize, modulo 2^32 (LAST_ELEMENT_ID_SENT_TO_RING, poseidon_api.rs:149-154: + 1 per element),
+ * hash_id of the last record handed to the host (LAST_HASH_ID_SENT_TO_HOST, :198-203), its layer_id, elements of the current
+ * tree no hash has consumed yet} */
+int blz_poseidon_counters(blz_poseidon* h, uint32_t out[4]);
+/* out = {device bytes held, 1 if the optimised partial rounds are in force (always 0 in this build), state of their self-check
+ * (0 not run, 1 equal, 2 refused; always 0), bit mask of the widths loaded} */
+int blz_poseidon_info(blz_poseidon* h, uint64_t out[4]);
+/* 1 (default): optimised partial rounds where their self-check holds; 0: dense always.  This build is dense either way. */
+int blz_poseidon_set_round_plan(blz_poseidon* h, int enable);
+/* device time from the first layer launch of the last finished tree to its last, ms */
+int blz_poseidon_last_kernel_ms(blz_poseidon* h, float* out);
+/* the HIP stream the layer kernels run on; see blz_msm_stream */
+int blz_poseidon_stream(blz_poseidon* h, void** hip_stream, int* device_id);
+/* DriverClient::reset (dclient.rs:88-93): drops the partial tree and every pending record; the instruction set, the height and
+ * the mode stay */
+int blz_poseidon_reset(blz_poseidon* h);
 
 /* ------------------------------------------------------------------ device / host memory helpers */
 

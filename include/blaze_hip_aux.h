@@ -53,6 +53,22 @@ int blz_test_field_op(int device_id, int curve, int field, int op, const uint8_t
 int blz_test_ec_op(int device_id, int curve, int op, const uint8_t* p, const uint8_t* q,
                    const uint8_t* inf_flags, uint8_t* out, uint8_t* out_inf, size_t n);
 
+/* ------------------------------------------------------------------ Poseidon (blaze_hip.h "Poseidon")
+ * words / len: an instruction word stream as blz_poseidon_initialize_words takes it.
+ * blz_test_poseidon_permute: the DEFINITION kernel - one lane per state, the dense textbook rounds on the 8 x 32-bit Montgomery
+ *   arithmetic (fp_mul, fp_add), sharing neither representation nor schedule with the product path; slow on purpose.  n states of
+ *   t words each (host pointers; any 256-bit words, taken as residues), permuted, canonical.
+ * blz_test_poseidon_hash: the PRODUCT path's kernel of width t on n independent inputs of t - 1 words (host pointers): n digests.
+ * blz_test_poseidon_tree_check: every node of a finished tree re-hashed from its children by the definition kernel and compared
+ *   on the device: d_input the tree's elements, d_records its records as blz_poseidon_tree_device returns them;
+ *   out = {nodes checked, nodes whose record differs}. */
+int blz_test_poseidon_permute(int device_id, int field, const uint8_t* words, size_t len, int t, const uint8_t* states_in,
+                              uint8_t* states_out, size_t n);
+int blz_test_poseidon_hash(int device_id, int field, const uint8_t* words, size_t len, int t, const uint8_t* inputs, uint8_t* digests,
+                           size_t n);
+int blz_test_poseidon_tree_check(int device_id, int field, const uint8_t* words, size_t len, int tree_mode, uint32_t tree_height,
+                                 const void* d_input, const void* d_records, uint64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

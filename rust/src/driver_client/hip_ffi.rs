@@ -13,6 +13,10 @@ pub struct BlzMsm {
 pub struct BlzNtt {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct BlzPoseidon {
+    _private: [u8; 0],
+}
 
 pub const BLZ_COMM_ID_BYTES: usize = 128;
 
@@ -96,4 +100,25 @@ extern "C" {
     pub fn blz_ntt_result(h: *mut BlzNtt, buf: usize, out: *mut u8, out_cap: usize) -> c_int;
     pub fn blz_ntt_reset(h: *mut BlzNtt) -> c_int;
     pub fn blz_ntt_last_kernel_ms(h: *mut BlzNtt, out: *mut f32) -> c_int;
+
+    // ---- Poseidon tree: PoseidonClient (ingo_hash::poseidon_api)
+    pub fn blz_poseidon_new(device_id: c_int, field: c_int, out: *mut *mut BlzPoseidon) -> c_int;
+    pub fn blz_poseidon_free(h: *mut BlzPoseidon);
+    pub fn blz_poseidon_loaded_binary_parameters(h: *mut BlzPoseidon, out: *mut u32) -> c_int;
+    pub fn blz_poseidon_initialize(h: *mut BlzPoseidon, tree_height: u32, tree_mode: c_int, instruction_path: *const c_char) -> c_int;
+    pub fn blz_poseidon_check_words(field: c_int, tree_mode: c_int, words: *const u8, len: usize, out: *mut u32) -> c_int;
+    pub fn blz_poseidon_initialize_words(h: *mut BlzPoseidon, tree_height: u32, tree_mode: c_int, words: *const u8, len: usize) -> c_int;
+    pub fn blz_poseidon_set_data(h: *mut BlzPoseidon, data: *const u8, len: usize) -> c_int;
+    pub fn blz_poseidon_set_data_device(h: *mut BlzPoseidon, d_data: *const c_void, len: usize) -> c_int;
+    pub fn blz_poseidon_wait_result(h: *mut BlzPoseidon) -> c_int;
+    pub fn blz_poseidon_num_pending_results(h: *mut BlzPoseidon, out: *mut u32) -> c_int;
+    pub fn blz_poseidon_raw_results(h: *mut BlzPoseidon, n: u32, out: *mut u8, cap: usize) -> c_int;
+    pub fn blz_poseidon_result(h: *mut BlzPoseidon, expected: u32, out: *mut u8, cap: usize, n: *mut u32) -> c_int;
+    pub fn blz_poseidon_tree_device(h: *mut BlzPoseidon, d_out: *mut c_void, cap: usize) -> c_int;
+    pub fn blz_poseidon_counters(h: *mut BlzPoseidon, out: *mut u32) -> c_int;
+    pub fn blz_poseidon_info(h: *mut BlzPoseidon, out: *mut u64) -> c_int;
+    pub fn blz_poseidon_set_round_plan(h: *mut BlzPoseidon, enable: c_int) -> c_int;
+    pub fn blz_poseidon_last_kernel_ms(h: *mut BlzPoseidon, out: *mut f32) -> c_int;
+    pub fn blz_poseidon_stream(h: *mut BlzPoseidon, hip_stream: *mut *mut c_void, device_id: *mut c_int) -> c_int;
+    pub fn blz_poseidon_reset(h: *mut BlzPoseidon) -> c_int;
 }
