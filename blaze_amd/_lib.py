@@ -123,6 +123,7 @@ _SIGS = {
     "blz_poseidon_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "blz_poseidon_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "blz_poseidon_set_round_plan": (C.c_int, [C.c_void_p, C.c_int]),
+    "blz_poseidon_prepare_round_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "blz_poseidon_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blz_poseidon_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     "blz_poseidon_reset": (C.c_int, [C.c_void_p]),
@@ -148,6 +149,7 @@ _AUX_SIGS = {
     "blz_test_ec_op": (C.c_int, [C.c_int, C.c_int, C.c_int, _u8p, _u8p, _u8p, _u8p, _u8p, C.c_size_t]),
     "blz_test_poseidon_permute": (C.c_int, [C.c_int, C.c_int, _u8p, C.c_size_t, C.c_int, _u8p, _u8p, C.c_size_t]),
     "blz_test_poseidon_hash": (C.c_int, [C.c_int, C.c_int, _u8p, C.c_size_t, C.c_int, _u8p, _u8p, C.c_size_t]),
+    "blz_test_poseidon_hash_plan": (C.c_int, [C.c_int, C.c_int, _u8p, C.c_size_t, C.c_int, _u8p, _u8p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "blz_test_poseidon_tree_check": (C.c_int, [C.c_int, C.c_int, _u8p, C.c_size_t, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 AUX_EXPORTED_SYMBOLS = tuple(_AUX_SIGS)

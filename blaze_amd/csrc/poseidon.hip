@@ -1,7 +1,8 @@
 // Poseidon octal Merkle-tree client for gfx950: the device behind src/ingo_hash/poseidon_api.rs (the reference's third
 // DriverPrimitive).  include/blaze_hip.h "Poseidon" states the hash, the tree, the record and the instruction stream;
 // DESIGN.md section 8 the kernel.  This file is the host side: the stream's parser and checks, the element FIFO, the layer
-// schedule (one launch per layer for a tree that arrives in one call) and the record queue.
+// schedule (one launch per layer for a tree that arrives in one call), the record queue, and the preparation of the optimised
+// partial rounds (derived and self-checked on the device: this file has no field arithmetic, it only compares words with r).
 #include <algorithm>
 #include <deque>
 #include <fstream>
@@ -185,7 +186,14 @@ struct blz_poseidon {
     int mode = BLZ_TREE_C;
     uint32_t width_mask = 0;
     PoseidonWidth w[POS_T_MAX + 1];
+    std::vector<PoseidonBlock> blocks;   // where each width's words are inside `raw`
     DevBuf raw, consts, input, layers, records;
+    // the optimised partial rounds: the switch (kept across initialize), their tables and the state of their self-check (per
+    // loaded instruction set: 0 not prepared yet, HADES_OK, HADES_REFUSED - then every width runs the dense rounds)
+    int plan_setting = 1;
+    uint32_t plan_state = 0;
+    DevBuf plan;
+    HadesPlan pl[POS_T_MAX + 1];
     uint64_t n_in = 0;                    // elements of one tree's FIFO
     int first_layer = 0;                  // lowest layer that is hashed (0 TreeC, 1 TreeD)
     std::vector<uint64_t> lay_n, lay_off, rec_off;   // nodes of layer l; its first digest / record (in nodes; layers below first_layer: unused)
@@ -240,6 +248,96 @@ void pos_drop_stream_state(blz_poseidon* h) {
     h->timing_open = false;
 }
 
+bool pos_plan_in_force(const blz_poseidon* h) { return h->plan_setting == 1 && h->plan_state == HADES_OK; }
+
+// The self-check's inputs for one width: n hashes of t - 1 words.  Fixed: the words 0, r - 1, r, r + 1, 2^256 - 1 in every
+// position of a hash of their own, then words of a xorshift generator (any 256-bit words: about half of them are >= r).
+void pos_check_batch(const uint32_t (&modulus)[8], int t, size_t n, std::vector<uint32_t>& out) {
+    const size_t a = (size_t)t - 1;
+    out.assign(n * a * 8, 0u);
+    uint64_t sx = 0x9E3779B97F4A7C15ull ^ ((uint64_t)t << 32);
+    for (size_t i = 0; i < n; ++i)
+        for (size_t k = 0; k < a; ++k) {
+            uint32_t* wd = out.data() + (i * a + k) * 8;
+            if (i == 0) continue;                                              // 0
+            if (i <= 3) {                                                      // r - 1, r, r + 1  (r is odd and its low word is not 0)
+                for (int q = 0; q < 8; ++q) wd[q] = modulus[q];
+                wd[0] += (uint32_t)i - 2u;
+            } else if (i == 4) {
+                for (int q = 0; q < 8; ++q) wd[q] = 0xffffffffu;
+            } else {
+                for (int q = 0; q < 8; ++q) {
+                    sx ^= sx << 13; sx ^= sx >> 7; sx ^= sx << 17;
+                    wd[q] = (uint32_t)(sx >> 16);
+                }
+            }
+        }
+}
+
+constexpr size_t POS_CHECK_HASHES = 320;   // per derived width: 64 waves' worth at t = 12, a ragged last block at every width
+
+// Derive the tables of the widths the tree mode hashes with, then hash a fixed batch per width with both kernels and compare.
+// Leaves plan_state at HADES_OK or HADES_REFUSED; a refusal is not an error.  Blocking, every wait bounded.
+int pos_prepare_plan(blz_poseidon* h) {
+    if (h->plan_state != 0) return BLZ_OK;
+    const uint32_t need = poseidon_need_mask(h->mode);
+    size_t elements = 0, nw = 0;
+    for (const auto& b : h->blocks)
+        if (need & (1u << b.t)) { elements += hades_plan_elements(b.t, b.rp); ++nw; }
+    const size_t status_at = elements * POS_SD * 4;
+    BLZ_TRY(h->plan.reserve(status_at + POS_T_MAX * 4 + 16, true));
+    uint32_t* const tables = h->plan.as<uint32_t>();
+    uint32_t* const d_status = tables + elements * POS_SD;
+    BLZ_HIP(hipMemsetAsync(d_status, 0, nw * 4, h->stream), BLZ_ERR_UNKNOWN);
+    size_t at = 0, k = 0;
+    for (const auto& b : h->blocks) {
+        if (!(need & (1u << b.t))) continue;
+        uint32_t* const tb = tables + at * POS_SD;
+        BLZ_TRY(h->ops->derive(h->stream, h->raw.as<uint32_t>() + b.tag * 8, b.t, b.rf, b.rp, tb, d_status + k));
+        h->pl[b.t] = hades_plan_at(tb, b.t, b.rp);
+        at += hades_plan_elements(b.t, b.rp);
+        ++k;
+    }
+    uint32_t status[POS_T_MAX] = {};
+    BLZ_POS_WAIT(h, sync_stream_bounded(h->stream, "round plan: derivation"));
+    BLZ_HIP(hipMemcpy(status, d_status, nw * 4, hipMemcpyDeviceToHost), BLZ_ERR_READ);
+    uint32_t state = HADES_OK;
+    for (size_t i = 0; i < nw; ++i)
+        if (status[i] != HADES_OK) state = HADES_REFUSED;
+    // the self-check: both kernels on the same inputs, digests compared word for word
+    DevBuf in, dig;
+    std::vector<uint32_t> words, got(2 * POS_CHECK_HASHES * 8);
+    int rc = BLZ_OK;
+    for (const auto& b : h->blocks) {
+        if (state != HADES_OK || rc != BLZ_OK) break;
+        if (!(need & (1u << b.t))) continue;
+        pos_check_batch(h->ops->modulus, b.t, POS_CHECK_HASHES, words);
+        if ((rc = in.reserve(words.size() * 4, true)) != BLZ_OK) break;
+        if ((rc = dig.reserve(got.size() * 4, true)) != BLZ_OK) break;
+        if (hipMemcpyAsync(in.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(BLZ_ERR_WRITE, "round plan: self-check inputs"); break; }
+        PoseidonJob job;
+        job.in = in.as<uint32_t>();
+        job.dig = dig.as<uint32_t>();
+        job.n = POS_CHECK_HASHES;
+        if ((rc = h->ops->hash(h->stream, h->w[b.t], job)) != BLZ_OK) break;
+        job.dig += POS_CHECK_HASHES * 8;
+        if ((rc = h->ops->hash_plan(h->stream, h->w[b.t], h->pl[b.t], job)) != BLZ_OK) break;
+        blz::wait_clear();
+        if ((rc = sync_stream_bounded(h->stream, "round plan: self-check")) != BLZ_OK) {
+            if (blz::wait_timed_out()) h->wedged = true;   // (the buffers stay: the kernels may still write them)
+            return rc;
+        }
+        if (hipMemcpy(got.data(), dig.p, got.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(BLZ_ERR_READ, "round plan: self-check digests"); break; }
+        if (memcmp(got.data(), got.data() + POS_CHECK_HASHES * 8, POS_CHECK_HASHES * 32) != 0) state = HADES_REFUSED;
+    }
+    in.release();
+    dig.release();
+    BLZ_TRY(rc);
+    h->plan_state = state;
+    BLZ_LOG(1, "Poseidon round plan: %s", state == HADES_OK ? "optimised partial rounds, self-check equal" : "refused (singular matrix or self-check): dense rounds");
+    return BLZ_OK;
+}
+
 // hash what can be hashed: every layer's nodes whose inputs exist, lowest layer first.  force: whatever the batch size.
 int pos_advance(blz_poseidon* h, bool force) {
     const bool last = h->received == h->n_in;
@@ -259,11 +357,16 @@ int pos_advance(blz_poseidon* h, bool force) {
         job.id0 = d0;
         job.layer = (uint32_t)l;
         if (!h->timing_open) {
+            // the round plan is prepared before a tree's first launch, outside the timed window (a switch set in mid-tree
+            // finds it at the next tree)
+            if (h->plan_setting == 1) BLZ_TRY(pos_prepare_plan(h));
             BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
             h->timing_open = true;
             h->timing_valid = false;
         }
-        BLZ_TRY(h->ops->hash(h->stream, h->w[l == 0 ? 12 : 9], job));
+        const int t = l == 0 ? 12 : 9;
+        if (pos_plan_in_force(h)) BLZ_TRY(h->ops->hash_plan(h->stream, h->w[t], h->pl[t], job));
+        else BLZ_TRY(h->ops->hash(h->stream, h->w[t], job));
         if (l == h->first_layer) {   // the launches that read the FIFO buffer
             BLZ_HIP(hipEventRecord(h->ev_in, h->stream), BLZ_ERR_UNKNOWN);
             h->in_busy = true;
@@ -409,7 +512,9 @@ int pos_initialize_core(blz_poseidon* h, uint32_t tree_height, int tree_mode, co
     BLZ_POS_WAIT(h, sync_stream_bounded(h->stream, "initialize: Poseidon stream"));
     BLZ_POS_WAIT(h, sync_stream_bounded(h->copy_stream, "initialize: Poseidon copy stream"));
     h->initialized = false;
-    h->input.release(); h->layers.release(); h->records.release(); h->raw.release(); h->consts.release();
+    h->input.release(); h->layers.release(); h->records.release(); h->raw.release(); h->consts.release(); h->plan.release();
+    h->plan_state = 0;
+    for (auto& x : h->pl) x = HadesPlan{};
     BLZ_TRY(poseidon_upload(h->ops, h->stream, ps, words, h->raw, h->consts, h->w));
     BLZ_TRY(h->input.reserve(bytes_in, true));
     BLZ_TRY(h->layers.reserve(bytes_lay ? bytes_lay : WORD, true));
@@ -418,6 +523,7 @@ int pos_initialize_core(blz_poseidon* h, uint32_t tree_height, int tree_mode, co
     h->height = tree_height;
     h->mode = tree_mode;
     h->width_mask = ps.width_mask;
+    h->blocks = ps.blocks;
     h->n_in = n_in;
     h->first_layer = first_layer;
     h->lay_n = lay_n; h->lay_off = lay_off; h->rec_off = rec_off;
@@ -429,8 +535,8 @@ int pos_initialize_core(blz_poseidon* h, uint32_t tree_height, int tree_mode, co
     h->last_hash_id = h->last_layer = 0;
     h->timing_valid = false;
     h->initialized = true;
-    BLZ_LOG(1, "Poseidon: height %u, %s, widths 0x%x, dense rounds (no optimised partial rounds in this build), %llu bytes", tree_height,
-            tree_mode == BLZ_TREE_C ? "TreeC" : "TreeD", ps.width_mask, (unsigned long long)(bytes_in + bytes_lay + bytes_rec));
+    BLZ_LOG(1, "Poseidon: height %u, %s, widths 0x%x, round plan %d (prepared before the first tree), %llu bytes", tree_height,
+            tree_mode == BLZ_TREE_C ? "TreeC" : "TreeD", ps.width_mask, h->plan_setting, (unsigned long long)(bytes_in + bytes_lay + bytes_rec));
     return BLZ_OK;
 }
 
@@ -480,7 +586,7 @@ void blz_poseidon_free(blz_poseidon* h) {
         delete h;
         return;
     }
-    h->input.release(); h->layers.release(); h->records.release(); h->raw.release(); h->consts.release();
+    h->input.release(); h->layers.release(); h->records.release(); h->raw.release(); h->consts.release(); h->plan.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev_in) (void)hipEventDestroy(h->ev_in);
@@ -509,7 +615,7 @@ int blz_poseidon_check_words(int field, int tree_mode, const uint8_t* words, siz
     if (out) {
         out[0] = (uint32_t)ps.blocks.size();
         out[1] = ps.width_mask;
-        out[2] = 0;   // this build runs the dense rounds only
+        out[2] = 0;   // admission needs field arithmetic (is Mh invertible?): blz_poseidon_prepare_round_plan / blz_poseidon_info answer
         out[3] = (uint32_t)ps.consumed;
     }
     return BLZ_OK;
@@ -610,9 +716,9 @@ int blz_poseidon_counters(blz_poseidon* h, uint32_t out[4]) {
 
 int blz_poseidon_info(blz_poseidon* h, uint64_t out[4]) {
     if (!h || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
-    out[0] = (uint64_t)(h->input.cap + h->layers.cap + h->records.cap + h->raw.cap + h->consts.cap);
-    out[1] = 0;   // dense rounds: this build has no optimised partial rounds
-    out[2] = 0;
+    out[0] = (uint64_t)(h->input.cap + h->layers.cap + h->records.cap + h->raw.cap + h->consts.cap + h->plan.cap);
+    out[1] = pos_plan_in_force(h) ? 1u : 0u;
+    out[2] = h->plan_state;
     out[3] = h->initialized ? h->width_mask : 0u;
     return BLZ_OK;
 }
@@ -620,7 +726,23 @@ int blz_poseidon_info(blz_poseidon* h, uint64_t out[4]) {
 int blz_poseidon_set_round_plan(blz_poseidon* h, int enable) {
     if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
     if (enable != 0 && enable != 1) return fail(BLZ_ERR_INVALID_PARAM, "round plan %d (0 dense, 1 optimised partial rounds where their self-check holds)", enable);
-    // (nothing to store: the optimised rounds are not built, both settings run the dense rounds)
+    // takes effect at the next layer launch (the bytes are the same either way); tables derived earlier are kept and reused
+    h->plan_setting = enable;
+    return BLZ_OK;
+}
+
+int blz_poseidon_prepare_round_plan(blz_poseidon* h, uint32_t out[2]) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    BLZ_POS_LIVE(h);
+    if (!h->initialized) return fail(BLZ_ERR_INVALID_PARAM, "prepare_round_plan before initialize");
+    if (h->plan_setting == 1) {
+        BLZ_TRY(use_device(h->device));
+        BLZ_TRY(pos_prepare_plan(h));
+    }
+    if (out) {
+        out[0] = pos_plan_in_force(h) ? 1u : 0u;
+        out[1] = h->plan_state;
+    }
     return BLZ_OK;
 }
 

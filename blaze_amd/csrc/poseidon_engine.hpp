@@ -28,13 +28,37 @@ struct PoseidonJob {
     uint32_t layer = 0;
 };
 
+// The optimised partial rounds of one width, derived on the device from the block's words; same element
+// format as PoseidonWidth.  Partial round k = 0 .. rp - 1: lane e reads sp[(2 k) t + e] (row 0 of the sparse matrix: v^T Mh^-j, slot 0
+// unused) and sp[(2 k + 1) t + e] (its column 0: m00, then Mh^(j-1) w), and the constant prc[k t + e].
+struct HadesPlan {
+    const uint32_t* sp = nullptr;    // 2 t rp elements
+    const uint32_t* prc = nullptr;   // t rp elements: diag(1, Mh^j) c_k
+    const uint32_t* pre = nullptr;   // t t elements, row-major: diag(1, Mh^rp) M, the matrix of the last full round of the first half
+};
+inline size_t hades_plan_elements(int t, int rp) { return (size_t)3 * t * rp + (size_t)t * t; }
+constexpr uint32_t HADES_OK = 1, HADES_REFUSED = 2;   // blz_poseidon_info word 2
+
 struct PoseidonFieldOps {
     uint32_t modulus[8];   // r, 32-bit words, little-endian
     // canonical 32-byte words -> the device form above (n elements, out: n * POS_SD dwords)
     int (*prep)(hipStream_t st, const uint32_t* d_words, uint32_t* d_out, uint32_t n);
     // the product path: one launch for the whole job
     int (*hash)(hipStream_t st, const PoseidonWidth& w, const PoseidonJob& job);
+    // d_block: the block's canonical words on the device, from its tag on (tag | round constants | matrix).  Fills the plan's tables
+    // and *d_status = HADES_OK, or *d_status = HADES_REFUSED when the matrix without row 0 and column 0 has no inverse
+    int (*derive)(hipStream_t st, const uint32_t* d_block, int t, int rf, int rp, uint32_t* d_tables, uint32_t* d_status);
+    // the same job through the optimised partial rounds
+    int (*hash_plan)(hipStream_t st, const PoseidonWidth& w, const HadesPlan& pl, const PoseidonJob& job);
 };
+// where derive() put width t's tables inside d_tables
+inline HadesPlan hades_plan_at(const uint32_t* d_tables, int t, int rp) {
+    HadesPlan pl;
+    pl.sp = d_tables;
+    pl.prc = pl.sp + (size_t)2 * t * rp * POS_SD;
+    pl.pre = pl.prc + (size_t)t * rp * POS_SD;
+    return pl;
+}
 const PoseidonFieldOps& poseidon_ops_bls377();
 const PoseidonFieldOps& poseidon_ops_bls381();
 const PoseidonFieldOps& poseidon_ops_bn254();

@@ -193,6 +193,12 @@ int poseidon_hash_t(hipStream_t st, const PoseidonWidth& w, const PoseidonJob& j
     return fail(BLZ_ERR_INVALID_PARAM, "no Poseidon kernel of width %d", w.t);
 }
 
+}  // namespace blz
+
+#include "poseidon_hades.hip.hpp"   // the optimised partial rounds: k_hades_derive, k_hades_hash
+
+namespace blz {
+
 template <class Fr>
 PoseidonFieldOps make_poseidon_ops() {
     using Q = typename Fr::RR;
@@ -201,6 +207,8 @@ PoseidonFieldOps make_poseidon_ops() {
     for (int i = 0; i < 8; ++i) ops.modulus[i] = Fr::MOD[i];
     ops.prep = &poseidon_prep_t<Q>;
     ops.hash = &poseidon_hash_t<Q>;
+    ops.derive = &hades_derive_t<Fr>;
+    ops.hash_plan = &hades_hash_t<Q>;
     return ops;
 }
 

@@ -396,7 +396,10 @@ __global__ __launch_bounds__(64) void k_test_pos_check_layer(const uint32_t* con
 }
 
 // the product path's kernel of width t on n independent inputs (device pointers): what the tree's layers run.  Blocking.
-static int poseidon_hash_batch(int device_id, int field, const uint8_t* words, size_t len, int t, const void* d_in, void* d_out, uint64_t n) {
+// plan_state != nullptr: through the optimised partial rounds, derived here for width t; *plan_state = HADES_REFUSED and no
+// digests when the width does not admit them.
+static int poseidon_hash_batch(int device_id, int field, const uint8_t* words, size_t len, int t, const void* d_in, void* d_out, uint64_t n,
+                               uint32_t* plan_state = nullptr) {
     const PoseidonFieldOps* ops = poseidon_ops_for(field);
     if (!ops) return fail(BLZ_ERR_INVALID_PARAM, "unknown field %d", field);
     if (!words || !d_in || !d_out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
@@ -404,19 +407,34 @@ static int poseidon_hash_batch(int device_id, int field, const uint8_t* words, s
     PoseidonStream ps;
     BLZ_TRY(poseidon_parse(field, 1u << t, words, len, ps));
     BLZ_TRY(use_device(device_id));
-    DevBuf raw, consts;
+    DevBuf raw, consts, plan;
     PoseidonWidth w[POS_T_MAX + 1];
     int rc = poseidon_upload(ops, nullptr, ps, words, raw, consts, w);
-    if (rc == BLZ_OK) {
+    HadesPlan pl;
+    if (rc == BLZ_OK && plan_state) {
+        const PoseidonBlock* blk = nullptr;
+        for (const auto& b : ps.blocks)
+            if (b.t == t) blk = &b;
+        const size_t el = hades_plan_elements(t, blk->rp);
+        rc = plan.reserve(el * POS_SD * 4 + 16, true);
+        uint32_t* const d_status = plan.as<uint32_t>() + el * POS_SD;
+        if (rc == BLZ_OK && hipMemset(d_status, 0, 4) != hipSuccess) rc = fail(BLZ_ERR_UNKNOWN, "hipMemset failed");
+        if (rc == BLZ_OK) rc = ops->derive(nullptr, raw.as<uint32_t>() + blk->tag * 8, t, blk->rf, blk->rp, plan.as<uint32_t>(), d_status);
+        if (rc == BLZ_OK) rc = sync_stream_bounded(nullptr, "Poseidon round plan derivation");
+        if (rc == BLZ_OK && hipMemcpy(plan_state, d_status, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(BLZ_ERR_READ, "hipMemcpy failed");
+        pl = hades_plan_at(plan.as<uint32_t>(), t, blk->rp);
+    }
+    if (rc == BLZ_OK && !(plan_state && *plan_state != HADES_OK)) {
         PoseidonJob job;
         job.in = (const uint32_t*)d_in;
         job.dig = (uint32_t*)d_out;
         job.n = n;
-        rc = ops->hash(nullptr, w[t], job);
+        rc = plan_state ? ops->hash_plan(nullptr, w[t], pl, job) : ops->hash(nullptr, w[t], job);
     }
     if (rc == BLZ_OK) rc = sync_stream_bounded(nullptr, "Poseidon hash batch");
     raw.release();
     consts.release();
+    plan.release();
     return rc;
 }
 
@@ -565,6 +583,21 @@ int blz_test_poseidon_hash(int device_id, int field, const uint8_t* words, size_
     BLZ_HIP(hipMemcpy(din, inputs, n * (size_t)(t - 1) * 32, hipMemcpyHostToDevice), BLZ_ERR_WRITE);
     BLZ_TRY(poseidon_hash_batch(device_id, field, words, len, t, din, dout, n));
     BLZ_HIP(hipMemcpy(digests, dout, n * 32, hipMemcpyDeviceToHost), BLZ_ERR_READ);
+    return BLZ_OK;
+}
+
+int blz_test_poseidon_hash_plan(int device_id, int field, const uint8_t* words, size_t len, int t, const uint8_t* inputs, uint8_t* digests, size_t n,
+                                uint32_t* state) {
+    if (!words || !inputs || !digests || !state) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    if (t < 2 || t > 16) return fail(BLZ_ERR_INVALID_PARAM, "width %d out of range", t);
+    BLZ_TRY(use_device(device_id));
+    *state = 0;
+    Tmp tmp;
+    void *din, *dout;
+    BLZ_TRY(tmp.alloc(&din, (n ? n : 1) * (size_t)(t - 1) * 32)); BLZ_TRY(tmp.alloc(&dout, (n ? n : 1) * 32));
+    BLZ_HIP(hipMemcpy(din, inputs, n * (size_t)(t - 1) * 32, hipMemcpyHostToDevice), BLZ_ERR_WRITE);
+    BLZ_TRY(poseidon_hash_batch(device_id, field, words, len, t, din, dout, n, state));
+    if (*state == HADES_OK) BLZ_HIP(hipMemcpy(digests, dout, n * 32, hipMemcpyDeviceToHost), BLZ_ERR_READ);
     return BLZ_OK;
 }
 

@@ -173,6 +173,13 @@ class PoseidonClient(DriverPrimitive[Hash, PoseidonInitializeParameters, bytes, 
     def set_round_plan(self, enable: bool) -> None:
         check(lib().blz_poseidon_set_round_plan(self._h, 1 if enable else 0))
 
+    def prepare_round_plan(self) -> dict:
+        """derive and self-check the optimised partial rounds now, not under the first tree (blz_poseidon_prepare_round_plan);
+        the two words info() reports: in force, and the self-check's state (0 not run, 1 equal, 2 refused: dense rounds)"""
+        v = (C.c_uint32 * 2)()
+        check(lib().blz_poseidon_prepare_round_plan(self._h, v))
+        return {"optimised_partial_rounds": bool(v[0]), "round_plan_check": int(v[1])}
+
     def last_kernel_ms(self) -> float:
         v = C.c_float()
         check(lib().blz_poseidon_last_kernel_ms(self._h, C.byref(v)))
@@ -187,4 +194,5 @@ def check_words(field: str, tree_mode: TreeMode, words) -> dict:
     p, n, _k = buf_ptr(words)
     v = (C.c_uint32 * 4)()
     check(lib().blz_poseidon_check_words(PoseidonClient._FIELDS[field], int(tree_mode), p, n, v))
+    # (word 2 is always 0: whether the widths admit the optimised rounds is PoseidonClient.prepare_round_plan's answer)
     return {"blocks": int(v[0]), "width_mask": int(v[1]), "optimised_partial_rounds": bool(v[2]), "words": int(v[3])}

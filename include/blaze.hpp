@@ -331,6 +331,13 @@ class PoseidonClient : public DriverPrimitive<Hash, PoseidonInitializeParameters
         check(blz_poseidon_initialize_words(h_, tree_height, int(mode), words.data(), words.size()));
     }
     void reset() { check(blz_poseidon_reset(h_)); }
+    void set_round_plan(bool enable) { check(blz_poseidon_set_round_plan(h_, enable ? 1 : 0)); }
+    // derive and self-check the optimised partial rounds now: {in force, self-check state (1 equal, 2 refused: dense rounds)}
+    std::array<uint32_t, 2> prepare_round_plan() {
+        std::array<uint32_t, 2> v{};
+        check(blz_poseidon_prepare_round_plan(h_, v.data()));
+        return v;
+    }
 };
 
 }  // namespace ingo_blaze

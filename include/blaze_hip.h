@@ -439,8 +439,15 @@ int blz_ntt_banks_postprocess_device(blz_ntt* h, const void* d_banks, void* d_ou
  * needs are present (TreeC 9 and 12, TreeD 9).  Any failure is LoadFailed (poseidon_api.rs:100-103) and leaves the handle as it
  * was.  tools/poseidon_params.py writes such a CSV.
  *
- * ROUNDS.  This build runs the dense rounds of the definition.  The optimised partial rounds (sparse matrices) are not built:
- * blz_poseidon_info reports 0 for them, blz_poseidon_set_round_plan accepts both settings and changes nothing. */
+ * ROUNDS.  The dense rounds above are the definition; by default the R_P partial rounds run in their optimised form, which gives
+ * the same bytes.  With M = [[m00, v^T], [w, Mh]] (Mh: M without row 0 and column 0) partial round k = 1 .. R_P, j = R_P - k + 1,
+ * multiplies by the sparse matrix [[m00, v^T Mh^-j], [Mh^(j-1) w, I]] (2t - 1 products instead of t^2) after adding the constants
+ * diag(1, Mh^j) c_k, and the full round in front of them multiplies by diag(1, Mh^R_P) M.  A width admits this iff Mh is
+ * invertible (R_P = 0: always).  The tables are derived ON THE DEVICE for the widths the tree mode hashes with, and self-checked:
+ * a fixed batch of inputs (0, r - 1, words >= r among them) per width through both round forms, digests compared.  Equal: the
+ * optimised rounds are in force.  A singular Mh or a differing digest: refused - the dense rounds run for every width; never an
+ * error, the records are the same.  This preparation happens once per loaded instruction set, before the first tree's first launch
+ * (outside blz_poseidon_last_kernel_ms) or when blz_poseidon_prepare_round_plan asks for it; never inside initialize. */
 enum blz_tree_mode { BLZ_TREE_C = 0, BLZ_TREE_D = 1 };   /* src/ingo_hash/utils.rs:18-30 */
 
 /* DriverClient::new + PoseidonClient::new(Hash::Poseidon, dclient) (poseidon_api.rs:77-79); field = enum blz_curve */
@@ -455,7 +462,8 @@ int blz_poseidon_loaded_binary_parameters(blz_poseidon* h, uint32_t out[2]);
  * estimate) and then fails in an allocation or a transfer leaves the handle UNINITIALISED: the earlier tree's buffers are gone by then. */
 int blz_poseidon_initialize(blz_poseidon* h, uint32_t tree_height, int tree_mode, const char* instruction_path);
 /* The load-time checks alone, host side, no device (like blz_msm_plan): out (nullable) = {blocks, bit mask of the widths,
- * 1 if every width admits the optimised partial rounds (always 0: not built), words consumed}. */
+ * 0, words consumed}.  Word 2 is reserved: whether the widths admit the optimised partial rounds takes field arithmetic, which
+ * the host side does not have - blz_poseidon_prepare_round_plan / blz_poseidon_info give that answer. */
 int blz_poseidon_check_words(int field, int tree_mode, const uint8_t* words, size_t len, uint32_t out[4]);
 /* initialize with the word stream from memory (len bytes = len / 32 words) */
 int blz_poseidon_initialize_words(blz_poseidon* h, uint32_t tree_height, int tree_mode, const uint8_t* words, size_t len);
@@ -488,11 +496,17 @@ int blz_poseidon_tree_device(blz_poseidon* h, void* d_out, size_t cap);
  * hash_id of the last record handed to the host (LAST_HASH_ID_SENT_TO_HOST, :198-203), its layer_id, elements of the current
  * tree no hash has consumed yet} */
 int blz_poseidon_counters(blz_poseidon* h, uint32_t out[4]);
-/* out = {device bytes held, 1 if the optimised partial rounds are in force (always 0 in this build), state of their self-check
- * (0 not run, 1 equal, 2 refused; always 0), bit mask of the widths loaded} */
+/* out = {device bytes held (the derived tables included), 1 if the optimised partial rounds are in force (setting 1 and self-check
+ * equal), state of their self-check for the loaded instruction set (0 not run yet, 1 equal, 2 refused), bit mask of the widths loaded} */
 int blz_poseidon_info(blz_poseidon* h, uint64_t out[4]);
-/* 1 (default): optimised partial rounds where their self-check holds; 0: dense always.  This build is dense either way. */
+/* 1 (default): optimised partial rounds if their self-check holds; 0: dense always, at once.  Back to 1 reuses the tables already
+ * derived.  The setting survives initialize and reset; initialize discards the tables and the self-check state, reset keeps them. */
 int blz_poseidon_set_round_plan(blz_poseidon* h, int enable);
+/* Derive and self-check the optimised partial rounds NOW instead of under the first tree (cf. blz_msm_prepare_window_table).
+ * out (nullable) = {in force, self-check state} as blz_poseidon_info reports them.  With the setting at 0 it does nothing and
+ * returns OK.  Null handle: InvalidPrimitiveParam; before initialize: InvalidPrimitiveParam; wedged handle: Unknown.  Blocking,
+ * bounded (BLAZE_WAIT_TIMEOUT_MS).  A refusal (state 2) is not an error. */
+int blz_poseidon_prepare_round_plan(blz_poseidon* h, uint32_t out[2]);
 /* device time from the first layer launch of the last finished tree to its last, ms */
 int blz_poseidon_last_kernel_ms(blz_poseidon* h, float* out);
 /* the HIP stream the layer kernels run on; see blz_msm_stream */

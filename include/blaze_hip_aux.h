@@ -59,6 +59,8 @@ int blz_test_ec_op(int device_id, int curve, int op, const uint8_t* p, const uin
  *   arithmetic (fp_mul, fp_add), sharing neither representation nor schedule with the product path; slow on purpose.  n states of
  *   t words each (host pointers; any 256-bit words, taken as residues), permuted, canonical.
  * blz_test_poseidon_hash: the PRODUCT path's kernel of width t on n independent inputs of t - 1 words (host pointers): n digests.
+ * blz_test_poseidon_hash_plan: the same through the OPTIMISED PARTIAL ROUNDS (k_hades_hash), derived here for width t whatever the
+ *   tree modes use: *state = 1 and n digests, or *state = 2 and no digests when the matrix without row 0 and column 0 is singular.
  * blz_test_poseidon_tree_check: every node of a finished tree re-hashed from its children by the definition kernel and compared
  *   on the device: d_input the tree's elements, d_records its records as blz_poseidon_tree_device returns them;
  *   out = {nodes checked, nodes whose record differs}. */
@@ -66,6 +68,8 @@ int blz_test_poseidon_permute(int device_id, int field, const uint8_t* words, si
                               uint8_t* states_out, size_t n);
 int blz_test_poseidon_hash(int device_id, int field, const uint8_t* words, size_t len, int t, const uint8_t* inputs, uint8_t* digests,
                            size_t n);
+int blz_test_poseidon_hash_plan(int device_id, int field, const uint8_t* words, size_t len, int t, const uint8_t* inputs, uint8_t* digests,
+                                size_t n, uint32_t* state);
 int blz_test_poseidon_tree_check(int device_id, int field, const uint8_t* words, size_t len, int tree_mode, uint32_t tree_height,
                                  const void* d_input, const void* d_records, uint64_t out[2]);
 

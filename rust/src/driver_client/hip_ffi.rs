@@ -118,6 +118,7 @@ extern "C" {
     pub fn blz_poseidon_counters(h: *mut BlzPoseidon, out: *mut u32) -> c_int;
     pub fn blz_poseidon_info(h: *mut BlzPoseidon, out: *mut u64) -> c_int;
     pub fn blz_poseidon_set_round_plan(h: *mut BlzPoseidon, enable: c_int) -> c_int;
+    pub fn blz_poseidon_prepare_round_plan(h: *mut BlzPoseidon, out: *mut u32) -> c_int;
     pub fn blz_poseidon_last_kernel_ms(h: *mut BlzPoseidon, out: *mut f32) -> c_int;
     pub fn blz_poseidon_stream(h: *mut BlzPoseidon, hip_stream: *mut *mut c_void, device_id: *mut c_int) -> c_int;
     pub fn blz_poseidon_reset(h: *mut BlzPoseidon) -> c_int;

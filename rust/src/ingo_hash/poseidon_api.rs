@@ -149,7 +149,7 @@ impl PoseidonClient {
         check(unsafe { blz_poseidon_initialize_words(self.h, tree_height, TreeMode::value(tree_mode) as i32, words.as_ptr(), words.len()) })
     }
 
-    /// The load-time checks alone (host side): `[blocks, width mask, optimised rounds possible, words consumed]`.
+    /// The load-time checks alone (host side): `[blocks, width mask, 0 (reserved: see prepare_round_plan), words consumed]`.
     pub fn check_words(field: i32, tree_mode: TreeMode, words: &[u8]) -> Result<[u32; 4]> {
         let mut v = [0u32; 4];
         check(unsafe { blz_poseidon_check_words(field, TreeMode::value(tree_mode) as i32, words.as_ptr(), words.len(), v.as_mut_ptr()) })?;
@@ -165,6 +165,14 @@ impl PoseidonClient {
 
     pub fn set_round_plan(&self, enable: bool) -> Result<()> {
         check(unsafe { blz_poseidon_set_round_plan(self.h, enable as i32) })
+    }
+
+    /// Derive and self-check the optimised partial rounds now instead of under the first tree:
+    /// `[in force, self-check state (0 not run, 1 equal, 2 refused: dense rounds)]`.
+    pub fn prepare_round_plan(&self) -> Result<[u32; 2]> {
+        let mut v = [0u32; 2];
+        check(unsafe { blz_poseidon_prepare_round_plan(self.h, v.as_mut_ptr()) })?;
+        Ok(v)
     }
 
     pub fn last_kernel_ms(&self) -> Result<f32> {

@@ -2,10 +2,15 @@
 """What a Poseidon tree costs on the device: kernel-time medians of resident TreeC h = 7 and h = 8 and
 TreeD h = 8 on BLS12-381 with tools/poseidon_params.py's t = 9 / 12 blocks of (8, 57) rounds, hashes per second, the definition kernel's time on the same inputs,
 blz_calib_mad_rate taken right behind the timed runs, and the issue fraction
-    multiply-adds the waves issue (ISA-counted: tests/test_poseidon_isa.py pins the formula to the code object) / time / that rate.
-Writes profiles/poseidon_tree.json.  The device work runs in ONE child process under its own time limit.
+    multiply-adds the waves issue (ISA-counted: tests/test_poseidon_isa.py and tests/test_poseidon_sparse_isa.py pin the formulas to
+    the code object) / time / that rate.
+BOTH round plans are measured in one process, tree by tree: set_round_plan(0) (dense rounds), then set_round_plan(1) (optimised
+partial rounds, prepared before the timed runs).  "plan_below_dense_min" says whether the plan's median is below the dense plan's
+MINIMUM of the same process: faster by more than the run-to-run spread.
+Writes profiles/poseidon_tree_sparse.json (profiles/poseidon_tree.json is the dense-only run of the build before the optimised
+rounds existed).  The device work runs in ONE child process under its own time limit.
 
-    python tools/poseidon_timing.py [--out profiles/poseidon_tree.json] [--rounds 9] [--timeout 300]
+    python tools/poseidon_timing.py [--out profiles/poseidon_tree_sparse.json] [--rounds 9] [--timeout 300]
 
 --one-tree H: nothing but one TreeC tree of height H whose whole input arrives in ONE set_data call, for a kernel trace - it must show
 one launch of the layer kernel per layer, not a batch loop (profiles/poseidon_kernel_stats.txt):
@@ -26,18 +31,27 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 QM = 72   # quotient products of a reduction on BLS12-381 Fr (81 less the 9 by the modulus's lowest limb, which is 1)
 
 
-def wave_mads(t, rounds):
-    """v_mad_u64_u32 a wave issues for the 64 // t hashes it holds: two conversions, and per round the S-box and a matrix row"""
-    return 2 * (81 + QM) + rounds * ((81 + QM) + 2 * (45 + QM) + 81 * t + QM * ((t + 5) // 6))
+RD = 9    # the quotient-digit step (rr_reduce2m)
+RF, RP = 8, 57
 
 
-def lane_mads(h, tree_c, rounds=65):
+def wave_mads(t, plan):
+    """v_mad_u64_u32 a wave issues for the 64 // t hashes it holds.  Dense: two conversions, and per round the S-box and a matrix
+    row of six products per reduction.  Plan: the full rounds with three products per reduction and the quotient-digit step, the
+    partial rounds 2 SQR + 2 MUL + that step"""
+    mul, sqr = 81 + QM, 45 + QM
+    if not plan:
+        return 2 * mul + (RF + RP) * (mul + 2 * sqr + 81 * t + QM * ((t + 5) // 6))
+    return 2 * mul + RF * (mul + 2 * sqr + 81 * t + QM * ((t + 2) // 3) + RD) + RP * (2 * sqr + 2 * mul + RD)
+
+
+def lane_mads(h, tree_c, plan):
     total = 0
     for layer in range(0 if tree_c else 1, h):
         n = 8 ** (h - 1 - layer)
         t = 12 if layer == 0 else 9
         hw = 64 // t
-        total += -(-n // hw) * wave_mads(t, rounds) * 64
+        total += -(-n // hw) * wave_mads(t, plan) * 64
     return total
 
 
@@ -51,7 +65,7 @@ def child(rounds: int) -> dict:
     import poseidon_params
 
     wb = b"".join(w.to_bytes(32, "little") for w in poseidon_params.generate("BLS381", [(9, 8, 57), (12, 8, 57)]))
-    res = {"field": "BLS381", "rounds_full_partial": [8, 57], "reps": rounds, "round_form": "dense"}
+    res = {"field": "BLS381", "rounds_full_partial": [RF, RP], "reps": rounds, "round_forms": ["dense", "plan"]}
     for name, mode, h in (("treec_h7", TreeMode.TreeC, 7), ("treec_h8", TreeMode.TreeC, 8), ("treed_h8", TreeMode.TreeD, 8)):
         tree_c = mode == TreeMode.TreeC
         n_in = (11 if tree_c else 1) * 8 ** (h - 1)
@@ -60,30 +74,40 @@ def child(rounds: int) -> dict:
         check(blaze_amd.aux().blz_synth_field_elements(0, d_in.ptr, n_in, 99 + h))
         cl = PoseidonClient(Hash.Poseidon, DriverClient(0))
         cl.initialize_words(h, mode, wb)
-        ms = []
-        for it in range(rounds + 2):
-            cl.set_data(d_in)
-            cl.wait_result()
-            if it >= 2:
-                ms.append(cl.last_kernel_ms())
-            if it < rounds + 1:
-                cl.reset()
         d_rec = DeviceBuffer(0, 64 * n_rec)
-        cl.tree_device(d_rec)
-        out = (C.c_uint64 * 2)()
-        t0 = time.perf_counter()
-        check(blaze_amd.aux().blz_test_poseidon_tree_check(0, 1, buf_ptr(wb)[0], len(wb), int(mode), h, d_in.ptr, d_rec.ptr, out))
-        def_ms = (time.perf_counter() - t0) * 1e3
-        assert out[0] == n_rec and out[1] == 0, list(out)
-        cal = (C.c_double * 4)()
-        check(blaze_amd.aux().blz_calib_mad_rate(0, 50, cal))
-        med = statistics.median(ms)
-        mads = lane_mads(h, tree_c)
-        res[name] = {"hashes": n_rec, "kernel_ms": round(med, 4), "kernel_ms_min": round(min(ms), 4), "kernel_ms_max": round(max(ms), 4),
-                     "hashes_per_s": round(n_rec / (med * 1e-3)), "definition_kernel_wall_ms": round(def_ms, 2),
-                     "definition_kernel_nodes_checked": int(out[0]),
-                     "lane_multiply_adds": mads, "calib_mad_rate": cal[0], "calib_clock_mhz": cal[2],
-                     "issue_fraction": round(mads / (med * 1e-3) / cal[0], 4), "device_bytes": cl.info()["device_bytes"]}
+        res[name] = {"hashes": n_rec}
+        for form, plan in (("dense", False), ("plan", True)):
+            cl.set_round_plan(plan)
+            if plan:
+                state = cl.prepare_round_plan()
+                assert state == {"optimised_partial_rounds": True, "round_plan_check": 1}, state
+            assert cl.info()["optimised_partial_rounds"] is plan
+            ms = []
+            for it in range(rounds + 2):
+                cl.set_data(d_in)
+                cl.wait_result()
+                if it >= 2:
+                    ms.append(cl.last_kernel_ms())
+                if it < rounds + 1:
+                    cl.reset()
+            cl.tree_device(d_rec)
+            out = (C.c_uint64 * 2)()
+            t0 = time.perf_counter()
+            check(blaze_amd.aux().blz_test_poseidon_tree_check(0, 1, buf_ptr(wb)[0], len(wb), int(mode), h, d_in.ptr, d_rec.ptr, out))
+            def_ms = (time.perf_counter() - t0) * 1e3
+            assert out[0] == n_rec and out[1] == 0, list(out)
+            cal = (C.c_double * 4)()
+            check(blaze_amd.aux().blz_calib_mad_rate(0, 50, cal))
+            med = statistics.median(ms)
+            mads = lane_mads(h, tree_c, plan)
+            res[name][form] = {"kernel_ms": round(med, 4), "kernel_ms_min": round(min(ms), 4), "kernel_ms_max": round(max(ms), 4),
+                               "hashes_per_s": round(n_rec / (med * 1e-3)), "definition_kernel_wall_ms": round(def_ms, 2),
+                               "definition_kernel_nodes_checked": int(out[0]),
+                               "lane_multiply_adds": mads, "calib_mad_rate": cal[0], "calib_clock_mhz": cal[2],
+                               "issue_fraction": round(mads / (med * 1e-3) / cal[0], 4), "device_bytes": cl.info()["device_bytes"]}
+        dense, plan = res[name]["dense"], res[name]["plan"]
+        res[name]["plan_over_dense"] = round(plan["kernel_ms"] / dense["kernel_ms"], 4)
+        res[name]["plan_below_dense_min"] = plan["kernel_ms"] < dense["kernel_ms_min"]
         cl.close()
         d_in.free()
         d_rec.free()
@@ -115,7 +139,7 @@ def one_tree(h: int) -> None:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--one-tree", type=int, default=0, metavar="H")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "poseidon_tree.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "poseidon_tree_sparse.json"))
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--timeout", type=int, default=300)
     ap.add_argument("--child", action="store_true")
