@@ -34,6 +34,11 @@ class DriverClientError(Exception):
 _lib = None
 _aux = None
 
+class BlzVecArg(C.Structure):
+    """struct blz_vec_arg (include/blaze_hip.h): one operand of blz_ntt_vec_op."""
+    _fields_ = [("d_ptr", C.c_void_p), ("buf", C.c_uint32), ("reserved", C.c_uint32), ("count", C.c_uint64)]
+
+
 # every exported symbol of include/blaze_hip.h: name -> (restype, argtypes)
 _u8p = C.c_void_p
 _SIGS = {
@@ -105,6 +110,7 @@ _SIGS = {
     "blz_ntt_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     "blz_ntt_reset": (C.c_int, [C.c_void_p]),
     "blz_ntt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "blz_ntt_vec_op": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg)]),
     "blz_ntt_banks_preprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
     "blz_ntt_banks_postprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
     "blz_poseidon_new": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

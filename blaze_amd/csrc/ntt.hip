@@ -88,7 +88,8 @@ struct blz_ntt {
     bool cs_wire = false;       // the 512-point kernel is the wire pass of a forward handle: CS.tG exists
     uint32_t* cs_stage = nullptr;   // device: s | the caller's shift | the check's flag
     bool in_flight = false;
-    int in_flight_buf = -1;   // buffer under transform while in_flight
+    int in_flight_buf = -1;   // buffer under transform (or written by an element-wise op) while in_flight
+    uint32_t in_flight_reads = 0;   // blz_ntt_vec_op in flight: bit b = transform buffer b is an operand it reads
     float last_ms = 0.f;
     bool wedged = false;      // a wait ran into BLAZE_WAIT_TIMEOUT_MS: only reset / free are accepted (common.hpp)
 };
@@ -298,6 +299,8 @@ static int ntt_set_data_common(blz_ntt* h, size_t buf_host, const void* data, si
     BLZ_NTT_LIVE(h);
     if (h->in_flight && h->in_flight_buf == (int)buf_host)
         return fail(BLZ_ERR_INVALID_PARAM, "buffer %zu is being transformed; call wait_result first", buf_host);
+    if (h->in_flight && ((h->in_flight_reads >> buf_host) & 1u))
+        return fail(BLZ_ERR_INVALID_PARAM, "buffer %zu is read by the element-wise op in flight; call wait_result first", buf_host);
     BLZ_TRY(use_device(h->device));
     // a dedicated copy stream: the compute stream may be busy on the other buffer (double-buffer
     // contract, tests/integration_ntt.rs:102-136).  Synchronised before returning: set_data is
@@ -321,6 +324,7 @@ int blz_ntt_start_process(blz_ntt* h, size_t buf_kernel) {
     BLZ_NTT_LIVE(h);
     if (h->in_flight) return fail(BLZ_ERR_INVALID_PARAM, "a transform is already running; call wait_result first");
     BLZ_TRY(use_device(h->device));
+    h->in_flight_reads = 0;
     void* b = h->buf[buf_kernel].p;
     void* s = h->scratch.p;
     BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
@@ -395,6 +399,8 @@ int blz_ntt_exchange(blz_ntt* h, size_t buf, const uint8_t* next_in, size_t in_l
     BLZ_NTT_LIVE(h);
     if (h->in_flight && h->in_flight_buf == (int)buf)
         return fail(BLZ_ERR_INVALID_PARAM, "buffer %zu is being transformed; call wait_result first", buf);
+    if (h->in_flight && ((h->in_flight_reads >> buf) & 1u))
+        return fail(BLZ_ERR_INVALID_PARAM, "buffer %zu is read by the element-wise op in flight; call wait_result first", buf);
     BLZ_TRY(use_device(h->device));
     char* dbuf = (char*)h->buf[buf].p;
     // Pieces of 64 MiB (1.2 ms of link; smaller ones pay more per-copy overhead than they hide: 16 MiB 93.3 ms per cycle, 64 MiB
@@ -625,7 +631,73 @@ int blz_ntt_reset(blz_ntt* h) {
     BLZ_TRY(sync_stream_bounded(h->copy_stream, "reset: NTT copy stream"));
     BLZ_TRY(sync_stream_bounded(h->copy_stream2, "reset: NTT copy stream"));
     h->in_flight = false;
+    h->in_flight_reads = 0;
     h->wedged = false;
+    return BLZ_OK;
+}
+
+// Element-wise ops on the transform buffers (include/blaze_hip.h).  Everything is checked before anything is enqueued; the op
+// then runs like a transform: compute stream, ev0 .. ev1, finished by blz_ntt_wait_result.  The batch inversion's tile totals
+// live in `scratch`, which only a transform of this handle uses - and none can be in flight.
+static int ntt_vec_operand(blz_ntt* h, const char* name, const blz_vec_arg* v, NttVecArg& out, uint32_t& reads) {
+    const uint64_t n = 1ull << h->logn;
+    if (v->reserved != 0) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: reserved must be 0", name);
+    if (!v->d_ptr) {
+        if (v->buf > 1) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: buf must be 0 or 1", name);
+        if (v->count != 0 && v->count != n)
+            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: a transform buffer holds %llu elements, count says %llu", name,
+                        (unsigned long long)n, (unsigned long long)v->count);
+        out = NttVecArg{h->buf[v->buf].as<uint32_t>(), n - 1};
+        reads |= 1u << v->buf;
+        return BLZ_OK;
+    }
+    if (v->count == 0 || (v->count & (v->count - 1)) != 0 || v->count > n)
+        return fail(BLZ_ERR_INVALID_PARAM, "operand %s: count %llu is not a power of two in [1, %llu]", name,
+                    (unsigned long long)v->count, (unsigned long long)n);
+    if (((uintptr_t)v->d_ptr & 15u) != 0) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not 16-byte aligned", name);
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, v->d_ptr) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not memory the runtime knows", name);
+    }
+    if (at.type != hipMemoryTypeDevice || at.device != h->device)
+        return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not device memory of device %d", name, h->device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)v->d_ptr) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not inside a device allocation", name);
+    }
+    if ((const char*)v->d_ptr + v->count * 32 > (const char*)base + size)
+        return fail(BLZ_ERR_INVALID_PARAM, "operand %s: %llu elements run past the end of the allocation d_ptr points into", name,
+                    (unsigned long long)v->count);
+    out = NttVecArg{(const uint32_t*)v->d_ptr, v->count - 1};
+    return BLZ_OK;
+}
+
+int blz_ntt_vec_op(blz_ntt* h, int op, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (op < 0 || op >= NTT_VEC_OPS) return fail(BLZ_ERR_INVALID_PARAM, "unknown element-wise op %d", op);
+    if (buf_dst > 1) return fail(BLZ_ERR_INVALID_PARAM, "buf_dst must be 0 or 1");
+    const bool takes_b = op != BLZ_VEC_INV, takes_c = op == BLZ_VEC_MULADD || op == BLZ_VEC_MULSUB;
+    if (!a || (b != nullptr) != takes_b || (c != nullptr) != takes_c)
+        return fail(BLZ_ERR_INVALID_PARAM, "element-wise op %d takes operands a%s%s, and the others must be NULL", op, takes_b ? ", b" : "",
+                    takes_c ? ", c" : "");
+    BLZ_NTT_LIVE(h);
+    if (h->in_flight) return fail(BLZ_ERR_INVALID_PARAM, "a transform or an element-wise op is already running; call wait_result first");
+    BLZ_TRY(use_device(h->device));
+    NttVecArg va{}, vb{}, vc{};
+    uint32_t reads = 0;
+    BLZ_TRY(ntt_vec_operand(h, "a", a, va, reads));
+    if (takes_b) BLZ_TRY(ntt_vec_operand(h, "b", b, vb, reads));
+    if (takes_c) BLZ_TRY(ntt_vec_operand(h, "c", c, vc, reads));
+    BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
+    BLZ_TRY(h->ops->vec_op(h->stream, op, h->buf[buf_dst].as<uint32_t>(), va, takes_b ? vb : va, takes_c ? vc : va, 1ull << h->logn,
+                           h->scratch.as<uint32_t>()));
+    BLZ_HIP(hipEventRecord(h->ev1, h->stream), BLZ_ERR_UNKNOWN);
+    h->in_flight = true;
+    h->in_flight_buf = (int)buf_dst;
+    h->in_flight_reads = reads & ~(1u << buf_dst);
     return BLZ_OK;
 }
 

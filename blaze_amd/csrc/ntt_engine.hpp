@@ -68,6 +68,15 @@ struct NttGeom {
                      // index bitrev(p)): folded into the wire pass's loads / the last pass's stores
 };
 
+// Element-wise ops on resident buffers (blz_ntt_vec_op; kernels: ntt_vec.hip.hpp).  An operand is `mask + 1` (a power of two)
+// 32-byte words at p; position e of the op reads word e & mask.
+struct NttVecArg {
+    const uint32_t* p;
+    uint64_t mask;
+};
+constexpr int NTT_VEC_OPS = 6;               // enum blz_vec_op: ADD SUB MUL MULADD MULSUB INV
+constexpr uint64_t NTT_VEC_INV_TILE = 1024;  // batch inversion: elements per block (256 lanes x 4); one 32-byte total per tile
+
 // per-field entry points.  Field ids follow enum blz_curve: the scalar field Fr of that curve.
 struct NttFieldOps {
     int two_adicity;
@@ -88,6 +97,9 @@ struct NttFieldOps {
     int (*coset_tables)(hipStream_t st, const NttTables& T, const NttTablesRR& TR, const NttGeom& g, const NttCoset& cs, const uint32_t* d_s);
     // ts2 and tB of the plain transform again
     int (*coset_unfold)(hipStream_t st, const NttTables& T, const NttTablesRR& TR, const NttGeom& g);
+    // dst[e] = op(a, b, c)[e], e < n (enum blz_vec_op; b / c ignored by the ops that do not take them).  dst may be an operand.
+    // totals: ceil(n / NTT_VEC_INV_TILE) x 32 bytes of device memory for the batch inversion's tile totals
+    int (*vec_op)(hipStream_t st, int op, uint32_t* dst, NttVecArg a, NttVecArg b, NttVecArg c, uint64_t n, uint32_t* totals);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

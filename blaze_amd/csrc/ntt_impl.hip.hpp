@@ -4,6 +4,7 @@
 #include "ntt_engine.hpp"
 #include "field.hip.hpp"
 #include "ntt_rr.hip.hpp"
+#include "ntt_vec.hip.hpp"
 
 namespace blz {
 
@@ -58,6 +59,7 @@ __global__ void k_ntt_table(uint32_t* out, int count, const uint32_t* __restrict
 }
 
 // out = (2^logn)^-1 in Montgomery form
+// (the loop below is ONE fp_mul and nothing else: tests/test_ntt_vec.py reads a field product's multiply-add count off it)
 template <class Fr>
 __global__ void k_ntt_ninv(uint32_t* out, int logn) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -510,6 +512,7 @@ NttFieldOps make_ntt_ops() {
     o.coset_check = &ntt_coset_check_t<Fr>;
     o.coset_tables = &ntt_coset_tables_t<Fr>;
     o.coset_unfold = &ntt_coset_unfold_t<Fr>;
+    o.vec_op = &ntt_vec_op_t<Fr>;
     return o;
 }
 

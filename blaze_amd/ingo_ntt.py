@@ -6,11 +6,12 @@ import enum
 from dataclasses import dataclass
 from typing import Optional
 
-from ._lib import DeviceBuffer, buf_ptr, check, lib
+from ._lib import BlzVecArg, DeviceBuffer, buf_ptr, check, lib
 from .driver_client import DriverClient, DriverPrimitive
 
 NTT_LOG_SIZE = 27  # ntt_data.rs:65: NTT_SIZE = 2^27
 NTT_WORD_SIZE = 32  # ntt_data.rs:66
+VEC_INV_TILE = 1024  # csrc/ntt_engine.hpp NTT_VEC_INV_TILE: elements per block of NTTClient.vec_op(NTTClient.INV, ...)
 
 
 class NTT(enum.Enum):  # ntt_api.rs:8-10
@@ -39,6 +40,7 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
     INVERSE = 2          # BLZ_NTT_INVERSE
     BITREV_INPUT = 4     # BLZ_NTT_BITREV_INPUT
     BITREV_OUTPUT = 8    # BLZ_NTT_BITREV_OUTPUT
+    ADD, SUB, MUL, MULADD, MULSUB, INV = range(6)   # enum blz_vec_op
 
     def __init__(self, _ptype: NTT, dclient: DriverClient, log_size: int = NTT_LOG_SIZE, inverse: bool = False,
                  field: str = "BLS381", flags: int = 0, root: Optional[int] = None):
@@ -54,11 +56,13 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         rb = None if root is None else int(root).to_bytes(32, "little")
         check(lib().blz_ntt_new_ex3(dclient.id, self._FIELDS[field], log_size, int(flags) | (self.INVERSE if inverse else 0), rb, C.byref(h)))
         self._h = h
+        self._vec_keep = None   # the operands of a vec_op in flight: their device memory must outlive it
 
     def close(self):
         if getattr(self, "_h", None):
             lib().blz_ntt_free(self._h)
             self._h = None
+            self._vec_keep = None
 
     def __del__(self):
         try:
@@ -86,6 +90,7 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
 
     def wait_result(self) -> None:  # ntt_api.rs:89-108
         check(lib().blz_ntt_wait_result(self._h))
+        self._vec_keep = None
 
     def result(self, buf_num: Optional[int] = None) -> Optional[bytes]:  # ntt_api.rs:110-124
         if buf_num is None:
@@ -125,6 +130,35 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
 
     def reset(self) -> None:
         check(lib().blz_ntt_reset(self._h))
+        self._vec_keep = None
+
+    @staticmethod
+    def _vec_arg(x):
+        if x is None:
+            return None
+        if isinstance(x, DeviceBuffer):
+            return BlzVecArg(x.ptr, 0, 0, x.nbytes // NTT_WORD_SIZE)
+        return BlzVecArg(None, int(x), 0, 0)
+
+    def vec_op(self, op: int, dst: int, a, b=None, c=None) -> None:
+        """Element-wise op over the client's n positions (include/blaze_hip.h blz_ntt_vec_op): transform buffer `dst` =
+        a + b (ADD), a - b (SUB), a * b (MUL), a * b + c (MULADD), a * b - c (MULSUB), 1 / a with 0 -> 0 (INV).  An int operand
+        names a transform buffer (0 | 1, `dst` included: in place); a DeviceBuffer is device words, nbytes / 32 of them - a
+        power of two up to n - read periodically along the buffer position (one word: a scalar).  Enqueued like a transform:
+        wait_result() finishes it, last_kernel_ms() then reports it; the DeviceBuffers are kept alive until then and must not be
+        written."""
+        args = [self._vec_arg(x) for x in (a, b, c)]
+        check(lib().blz_ntt_vec_op(self._h, int(op), dst, *[None if v is None else C.byref(v) for v in args]))
+        self._vec_keep = (a, b, c)
+
+    def scalar(self, value: int) -> DeviceBuffer:
+        """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""
+        v = int(value)
+        if v < 0 or v >> 256:
+            raise ValueError("a vec_op operand word is a 256-bit unsigned integer")
+        d = DeviceBuffer(self.driver_client.id, NTT_WORD_SIZE)
+        d.upload(v.to_bytes(NTT_WORD_SIZE, "little"))
+        return d
 
     def set_coset(self, shift: Optional[int]) -> None:
         """Transforms started from now on run on the coset shift * <w> (include/blaze_hip.h blz_ntt_set_coset): a forward client

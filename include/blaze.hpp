@@ -248,6 +248,14 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
         check(blz_ntt_get_coset(h_, v.data()));
         return v;
     }
+    // element-wise op on the transform buffers (blaze_hip.h blz_ntt_vec_op): buffer dst = op(a, b, c), position by position;
+    // enqueued like a transform - wait_result() finishes it.  Operands: buffer(i) names transform buffer i, words(p, count)
+    // `count` 32-byte device words read periodically (count = 1: a scalar); nullptr for the operands the op does not take
+    static blz_vec_arg buffer(uint32_t i) { return blz_vec_arg{nullptr, i, 0u, 0u}; }
+    static blz_vec_arg words(const void* d_ptr, uint64_t count) { return blz_vec_arg{d_ptr, 0u, 0u, count}; }
+    void vec_op(blz_vec_op op, size_t dst, const blz_vec_arg* a, const blz_vec_arg* b = nullptr, const blz_vec_arg* c = nullptr) {
+        check(blz_ntt_vec_op(h_, (int)op, dst, a, b, c));
+    }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

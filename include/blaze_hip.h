@@ -399,6 +399,41 @@ int blz_ntt_stream(blz_ntt* h, void** hip_stream, int* device_id);
 int blz_ntt_reset(blz_ntt* h);
 /* kernel time of the last transform in ms (what benches/ntt_bench.rs:34-39 times, minus reset()) */
 int blz_ntt_last_kernel_ms(blz_ntt* h, float* out);
+/* Element-wise ops on resident buffers: the "combine" step between two transforms (a quotient polynomial is
+ * evaluate on g<w>, combine point by point, interpolate back) without a trip through the host.  Over the handle's field,
+ * n = 2^log_size elements, position by position: dst[p] = op(a[p], b[p], c[p]).
+ *   Values: every input word is any 256-bit value and counts as its residue (the transforms' rule); every output word is
+ *   canonical (< r), little-endian.  BLZ_VEC_INV maps 0 (and r, 2r ...) to 0.
+ *   Operands: d_ptr == NULL names the handle's transform buffer `buf` (count 0 or n); otherwise d_ptr is device memory of the
+ *   handle's device, 16-byte aligned, holding `count` 32-byte elements, count a power of two, 1 <= count <= n, and position
+ *   p of the op reads element p & (count - 1): count = 1 is a scalar, count = 4 carries the four values of 1 / Z_H on a 4x
+ *   domain, count = n is a vector.  The period runs along the buffer POSITION p: the handle's BLZ_NTT_BITREV_* flags and
+ *   its coset shift play no part here, the op sees positions, not logical indices.
+ *   dst is the transform buffer buf_dst and may be a buffer an operand names (in place); a and b may be the same (a square).
+ *   Operands an op does not take must be NULL, operands it takes must not be.
+ *   Protocol: that of a transform.  The op is enqueued on the handle's compute stream and the call returns;
+ *   blz_ntt_wait_result finishes it (bounded, as for a transform) and blz_ntt_last_kernel_ms then reports its device time.
+ *   Until then buf_dst may not be read, written or exchanged, the transform buffers the op READS may be read
+ *   (blz_ntt_result) but not written or exchanged, and blz_ntt_start_process, blz_ntt_set_coset and another
+ *   blz_ntt_vec_op are refused.  Memory behind a d_ptr must stay valid and unwritten until blz_ntt_wait_result returns: the
+ *   library does not copy it.  blz_ntt_reset drops an op in flight like a transform.
+ *   BLZ_ERR_INVALID_PARAM, before anything is enqueued: null handle, unknown op, buf_dst > 1, buf > 1, reserved != 0, a
+ *   count that is zero, not a power of two or above n (d_ptr == NULL: neither 0 nor n), a missing or surplus operand, a d_ptr
+ *   the runtime does not know as device memory of the handle's device, or one that is not 16-byte aligned. */
+enum blz_vec_op { BLZ_VEC_ADD = 0,     /* dst = a + b     */
+                  BLZ_VEC_SUB = 1,     /* dst = a - b     */
+                  BLZ_VEC_MUL = 2,     /* dst = a * b     */
+                  BLZ_VEC_MULADD = 3,  /* dst = a * b + c */
+                  BLZ_VEC_MULSUB = 4,  /* dst = a * b - c */
+                  BLZ_VEC_INV = 5 };   /* dst = a^-1, and 0 -> 0 (batch inversion) */
+typedef struct blz_vec_arg {
+    const void* d_ptr;   /* NULL: the handle's transform buffer `buf`; else device memory on the handle's device */
+    uint32_t buf;        /* 0 | 1, read only when d_ptr == NULL */
+    uint32_t reserved;   /* must be 0 */
+    uint64_t count;      /* d_ptr != NULL: number of 32-byte elements, a power of two, 1 <= count <= n;
+                            position p of the op reads element p & (count - 1).  d_ptr == NULL: 0 or n */
+} blz_vec_arg;
+int blz_ntt_vec_op(blz_ntt* h, int op, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c);
 /* NTTBanks::preprocess / postprocess (ntt_data.rs:80-156) as device permutations, for byte
  * compatibility with bank files of the FPGA flow; n = 2^log_size elements (log_size >= 10), 16 banks
  * contiguous (n/16 elements each); 2^27 uses the reference's 512 groups x 256 block pairs, smaller sizes

@@ -17,6 +17,16 @@ pub struct BlzNtt {
 pub struct BlzPoseidon {
     _private: [u8; 0],
 }
+/// `struct blz_vec_arg`: one operand of `blz_ntt_vec_op` - transform buffer `buf` of the handle (`d_ptr` null) or `count`
+/// 32-byte device words at `d_ptr`, read periodically along the buffer position.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct BlzVecArg {
+    pub d_ptr: *const c_void,
+    pub buf: u32,
+    pub reserved: u32,
+    pub count: u64,
+}
 
 pub const BLZ_COMM_ID_BYTES: usize = 128;
 
@@ -100,6 +110,7 @@ extern "C" {
     pub fn blz_ntt_result(h: *mut BlzNtt, buf: usize, out: *mut u8, out_cap: usize) -> c_int;
     pub fn blz_ntt_reset(h: *mut BlzNtt) -> c_int;
     pub fn blz_ntt_last_kernel_ms(h: *mut BlzNtt, out: *mut f32) -> c_int;
+    pub fn blz_ntt_vec_op(h: *mut BlzNtt, op: c_int, buf_dst: usize, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg) -> c_int;
 
     // ---- Poseidon tree: PoseidonClient (ingo_hash::poseidon_api)
     pub fn blz_poseidon_new(device_id: c_int, field: c_int, out: *mut *mut BlzPoseidon) -> c_int;

@@ -129,7 +129,49 @@ impl NTTClient {
         Ok(v)
     }
 
+    /// Element-wise op over the client's n positions (blaze_hip.h blz_ntt_vec_op): transform buffer `dst` = a + b, a - b, a * b,
+    /// a * b + c, a * b - c or 1 / a (0 -> 0), by `op` (`VecOp`).  Enqueued like a transform: `wait_result` finishes it.
+    ///
+    /// # Safety
+    /// The library checks that a `VecOperand::Words` pointer is device memory of the client's device holding `count` words, and
+    /// does not copy it: the kernels read it until `wait_result` (or `reset_engine`) returns.  The caller keeps that memory
+    /// allocated and unwritten until then; nothing in the types enforces it.
+    pub unsafe fn vec_op(&self, op: VecOp, dst: usize, a: VecOperand, b: Option<VecOperand>, c: Option<VecOperand>) -> Result<()> {
+        let (ra, rb, rc) = (a.raw(), b.map(|v| v.raw()), c.map(|v| v.raw()));
+        let p = |v: &Option<BlzVecArg>| v.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg);
+        check(blz_ntt_vec_op(self.h, op as std::os::raw::c_int, dst, &ra, p(&rb), p(&rc)))
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
+    }
+}
+
+/// `enum blz_vec_op`
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum VecOp {
+    Add = 0,
+    Sub = 1,
+    Mul = 2,
+    MulAdd = 3,
+    MulSub = 4,
+    Inv = 5,
+}
+
+/// An operand of `NTTClient::vec_op`: a transform buffer of the client (0 | 1), or `count` 32-byte device words (a power of two
+/// up to n; 1 = a scalar) read periodically along the buffer position.
+#[derive(Clone, Copy)]
+pub enum VecOperand {
+    Buffer(u32),
+    Words { d_ptr: *const std::os::raw::c_void, count: u64 },
+}
+
+impl VecOperand {
+    fn raw(&self) -> BlzVecArg {
+        match *self {
+            VecOperand::Buffer(buf) => BlzVecArg { d_ptr: std::ptr::null(), buf, reserved: 0, count: 0 },
+            VecOperand::Words { d_ptr, count } => BlzVecArg { d_ptr, buf: 0, reserved: 0, count },
+        }
     }
 }
