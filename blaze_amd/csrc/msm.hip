@@ -196,6 +196,141 @@ MsmPlan make_table_plan(uint32_t npts, int c, int need_bits) {
     return P;
 }
 
+// ------------------------------------------------------------------------------------------------
+// tail plan (msm_engine.hpp TailPlan): host arithmetic over the window plan, no device
+// ------------------------------------------------------------------------------------------------
+int plan_tail(const MsmPlan& P, TailTraits tr, bool piecewise, TailPlan& T) {
+    T = TailPlan();
+    // ---- unit folds.  A bucket holds at most one entry per point (window-table tasks: one per point and window)
+    // (64-bit stride: with BLAZE_MSM_PLAN L < 8 and close to 2^31 points, maxunits exceeds 2^28 and a u32 stride would wrap to 0)
+    const uint64_t maxunits = ((uint64_t)P.npts * (P.table ? P.W : 1) + P.L - 1) / P.L;
+    for (uint64_t stride = 1; stride < maxunits; stride *= 16) ++T.unit_passes;
+    // where the plan itself says that buckets hold several units each (mean run > L / 2), the lane-per-bucket fold takes
+    // every bucket of up to 64 units and the tree only the hot ones beyond
+    // (... and for every task of up to 2^22 points: one window of such a task can be twice as dense as the mean - the top real
+    // window of 255-bit scalars below r covers 0x39f6 of its 2^15 buckets at c = 16 - and the quad tree, built for a handful of
+    // hot buckets, spent 0.48 ms of a 4.8 ms 2^20 task on its 14 K two-unit buckets; one pass over the unit offsets is nothing here)
+    T.thr = ((uint64_t)P.npts * P.W / (P.G ? P.G : 1) > P.L / 2 || P.npts <= (1u << 22)) ? 64u : 0u;
+    // The windows the plan knows to be hot (the top ones, where the scalars' bits run out: a few buckets with long runs):
+    // a suffix [hot_start, G) of the bucket space goes to k_fold_hot - eight waves per bucket, sixteen on the row law - and the
+    // other folds leave it alone.  Only for a small suffix of a larger space: where EVERY window is like that (the precompute
+    // shapes) the lane-per-bucket fold is the throughput-bound answer.
+    T.hot_start = (uint32_t)P.G;
+    if (tr.rr && !P.table && !piecewise && P.ebits > 0) {
+        int lowest = -1, off = 0;
+        bool any = false;
+        int offs[MSM_MAX_W];
+        for (int w = 0; w < P.W; ++w) { offs[w] = off; off += P.width[w]; }
+        for (int w = P.W - 1; w >= 0; --w) {
+            const int cw = P.width[w];
+            int t = P.ebits - offs[w];
+            if (t > cw) t = cw;
+            const double slots = (double)(1ull << (cw - 1));
+            double active = t >= cw ? slots : t > 0 ? (double)(1ull << t) + 1.0 : t == 0 ? 1.0 : 0.0;
+            if (active > slots) active = slots;
+            const double entries = t >= 0 ? (double)P.npts : 0.0;
+            const bool hot = active > 0 && entries / active >= 12.0 * (double)P.L;   // a dozen units or more per bucket
+            if (!hot && entries > 0) break;       // a normal window: the suffix ends above it
+            lowest = w;
+            any = any || hot;
+        }
+        if (any && lowest > 0 && P.G - P.boff[lowest] <= 16384) T.hot_start = P.boff[lowest];
+    }
+    if (T.hot_start < P.G) T.hot = tr.row ? TailPlan::HOT_ROW : TailPlan::HOT_WAVES8;
+
+    // ---- bucket reduce
+    // level 0 is throughput-bound (2 adds per bucket): long segments; the upper levels have few
+    // lanes and are latency-bound on their sequential chain: short segments, more levels
+    // (a small bucket space cannot fill the chip with long segments: the level wants >= 2^18 lanes - two full rounds of
+    // two waves per SIMD - before it wants long segments; the extra segment sums are absorbed by the upper levels, which
+    // run on the tail stream).  Same-box sweeps, profiles/r03_seg_sweep.txt: 17.8 M bucket slots (the 2^26 plan) 64 best; 12.6 M: 32 (61.9 against 62.9 ms per MSM);
+    // 5 - 7 M: 16 (17.2 against 17.8); 2.1 M (2^22): 8 (10.1 against 11.1).  Powers of two only: the upper levels weigh
+    // segment t by shifts.
+    uint32_t seg0 = 64;
+    while (seg0 > 8 && P.G / seg0 < 262144) seg0 >>= 1;
+    seg0 = (uint32_t)exp_knob("BLAZE_MSM_SEG", (int)seg0);
+    const uint32_t segu = (uint32_t)exp_knob("BLAZE_MSM_SEG_UPPER", 8);
+    const uint32_t quad_max = (uint32_t)exp_knob("BLAZE_REDUCE_QUAD_MAX", 131072), row_max = (uint32_t)exp_knob("BLAZE_REDUCE_ROW_MAX", 8192);
+    bool row_levels = false;
+    int shift = 0;
+    for (uint32_t M = P.Bw;;) {
+        if (T.levels == 16) return fail(BLZ_ERR_UNKNOWN, "bucket reduce of %u buckets per window needs more than 16 levels (segments of %u / %u)", P.Bw, seg0, segu);
+        TailPlan::Level& l = T.level[T.levels];
+        l.M = M;
+        l.SEG = T.levels == 0 ? seg0 : segu;
+        l.T = l.SEG ? (M + l.SEG - 1) / l.SEG : M;
+        l.shift = shift;
+        // few segments: one per wave on the row law, from here to the end (k_reduce_level_row); else level 0 a lane per segment
+        // (a quad while the level is small), the upper levels a quad
+        if (tr.row && l.T * (uint32_t)P.Wv <= row_max) row_levels = true;
+        l.kind = row_levels ? TailPlan::Level::ROW : !tr.rr ? TailPlan::Level::W32
+                 : T.levels > 0 || l.T * (uint32_t)P.Wv <= quad_max ? TailPlan::Level::QUAD : TailPlan::Level::RR;
+        for (uint32_t t = 1; t < l.SEG; t <<= 1) ++shift;   // (the next level weighs this one's segments by shifts)
+        ++T.levels;
+        M = l.T;
+        if (M == 1) break;
+    }
+
+    // ---- bucket folds.  Where the curve has the row law, a task of up to 2^17 bucket slots and units folds its buckets on it: one
+    // wave per bucket; the sums leave in the accumulator form unless everything behind them runs on the row law too
+    // (a latency tool: chip-wide the row law adds ~5 x slower than one lane per point - 2^18 elements, 82 K buckets of four units:
+    // 0.41 ms against the lane-per-bucket fold's 0.19 - so only while the units to fold are few)
+    if (T.thr == 0 || T.hot_start == 0) T.fold = TailPlan::FOLD_NONE;
+    else if (tr.row && !piecewise && P.G <= (1u << 17) && (uint64_t)P.npts * P.W / P.L <= (1u << 17))
+        T.fold = T.level[0].kind == TailPlan::Level::ROW ? TailPlan::FOLD_ROW_WEAK : TailPlan::FOLD_ROW_STRICT;
+    else   // small bucket spaces: one wave per bucket (latency), else one lane (throughput)
+        T.fold = tr.rr && T.hot_start <= 32768 ? TailPlan::FOLD_WAVE : TailPlan::FOLD_LANE;
+
+    // ---- finish
+    T.finish_row = tr.row;
+    FinishPlan& fp = T.fp;
+    fp.W = P.W;
+    fp.logV = 0;
+    while ((1u << fp.logV) < P.Bw) ++fp.logV;
+    if (P.table) {
+        // one bucket set for all the scalar's windows (their weights are in the table's points): a single window at bit 0
+        fp.W = 1;
+        fp.v0[0] = 0;
+        fp.m[0] = (uint8_t)(P.G >> fp.logV);
+        fp.off[0] = 0;
+    } else {
+        int off = P.base_bit;
+        for (int w = 0; w < P.W; ++w) {
+            const uint32_t v0 = P.boff[w] >> fp.logV, m = (P.boff[w + 1] - P.boff[w]) >> fp.logV;
+            if (v0 > 0xffffu || m > 0xffu || off > 0xffff)
+                return fail(BLZ_ERR_UNKNOWN, "window plan outside k_finish's table range (window %d: v0=%u m=%u off=%d)", w, v0, m, off);
+            fp.v0[w] = (uint16_t)v0;
+            fp.m[w] = (uint8_t)m;
+            fp.off[w] = (uint16_t)off;
+            off += P.width[w];
+        }
+    }
+
+    // ---- what the launchers could only get wrong silently
+    const char* bad = nullptr;
+    if ((T.hot == TailPlan::HOT_WAVES8 || T.fold == TailPlan::FOLD_WAVE) && !tr.rr) bad = "a reduced-radix fold";
+    if ((T.hot == TailPlan::HOT_ROW || T.fold == TailPlan::FOLD_ROW_STRICT || T.fold == TailPlan::FOLD_ROW_WEAK || T.finish_row) && !tr.row) bad = "a row-law kernel";
+    if (!T.finish_row && tr.row) bad = "the quad walk";   // (k_finish exists for the fields without the row law only)
+    if (T.fold == TailPlan::FOLD_ROW_WEAK && T.level[0].kind != TailPlan::Level::ROW) bad = "a weak row fold without a row level 0 behind it";
+    for (int l = 0; l < T.levels && !bad; ++l) {
+        const TailPlan::Level::Kind k = T.level[l].kind;
+        if (k == TailPlan::Level::ROW ? !tr.row : k == TailPlan::Level::W32 ? tr.rr : !tr.rr) bad = "a reduce level on a law the field lacks";
+        else if (k == TailPlan::Level::RR && l > 0) bad = "the lane-per-segment reduced-radix level above level 0";
+        else if (l > 0 && T.level[l - 1].kind == TailPlan::Level::ROW && k != TailPlan::Level::ROW) bad = "a row level in front of another law's";
+    }
+    if (bad) return fail(BLZ_ERR_UNKNOWN, "tail plan names %s (%s)", bad, describe(T).c_str());
+    return BLZ_OK;
+}
+
+std::string describe(const TailPlan& T) {
+    static const char* const hot[] = {"", " hot", " hot_row"};
+    static const char* const fold[] = {"none", "lane", "wave", "row_strict", "row_weak"};
+    static const char* const kind[] = {"w32", "rr", "quad", "row"};
+    std::string s = "units" + std::to_string(T.unit_passes) + hot[T.hot] + " fold_" + fold[T.fold] + " |";
+    for (int l = 0; l < T.levels; ++l) s += std::string(l ? " L" : " L0") + kind[T.level[l].kind];
+    return s + (T.finish_row ? " finish_row" : " finish");
+}
+
 // zero-fill (hipMemsetAsync's fill kernel took 0.7 ms for the 71 MB bucket-count array: ~100 GB/s)
 __global__ __launch_bounds__(256) void k_zero(uint4* __restrict__ p, size_t n16) {
     __builtin_amdgcn_s_setprio(3);   // sort-stage kernel: may run underneath another task's accumulation (msm_sort3.hip)
@@ -469,7 +604,7 @@ __global__ __launch_bounds__(256) void k_unit_order(const uint32_t* __restrict__
 // host side
 // ------------------------------------------------------------------------------------------------
 
-static const MsmCurveOps* ops_for(int curve, int repr = 0) {
+const MsmCurveOps* msm_ops_for(int curve, int repr) {
     switch (curve) {
         case BLZ_BLS377: return &msm_ops_bls377();
         case BLZ_BLS381: return &msm_ops_bls381();
@@ -479,12 +614,12 @@ static const MsmCurveOps* ops_for(int curve, int repr = 0) {
 }
 
 int msm_points_from_mont(int format_id, const void* d_mont, void* d_raw, uint64_t npts, hipStream_t st) {
-    const MsmCurveOps* ops = (format_id >> 16) ? nullptr : ops_for(format_id & 0xff, (format_id >> 8) & 0xff);   // (an even-base copy is not the whole table)
+    const MsmCurveOps* ops = (format_id >> 16) ? nullptr : msm_ops_for(format_id & 0xff, (format_id >> 8) & 0xff);   // (an even-base copy is not the whole table)
     if (!ops) return fail(BLZ_ERR_UNKNOWN, "no conversion back from Montgomery format 0x%x", format_id);
     return ops->points_from_mont(d_mont, d_raw, npts, st);
 }
 int msm_points_all_canonical(int format_id, const void* d_raw, uint64_t npts, uint32_t* flag, hipStream_t st) {
-    const MsmCurveOps* ops = ops_for(format_id & 0xff, (format_id >> 8) & 0xff);
+    const MsmCurveOps* ops = msm_ops_for(format_id & 0xff, (format_id >> 8) & 0xff);
     if (!ops) return fail(BLZ_ERR_UNKNOWN, "unknown Montgomery format 0x%x", format_id);
     return ops->points_all_canonical(d_raw, npts, flag, st);
 }
@@ -518,7 +653,7 @@ int MsmEngine::init(int device_id, int curve_id, int precompute_factor) {
         // (experiment builds: BLAZE_BN254_REPR = 0 | 1 overrides the choice by precompute factor)
         repr = exp_knob("BLAZE_BN254_REPR", precompute_factor > 1 ? 1 : 0) ? 1 : 0;
     }
-    if (!ops_for(curve, repr)) return fail(BLZ_ERR_INVALID_PARAM, "unknown curve %d", curve);
+    if (!msm_ops_for(curve, repr)) return fail(BLZ_ERR_INVALID_PARAM, "unknown curve %d", curve);
     BLZ_TRY(use_device(device));
     // The runtime multiplexes a process's streams over a few hardware queues PER PRIORITY LEVEL, and which queue a new stream
     // lands on depends on every stream the process ever created or destroyed: a handle opened after another one was closed had
@@ -620,24 +755,24 @@ int MsmEngine::sync_all() {
 
 int MsmEngine::points_to_mont(const void* d_raw, void* d_mont, uint32_t npts) {
     BLZ_TRY(use_device(device));
-    return ops_for(curve, repr)->points_to_mont(*this, d_raw, d_mont, npts);
+    return msm_ops_for(curve, repr)->points_to_mont(*this, d_raw, d_mont, npts);
 }
 
 int MsmEngine::points_to_mont_even(const void* d_raw, void* d_mont, uint32_t nq) {
     BLZ_TRY(use_device(device));
-    return ops_for(curve, repr)->points_to_mont_even(*this, d_raw, d_mont, nq);
+    return msm_ops_for(curve, repr)->points_to_mont_even(*this, d_raw, d_mont, nq);
 }
 int MsmEngine::check_precompute(const void* d_raw, uint64_t nelem, uint32_t* flag, hipStream_t st) {
     BLZ_TRY(use_device(device));
-    return ops_for(curve, 0)->check_precompute(*this, d_raw, nelem, flag, st);   // (reads wire-format points: always on the faster arithmetic)
+    return msm_ops_for(curve, 0)->check_precompute(*this, d_raw, nelem, flag, st);   // (reads wire-format points: always on the faster arithmetic)
 }
 
 int MsmEngine::build_table(const void* d_raw, void* d_table, uint32_t npts, int c, int W, int base_shift, void* scratch, uint32_t* flag,
                            hipStream_t st) {
     BLZ_TRY(use_device(device));
-    return ops_for(curve, repr)->build_table(*this, d_raw, d_table, npts, c, W, base_shift, scratch, flag, st);
+    return msm_ops_for(curve, repr)->build_table(*this, d_raw, d_table, npts, c, W, base_shift, scratch, flag, st);
 }
-size_t MsmEngine::table_scratch_bytes(int W) const { return ops_for(curve, repr)->table_scratch_bytes(W); }
+size_t MsmEngine::table_scratch_bytes(int W) const { return msm_ops_for(curve, repr)->table_scratch_bytes(W); }
 
 // do the hidden sort's waves (sv VGPRs) fit on a SIMD beside the accumulation's (av VGPRs each, as many as fit)?  Measured: the
 // sort runs beside 2 x 200 + 72 = 472 registers and waits for the accumulation to END behind 2 x 208 + 72 = 488.
@@ -656,7 +791,7 @@ MsmPlan MsmEngine::plan_for(uint32_t npts, int sbits) const {
     return make_plan(npts, sbits, ebits, plan_override("c", 0));
 }
 
-MsmPlan MsmEngine::plan_for_range(uint32_t npts, int bit_lo, int bit_hi) const {
+static MsmPlan range_plan(int curve, uint32_t npts, int bit_lo, int bit_hi) {
     const int vbits = bit_hi - bit_lo;
     int ebits = kScalarFieldBits[curve] - bit_lo;   // real bits of canonical scalars inside the range
     if (ebits > vbits) ebits = vbits;
@@ -664,6 +799,40 @@ MsmPlan MsmEngine::plan_for_range(uint32_t npts, int bit_lo, int bit_hi) const {
     MsmPlan P = make_plan(npts, vbits, ebits, plan_override("c", 0));
     P.base_bit = bit_lo;
     return P;
+}
+MsmPlan MsmEngine::plan_for_range(uint32_t npts, int bit_lo, int bit_hi) const { return range_plan(curve, npts, bit_lo, bit_hi); }
+
+int msm_task_plan(int curve, uint32_t npts, int sbits, int table_c, int bit_lo, int bit_hi, MsmPlan& P, bool* ranged_out) {
+    if (curve < 0 || curve > 2) return fail(BLZ_ERR_INVALID_PARAM, "unknown curve %d", curve);
+    const int ebits = sbits == 256 ? kScalarFieldBits[curve] : sbits;
+    const bool ranged = bit_hi > bit_lo && !(bit_lo == 0 && bit_hi >= sbits);
+    if (ranged && (sbits != 256 || (bit_lo & 31) || (bit_hi & 31) || bit_hi > 256))
+        return fail(BLZ_ERR_INVALID_PARAM, "scalar range [%d, %d): 32-bit aligned ranges of 256-bit scalars", bit_lo, bit_hi);
+    // (a window table of a ranged handle holds 2^(lo + c j) P: the plan covers hi - lo bits + the carry, no closing doublings)
+    P = table_c > 0 ? make_table_plan(npts, table_c, ranged ? bit_hi - bit_lo + 1 : 257)
+        : ranged    ? range_plan(curve, npts, bit_lo, bit_hi)
+                    : make_plan(npts, sbits, ebits, plan_override("c", 0));
+    if (P.c == 0) return fail(BLZ_ERR_INVALID_PARAM, "no window plan for npts=%u sbits=%d%s", npts, sbits, table_c > 0 ? " (window table)" : "");
+    if (P.table && !msm_sort3_ok(P, sbits)) return fail(BLZ_ERR_INVALID_PARAM, "window-table task outside the sort's range (c=%d)", P.c);
+    P.L = (uint32_t)plan_override("L", (int)P.L);
+    if (P.L < 1) P.L = 1;
+    if (P.L > (uint32_t)MAX_L) P.L = MAX_L;
+    if (ranged_out) *ranged_out = ranged;
+    return BLZ_OK;
+}
+
+int msm_task_pieces(const MsmPlan& P, int want, bool phased, uint32_t* per_out) {
+    if (want < 1 || P.table) want = 1;
+    if (want > MSM_MAX_SLICES) want = MSM_MAX_SLICES;
+    // pieces of whole 16-point groups (keeps every piece's scalars 16-byte aligned; pf = 8: whole elements)
+    // A task whose pieces arrive over the link (phased) ends with HALF a piece: behind the last byte sit that piece's
+    // accumulation, the bucket reduce and the tail, and the accumulation is the one part of it that shrinks with the piece
+    // (config 2: 13.5 -> 13.0 ms, the lone 2^26 HBM flow 138.6 -> 133); the pieces before it are 1 / (2 k - 1) larger.
+    const uint64_t halves = (phased && want >= 4) ? 2ull * want - 1 : 2ull * want;
+    const uint32_t per = (uint32_t)(((2ull * P.npts + halves - 1) / halves + 15) & ~(uint64_t)15);
+    if (want > 1) want = (int)(((uint64_t)P.npts + per - 1) / per);
+    *per_out = want > 1 ? per : P.npts;
+    return want;
 }
 
 // A task is enqueued in four steps - begin(), then per piece sort_slice() and accumulate_slice(), then end() - so that a
@@ -678,7 +847,7 @@ MsmPlan MsmEngine::plan_for_range(uint32_t npts, int bit_lo, int bit_hi) const {
 // unit folds and k_merge_buckets, and the reduce reads bucket_sums through the identity map.
 int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int bit_lo, int bit_hi, int nslices, bool phased) {
     BLZ_TRY(use_device(device));
-    const MsmCurveOps* ops = ops_for(curve, repr);
+    const MsmCurveOps* ops = msm_ops_for(curve, repr);
     hipStream_t st = stream;
     if (npts == 0) return fail(BLZ_ERR_INVALID_PARAM, "begin: empty task");
     // slots are handed out round-robin, so results complete in submission order
@@ -686,32 +855,16 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
     if (slots[slot].busy) slot = (slot + 1) % MSM_QUEUE_DEPTH;
     if (slots[slot].busy) return fail(BLZ_ERR_INVALID_PARAM, "task queue full (%d tasks in flight)", MSM_QUEUE_DEPTH);
     MsmSlot& S = slots[slot];
-    const int ebits = sbits == 256 ? kScalarFieldBits[curve] : sbits;
-    const bool ranged = bit_hi > bit_lo && !(bit_lo == 0 && bit_hi >= sbits);
-    if (ranged && (sbits != 256 || (bit_lo & 31) || (bit_hi & 31) || bit_hi > 256))
-        return fail(BLZ_ERR_INVALID_PARAM, "scalar range [%d, %d): 32-bit aligned ranges of 256-bit scalars", bit_lo, bit_hi);
-    // (a window table of a ranged handle holds 2^(lo + c j) P: the plan covers hi - lo bits + the carry, no closing doublings)
-    MsmPlan P = table_c > 0 ? make_table_plan(npts, table_c, ranged ? bit_hi - bit_lo + 1 : 257)
-                : ranged    ? plan_for_range(npts, bit_lo, bit_hi)
-                            : make_plan(npts, sbits, ebits, plan_override("c", 0));
-    if (P.c == 0) return fail(BLZ_ERR_INVALID_PARAM, "no window plan for npts=%u sbits=%d%s", npts, sbits, table_c > 0 ? " (window table)" : "");
-    if (P.table && !msm_sort3_ok(P, sbits)) return fail(BLZ_ERR_INVALID_PARAM, "window-table task outside the sort's range (c=%d)", P.c);
-    P.L = (uint32_t)plan_override("L", (int)P.L);
-    if (P.L < 1) P.L = 1;
-    if (P.L > (uint32_t)MAX_L) P.L = MAX_L;
+    MsmPlan P;
+    bool ranged = false;
+    BLZ_TRY(msm_task_plan(curve, npts, sbits, table_c, bit_lo, bit_hi, P, &ranged));
     const uint64_t G = P.G;
-    BLZ_LOG(2, "msm plan: npts=%u sbits=%d c=%d W=%d Bw=%u G=%llu L=%u pieces=%d", npts, sbits, P.c, P.W, P.Bw,
-            (unsigned long long)G, P.L, nslices);
-    if (nslices < 1 || P.table) nslices = 1;
-    if (nslices > MSM_MAX_SLICES) nslices = MSM_MAX_SLICES;
-    // pieces of whole 16-point groups (keeps every piece's scalars 16-byte aligned; pf = 8: whole elements)
-    // A task whose pieces arrive over the link (phased) ends with HALF a piece: behind the last byte sit that piece's
-    // accumulation, the bucket reduce and the tail, and the accumulation is the one part of it that shrinks with the piece
-    // (config 2: 13.5 -> 13.0 ms, the lone 2^26 HBM flow 138.6 -> 133); the pieces before it are 1 / (2 k - 1) larger.
-    const uint64_t halves = (phased && nslices >= 4) ? 2ull * nslices - 1 : 2ull * nslices;
-    uint32_t per = (uint32_t)(((2ull * npts + halves - 1) / halves + 15) & ~(uint64_t)15);
-    if (nslices > 1) nslices = (int)(((uint64_t)npts + per - 1) / per);
-    const uint64_t max_entries = (uint64_t)(nslices > 1 ? per : npts) * P.W;
+    uint32_t per = npts;
+    nslices = msm_task_pieces(P, nslices, phased, &per);
+    BLZ_TRY(plan_tail(P, ops->tail, nslices > 1, S.tail));   // (a refusal leaves the slot free)
+    BLZ_LOG(2, "msm plan: npts=%u sbits=%d c=%d W=%d Bw=%u G=%llu L=%u pieces=%d tail: %s", npts, sbits, P.c, P.W, P.Bw,
+            (unsigned long long)G, P.L, nslices, describe(S.tail).c_str());
+    const uint64_t max_entries = (uint64_t)per * P.W;
     const uint64_t max_units = G + max_entries / P.L + 1;
     if (max_units >= (1ull << 32)) return fail(BLZ_ERR_INVALID_PARAM, "unit bound %llu exceeds 32 bits", (unsigned long long)max_units);
 
@@ -766,7 +919,7 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
     S.bit_hi = bit_hi;
     S.repr = repr;
     S.slices = nslices;
-    S.pts_per_slice = nslices > 1 ? per : npts;
+    S.pts_per_slice = per;
     S.max_units = max_units;
     S.use_s3 = s3 && (hide || hide_env == 2 || P.table);
     S.sort_hidden = hide;
@@ -785,7 +938,7 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
     }
     BLZ_TRY(blocksums.reserve((size_t)((G + 1 + SCAN_TILE - 1) / SCAN_TILE) * 8));
     if (nslices > 1) {
-        const size_t sum_bytes = (size_t)ops->partial_dwords * 4;
+        const size_t sum_bytes = (size_t)ops->tail.partial_dwords * 4;
         BLZ_TRY(bucket_sums.reserve((G + 1) * sum_bytes));
         BLZ_TRY(bucket_ident.reserve((G + 2) * 4));
         hipLaunchKernelGGL(k_zero, dim3(2048), dim3(256), 0, st, (uint4*)bucket_sums.p, ((G + 1) * sum_bytes + 15) / 16);   // all-zero = infinity
@@ -887,13 +1040,13 @@ int MsmEngine::accumulate_slice(int slot, int sl, const void* d_pts) {
     if (slot < 0 || slot >= MSM_QUEUE_DEPTH || !slots[slot].open) return fail(BLZ_ERR_INVALID_PARAM, "slot %d has no task being enqueued", slot);
     MsmSlot& S = slots[slot];
     if (S.repr != repr) return fail(BLZ_ERR_INVALID_PARAM, "the handle's arithmetic changed while task %d was being enqueued", slot);
-    const MsmCurveOps* ops = ops_for(curve, repr);
+    const MsmCurveOps* ops = msm_ops_for(curve, repr);
     cur = slot;
     last_plan = S.plan;
     sort_st = S.sort_hidden ? sort_stream : stream;
     sb_sel = S.pingpong ? (slot + sl) % MSM_QUEUE_DEPTH : slot;
     if (S.sort_hidden) BLZ_HIP(hipStreamWaitEvent(stream, S.pingpong ? S.ev_sorted_pp[sl & 1] : S.ev_sorted, 0), BLZ_ERR_UNKNOWN);
-    BLZ_TRY(ops->run_accumulate(*this, d_pts, (uint32_t)S.max_units, S.slices > 1 ? sl : -1));
+    BLZ_TRY(ops->run_accumulate(*this, S, d_pts, (uint32_t)S.max_units, S.slices > 1 ? sl : -1));
     if (S.slices > 1) BLZ_TRY(ops->merge_buckets(*this));
     if (S.pingpong) {
         BLZ_HIP(hipEventRecord(S.ev_acc_pp[sl & 1], stream), BLZ_ERR_UNKNOWN);
@@ -908,7 +1061,7 @@ int MsmEngine::end(int slot) {
     if (slot < 0 || slot >= MSM_QUEUE_DEPTH || !slots[slot].open) return fail(BLZ_ERR_INVALID_PARAM, "slot %d has no task being enqueued", slot);
     MsmSlot& S = slots[slot];
     if (S.repr != repr) return fail(BLZ_ERR_INVALID_PARAM, "the handle's arithmetic changed while task %d was being enqueued", slot);
-    const MsmCurveOps* ops = ops_for(curve, repr);
+    const MsmCurveOps* ops = msm_ops_for(curve, repr);
     cur = slot;
     last_plan = S.plan;
     if (S.task_inputs_event) {
@@ -920,9 +1073,9 @@ int MsmEngine::end(int slot) {
     sb_sel = slot;
     if (S.slices > 1) {
         hipLaunchKernelGGL(k_iota, dim3(1024), dim3(256), 0, stream, bucket_ident.as<uint32_t>(), S.plan.G + 2);
-        BLZ_TRY(ops->run_reduce(*this, bucket_sums.p, bucket_ident.p));
+        BLZ_TRY(ops->run_reduce(*this, S, bucket_sums.p, bucket_ident.p));
     } else {
-        BLZ_TRY(ops->run_reduce(*this, partial.p, sb().unit_off.p));
+        BLZ_TRY(ops->run_reduce(*this, S, partial.p, sb().unit_off.p));
     }
     S.l0_recorded = true;
     S.open = false;
@@ -944,7 +1097,7 @@ int MsmEngine::run(const void* d_pts, const void* d_scalars, uint32_t npts, int 
                    int bit_hi) {
     BLZ_TRY(use_device(device));
     if (npts == 0) {
-        const MsmCurveOps* ops = ops_for(curve, repr);
+        const MsmCurveOps* ops = msm_ops_for(curve, repr);
         hipStream_t st = stream;
         int slot = (cur + 1) % MSM_QUEUE_DEPTH;
         if (slots[slot].busy) slot = (slot + 1) % MSM_QUEUE_DEPTH;
@@ -1024,7 +1177,7 @@ int MsmEngine::finish(int slot, uint8_t* out) {
 
 int MsmEngine::combine_partials(const uint8_t* partials, size_t cnt, uint8_t* out, bool on_device) {
     BLZ_TRY(use_device(device));
-    return ops_for(curve, repr)->combine(*this, partials, cnt, out, on_device);
+    return msm_ops_for(curve, repr)->combine(*this, partials, cnt, out, on_device);
 }
 
 }  // namespace blz

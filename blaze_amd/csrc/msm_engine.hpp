@@ -41,6 +41,54 @@ MsmPlan make_plan(uint32_t npts, int sbits, int ebits, int force_c);
 int table_window_bits(uint32_t npts, int need_bits = 257);
 inline int table_windows(int c, int need_bits = 257) { return (need_bits + c - 1) / c; }
 MsmPlan make_table_plan(uint32_t npts, int c, int need_bits = 257);
+// The window plan a task gets (begin(); the tail-plan test hook): a window table's, a scalar range's or the plain one, with
+// BLAZE_MSM_PLAN's unit length and its clamps applied.  *ranged: the task covers only bits [bit_lo, bit_hi) of its scalars.
+int msm_task_plan(int curve, uint32_t npts, int sbits, int table_c, int bit_lo, int bit_hi, MsmPlan& P, bool* ranged);
+// ... and the pieces it is enqueued in (`want` asked for; phased: they arrive over the link): *per points each
+int msm_task_pieces(const MsmPlan& P, int want, bool phased, uint32_t* per);
+
+// ------------------------------------------------------------------------------------------------
+// The tail of a task - everything behind k_accumulate: the unit folds, the bucket-reduce levels, the Horner walk - is
+// served by kernels on four group laws: the 32-bit thread law, the reduced-radix thread law, the DPP quad law and the
+// wave-wide row law (msm_impl.hip.hpp).  Which kernels a task runs is decided ONCE, by plan_tail() in begin(), from the
+// window plan and the laws the field has; the launchers (run_accumulate_t / run_reduce_t) only launch what the plan names.
+// ------------------------------------------------------------------------------------------------
+struct TailTraits {
+    bool rr = false;          // the field has a reduced-radix twin (USE_RR): reduced-radix and quad kernels
+    bool row = false;         // ... on the loose 28-bit budget: the row law (ec_row.hip.hpp)
+    int partial_dwords = 0;   // dwords of one unit / bucket sum in `partial`
+};
+// window table of k_finish: window w owns virtual windows v0 .. v0 + m - 1 and starts at scalar bit `off`
+struct FinishPlan {
+    int W, logV;
+    uint16_t v0[MSM_MAX_W], off[MSM_MAX_W];   // make_plan keeps m <= 128 and sum m < 2^16 (checked when filled)
+    uint8_t m[MSM_MAX_W];
+};
+struct TailPlan {
+    // unit folds.  k_combine_units' tree (unit_passes launches: strides 1, 16, 256, ...) takes the buckets of more than
+    // `thr` units; a suffix [hot_start, G) of the bucket space - the windows the plan knows to be hot - goes to `hot`, the
+    // buckets of 2 .. thr units below it to `fold`
+    uint32_t thr = 0, hot_start = 0;
+    int unit_passes = 0;
+    enum Hot { HOT_NONE, HOT_WAVES8, HOT_ROW } hot = HOT_NONE;   // k_fold_hot / k_fold_hot_row
+    // k_combine_buckets (a lane per bucket) / _wave / _row; FOLD_ROW_WEAK leaves the sums in the row law's weakly
+    // normalised form, which k_reduce_level_row alone reads: only in front of a ROW level 0
+    enum Fold { FOLD_NONE, FOLD_LANE, FOLD_WAVE, FOLD_ROW_STRICT, FOLD_ROW_WEAK } fold = FOLD_NONE;
+    // bucket reduce: level l folds M sums per virtual window into T segments of SEG; level 0 stays on the main stream
+    struct Level {
+        uint32_t M, SEG, T;
+        int shift;
+        enum Kind { W32, RR, QUAD, ROW } kind;
+    } level[16];
+    int levels = 0;
+    bool finish_row = false;   // k_finish_row / k_finish
+    FinishPlan fp;
+};
+// BLZ_ERR_UNKNOWN (nothing enqueued yet) for a plan the kernels cannot serve: a window plan outside k_finish's table range,
+// a kernel on a law the field lacks, a weak row fold or a row level in front of a reader on another law
+int plan_tail(const MsmPlan& P, TailTraits tr, bool piecewise, TailPlan& out);
+// one canonical line: "units2 hot_row fold_row_weak | L0row Lrow Lrow finish_row"
+std::string describe(const TailPlan& T);
 
 // Task queue (msm_hw_code.rs:19-25: the device has a task queue and a result queue): up to
 // MSM_QUEUE_DEPTH tasks may be in flight.  The throughput-bound part of a task (sort, bucket
@@ -64,6 +112,7 @@ struct MsmSlot {
     uint32_t* stats_h = nullptr;   // pinned: [0] total units, [1] max bucket count, [2] total entries (read in finish())
     uint64_t max_units = 0;        // the bound the launches of this task were sized by
     MsmPlan plan;
+    TailPlan tail;                 // what runs behind the accumulation (begin())
     // piecewise tasks (msm.hip begin()): one event pair per piece around its k_accumulate_cont launch; finish() sums them
     hipEvent_t slice_ev[2 * 64] = {};
     int slices = 1;
@@ -195,12 +244,12 @@ struct MsmCurveOps {
     int (*emit_infinity)(MsmEngine&);
     // phase 1 after a digit sort: unit lists, k_accumulate, k_combine_units (at most max_units units; the real count is on
     // the device).  slice >= 0: piece of a piecewise task - k_accumulate_cont, bracketed by the piece's events.
-    int (*run_accumulate)(MsmEngine&, const void* d_pts, uint32_t max_units, int slice);
+    int (*run_accumulate)(MsmEngine&, MsmSlot&, const void* d_pts, uint32_t max_units, int slice);
     // piecewise tasks: bucket_sums[g] += the piece's sum of bucket g where its run needed several units
     int (*merge_buckets)(MsmEngine&);
     // phases 2 - 3 over bucket sums found at sums[unit_off[g]] (unit_off[g + 1] > unit_off[g], else the bucket is empty)
-    int (*run_reduce)(MsmEngine&, const void* sums, const void* unit_off);
-    int partial_dwords;   // dwords of one unit / bucket sum in `partial`
+    int (*run_reduce)(MsmEngine&, MsmSlot&, const void* sums, const void* unit_off);
+    TailTraits tail;
     // VGPRs of k_accumulate as compiled (hipFuncGetAttributes): what the hidden sort has to fit beside
     int (*accumulate_vgprs)();
     // window table of npts wire-format points (msm_impl.hip.hpp k_build_window_table): table[i W + j] = 2^(base_shift + c j) P_i in the
@@ -223,5 +272,6 @@ const MsmCurveOps& msm_ops_bls377();
 const MsmCurveOps& msm_ops_bls381();
 const MsmCurveOps& msm_ops_bn254();
 const MsmCurveOps& msm_ops_bn254_w32();
+const MsmCurveOps* msm_ops_for(int curve, int repr = 0);   // nullptr: unknown curve
 
 }  // namespace blz

@@ -908,13 +908,7 @@ __device__ void emit_result(uint32_t* out, const XYZZ<F>& p) {
     fp_store(out + 2 * F::N, x);
 }
 
-// window table of k_finish: window w owns virtual windows v0 .. v0 + m - 1 and starts at scalar bit `off`
-struct FinishPlan {
-    int W, logV;
-    uint16_t v0[MSM_MAX_W], off[MSM_MAX_W];   // make_plan keeps m <= 128 and sum m < 2^16 (checked when filled)
-    uint8_t m[MSM_MAX_W];
-};
-
+// (FinishPlan - the window table of k_finish - is filled by plan_tail(): msm_engine.hpp)
 // The bucket reduce leaves, per virtual window v (V buckets), A_v = sum of its buckets and
 // C_v = sum_b (b + 1) B_b.  A window made of m virtual windows has
 //   S_w = sum_j C_(v0+j) + V * sum_j j * A_(v0+j),
@@ -1165,7 +1159,7 @@ __global__ __launch_bounds__(64, 2) void k_combine_buckets_wave(const uint32_t* 
     if (lane == 0) ptrr_store(partial, u0, acc);
 }
 
-// The same fold on the row law (ec_row.hip.hpp) for the tasks whose whole tail runs on it (small_row_tail: every reduce level is a
+// The same fold on the row law (ec_row.hip.hpp) for the tasks whose whole tail runs on it (TailPlan::FOLD_ROW_WEAK: every reduce level is a
 // row level): one wave per bucket adds the bucket's units in sequence, ~3 us per addition - against ~20 us per ROUND of the
 // shuffle tree above and k_fold_hot's 0.09 ms for the 16-unit buckets of a 2^13 task's top window - and leaves the sum, in
 // the row law's weakly normalised form (read by k_reduce_level_row only), in the bucket's first unit.
@@ -1307,31 +1301,24 @@ __global__ __launch_bounds__(128, 2) void k_merge_buckets(const uint32_t* __rest
     }
 }
 
-// phase 1 after a digit sort: at most U units (the real count is in E.sb().stats on the device)
-// level 0's segment length (run_reduce_t) and whether the task's reduce runs on the row law from level 0 on
-inline uint32_t reduce_seg0(const MsmPlan& P) {
-    uint32_t seg0_auto = 64;
-    while (seg0_auto > 8 && P.G / seg0_auto < 262144) seg0_auto >>= 1;
-    return (uint32_t)exp_knob("BLAZE_MSM_SEG", (int)seg0_auto);
-}
-inline uint32_t reduce_row_max() { return (uint32_t)exp_knob("BLAZE_REDUCE_ROW_MAX", 8192); }
+// The launchers below only launch what the task's TailPlan names (plan_tail(), msm.hip); a kernel the field does not have is an error.
 template <class F>
-bool small_row_tail(const MsmPlan& P) {
-    if constexpr (USE_RR<F>) {
-        if constexpr (!RR_TIGHT<typename F::RR>) {
-            if (exp_knob("BLAZE_FINISH_ROW", 1) == 0) return false;
-            const uint32_t seg0 = reduce_seg0(P);
-            return (uint64_t)((P.Bw + seg0 - 1) / seg0) * (uint64_t)P.Wv <= reduce_row_max();
-        }
-    }
-    return false;
+constexpr bool has_row_law() {
+    if constexpr (USE_RR<F>) return !RR_TIGHT<typename F::RR>;
+    else return false;
 }
+template <class F>
+constexpr bool HAS_RR = USE_RR<F>;          // reduced-radix thread law + the quad law on it
+template <class F>
+constexpr bool HAS_ROW = has_row_law<F>();  // the wave-wide row law (ec_row.hip.hpp)
+inline int no_tail_kernel(const char* name) { return fail(BLZ_ERR_UNKNOWN, "the tail plan names %s, which this field does not have", name); }
 
+// phase 1 after a digit sort: at most U units (the real count is in E.sb().stats on the device)
 template <class F>
-int run_accumulate_t(MsmEngine& E, const void* d_pts, uint32_t U, int slice) {
+int run_accumulate_t(MsmEngine& E, MsmSlot& S, const void* d_pts, uint32_t U, int slice) {
     hipStream_t st = E.stream;
-    MsmSlot& S = E.slots[E.cur];
-    const MsmPlan& P = E.last_plan;
+    const MsmPlan& P = S.plan;
+    const TailPlan& T = S.tail;
     BLZ_TRY(E.partial.reserve(((size_t)U + 1) * 4 * partial_dwords<F>()));
     if (slice <= 0) BLZ_HIP(hipEventRecord(S.ev[1], st), BLZ_ERR_UNKNOWN);   // (piecewise task: the FIRST piece's sort stage is done)
     S.accum_timed = true;
@@ -1348,98 +1335,44 @@ int run_accumulate_t(MsmEngine& E, const void* d_pts, uint32_t U, int slice) {
                            E.sb().unit_bucket.as<uint32_t>(), E.sb().unit_order.as<uint32_t>(), E.sb().stats.as<uint32_t>(), P.L,
                            E.partial.as<uint32_t>(), E.bucket_sums.as<uint32_t>(), slice == 0 ? 1u : 0u);
     BLZ_HIP(hipEventRecord(slice < 0 ? S.ev[6] : S.slice_ev[2 * slice + 1], st), BLZ_ERR_UNKNOWN);
-    // a bucket holds at most one entry per point (window-table tasks: one per point and window)
-    const uint64_t maxunits = ((uint64_t)P.npts * (P.table ? P.W : 1) + P.L - 1) / P.L;
     uint64_t full_bound = (uint64_t)P.npts * P.W / P.L + 1;  // units of length L: at most entries / L
     if (full_bound > U) full_bound = U;
-    // where the plan itself says that buckets hold several units each (mean run > L / 2), the lane-per-bucket fold takes
-    // every bucket of up to 64 units and the tree only the hot ones beyond
-    // (... and for every task of up to 2^22 points: one window of such a task can be twice as dense as the mean - the top real
-    // window of 255-bit scalars below r covers 0x39f6 of its 2^15 buckets at c = 16 - and the quad tree, built for a handful of
-    // hot buckets, spent 0.48 ms of a 4.8 ms 2^20 task on its 14 K two-unit buckets; one pass over the unit offsets is nothing here)
-    const uint32_t thr = ((uint64_t)P.npts * P.W / (P.G ? P.G : 1) > P.L / 2 || P.npts <= (1u << 22)) ? 64u : 0u;
-    // The windows the plan knows to be hot (the top ones, where the scalars' bits run out: a few buckets with long runs):
-    // a suffix [hot_start, G) of the bucket space goes to k_fold_hot - eight waves per bucket - and the two folds below
-    // leave it alone.  Only for a small suffix of a larger space: where EVERY window is like that (the precompute shapes) the
-    // lane-per-bucket fold below is the throughput-bound answer.
-    uint32_t hot_start = (uint32_t)P.G;
-    // Where the curve has the row law (ec_row.hip.hpp), a task of up to 2^17 bucket slots and units folds its buckets on it: one wave per bucket
-    // (k_combine_buckets_row, buckets of up to 64 units), sixteen per bucket of the plan's hot windows (k_fold_hot_row).  The
-    // sums leave in the accumulator form unless everything behind them runs on the row law too (small_row_tail).
-    bool row_law = false;
-    if constexpr (USE_RR<F>) row_law = !RR_TIGHT<typename F::RR> && exp_knob("BLAZE_FINISH_ROW", 1) != 0 && exp_knob("BLAZE_FOLD_ROW", 1) != 0;
-    // (a latency tool: chip-wide the row law adds ~5 x slower than one lane per point - 2^18 elements, 82 K buckets of four units:
-    // 0.41 ms against the lane-per-bucket fold's 0.19 - so only while the units to fold are few)
-    const bool row_fold = row_law && slice < 0 && thr != 0 && P.G <= (1u << 17) && (uint64_t)P.npts * P.W / P.L <= (1u << 17);
-    const bool row_tail = row_fold && small_row_tail<F>(P);
-    if constexpr (USE_RR<F>) {
-        if (!P.table && slice < 0 && P.ebits > 0 && exp_knob("BLAZE_FOLD_HOT", 1) != 0) {
-            int lowest = -1, off = 0;
-            bool any = false;
-            int offs[MSM_MAX_W];
-            for (int w = 0; w < P.W; ++w) { offs[w] = off; off += P.width[w]; }
-            for (int w = P.W - 1; w >= 0; --w) {
-                const int cw = P.width[w];
-                int t = P.ebits - offs[w];
-                if (t > cw) t = cw;
-                const double slots = (double)(1ull << (cw - 1));
-                double active = t >= cw ? slots : t > 0 ? (double)(1ull << t) + 1.0 : t == 0 ? 1.0 : 0.0;
-                if (active > slots) active = slots;
-                const double entries = t >= 0 ? (double)P.npts : 0.0;
-                const bool hot = active > 0 && entries / active >= 12.0 * (double)P.L;   // a dozen units or more per bucket
-                if (!hot && entries > 0) break;       // a normal window: the suffix ends above it
-                lowest = w;
-                any = any || hot;
-            }
-            if (any && lowest > 0 && P.G - P.boff[lowest] <= 16384) hot_start = P.boff[lowest];
-        }
+    const uint32_t* unit_off = E.sb().unit_off.as<uint32_t>();
+    uint32_t* partial = E.partial.as<uint32_t>();
+    uint64_t stride = 1;
+    for (int pass = 0; pass < T.unit_passes; ++pass, stride *= 16)
+        hipLaunchKernelGGL(k_combine_units<F>, dim3((uint32_t)((full_bound / 16 + 1) * 4 / 128 + 1)), dim3(128), 0, st, unit_off,
+                           E.sb().unit_bucket.as<uint32_t>(), E.sb().unit_order.as<uint32_t>(), E.sb().lenhist.as<uint32_t>() + P.L,
+                           E.sb().stats.as<uint32_t>(), P.L, (uint32_t)stride, T.thr, T.hot_start, partial);
+    const dim3 hot_grid((uint32_t)(P.G - T.hot_start)), fold_grid(T.hot_start);   // a block per bucket
+    switch (T.hot) {
+        case TailPlan::HOT_NONE: break;
+        case TailPlan::HOT_WAVES8:
+            if constexpr (HAS_RR<F>) hipLaunchKernelGGL(k_fold_hot<F>, hot_grid, dim3(512), 0, st, unit_off, T.hot_start, partial);
+            else return no_tail_kernel("k_fold_hot");
+            break;
+        case TailPlan::HOT_ROW:
+            if constexpr (HAS_ROW<F>) hipLaunchKernelGGL(k_fold_hot_row<F>, hot_grid, dim3(1024), 0, st, unit_off, T.hot_start, partial);
+            else return no_tail_kernel("k_fold_hot_row");
+            break;
     }
-    // (64-bit stride: with BLAZE_MSM_L < 8 and close to 2^31 points, maxunits exceeds 2^28 and a u32 stride would
-    // wrap to 0 - an endless launch loop)
-    for (uint64_t stride = 1; stride < maxunits; stride *= 16)
-        hipLaunchKernelGGL(k_combine_units<F>, dim3((uint32_t)((full_bound / 16 + 1) * 4 / 128 + 1)), dim3(128), 0, st,
-                           E.sb().unit_off.as<uint32_t>(), E.sb().unit_bucket.as<uint32_t>(), E.sb().unit_order.as<uint32_t>(),
-                           E.sb().lenhist.as<uint32_t>() + P.L, E.sb().stats.as<uint32_t>(), P.L, (uint32_t)stride, thr, hot_start,
-                           E.partial.as<uint32_t>());
-    if constexpr (USE_RR<F>) {
-        if (hot_start < P.G) {
-            bool done = false;
-            if constexpr (!RR_TIGHT<typename F::RR>) {
-                if (row_law) {
-                    hipLaunchKernelGGL(k_fold_hot_row<F>, dim3((uint32_t)(P.G - hot_start)), dim3(1024), 0, st, E.sb().unit_off.as<uint32_t>(), hot_start,
-                                       E.partial.as<uint32_t>());
-                    done = true;
-                }
-            }
-            if (!done)
-                hipLaunchKernelGGL(k_fold_hot<F>, dim3((uint32_t)(P.G - hot_start)), dim3(512), 0, st, E.sb().unit_off.as<uint32_t>(), hot_start,
-                                   E.partial.as<uint32_t>());
-        }
-    }
-    if (row_fold) {
-        if constexpr (USE_RR<F>) {
-            if constexpr (!RR_TIGHT<typename F::RR>) {
-                if (hot_start > 0) {
-                    if (row_tail)
-                        hipLaunchKernelGGL((k_combine_buckets_row<F, false>), dim3(hot_start), dim3(64), 0, st, E.sb().unit_off.as<uint32_t>(), thr,
-                                           E.partial.as<uint32_t>());
-                    else
-                        hipLaunchKernelGGL((k_combine_buckets_row<F, true>), dim3(hot_start), dim3(64), 0, st, E.sb().unit_off.as<uint32_t>(), thr,
-                                           E.partial.as<uint32_t>());
-                }
-            }
-        }
-    } else if (thr && hot_start > 0) {
-        bool wave = false;
-        if constexpr (USE_RR<F>) wave = hot_start <= 32768;   // small bucket spaces: one wave per bucket (latency), else one lane (throughput)
-        if (wave) {
-            if constexpr (USE_RR<F>)
-                hipLaunchKernelGGL(k_combine_buckets_wave<F>, dim3(hot_start), dim3(64), 0, st, E.sb().unit_off.as<uint32_t>(), thr,
-                                   E.partial.as<uint32_t>());
-        } else {
-            hipLaunchKernelGGL(k_combine_buckets<F>, dim3((hot_start + 127) / 128), dim3(128), 0, st, E.sb().unit_off.as<uint32_t>(),
-                               (uint64_t)hot_start, thr, E.partial.as<uint32_t>());
-        }
+    switch (T.fold) {
+        case TailPlan::FOLD_NONE: break;
+        case TailPlan::FOLD_LANE:
+            hipLaunchKernelGGL(k_combine_buckets<F>, dim3((T.hot_start + 127) / 128), dim3(128), 0, st, unit_off, (uint64_t)T.hot_start, T.thr, partial);
+            break;
+        case TailPlan::FOLD_WAVE:
+            if constexpr (HAS_RR<F>) hipLaunchKernelGGL(k_combine_buckets_wave<F>, fold_grid, dim3(64), 0, st, unit_off, T.thr, partial);
+            else return no_tail_kernel("k_combine_buckets_wave");
+            break;
+        case TailPlan::FOLD_ROW_STRICT:
+            if constexpr (HAS_ROW<F>) hipLaunchKernelGGL((k_combine_buckets_row<F, true>), fold_grid, dim3(64), 0, st, unit_off, T.thr, partial);
+            else return no_tail_kernel("k_combine_buckets_row");
+            break;
+        case TailPlan::FOLD_ROW_WEAK:
+            if constexpr (HAS_ROW<F>) hipLaunchKernelGGL((k_combine_buckets_row<F, false>), fold_grid, dim3(64), 0, st, unit_off, T.thr, partial);
+            else return no_tail_kernel("k_combine_buckets_row");
+            break;
     }
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     return BLZ_OK;
@@ -1456,127 +1389,84 @@ int merge_buckets_t(MsmEngine& E) {
 
 // phases 2 - 3: bucket reduce over the sums at sums[unit_off[g]], then the window combine
 template <class F>
-int run_reduce_t(MsmEngine& E, const void* sums, const void* unit_off_v) {
+int run_reduce_t(MsmEngine& E, MsmSlot& S, const void* sums, const void* unit_off_v) {
     hipStream_t st = E.stream;
-    MsmSlot& S = E.slots[E.cur];
-    const MsmPlan& P = E.last_plan;
+    const MsmPlan& P = S.plan;
+    const TailPlan& T = S.tail;
     const uint32_t* unit_off = (const uint32_t*)unit_off_v;
+    uint32_t* const result = E.slot_result((int)(&S - E.slots));
     BLZ_HIP(hipEventRecord(S.ev[2], st), BLZ_ERR_UNKNOWN);
 
     // ---- phase 2
-    // level 0 is throughput-bound (2 adds per bucket): long segments; the upper levels have few
-    // lanes and are latency-bound on their sequential chain: short segments, more levels
-    // (a small bucket space cannot fill the chip with long segments: the level wants >= 2^18 lanes - two full rounds of
-    // two waves per SIMD - before it wants long segments; the extra segment sums are absorbed by the upper levels, which
-    // run on the tail stream).  Same-box sweeps, profiles/r03_seg_sweep.txt: 17.8 M bucket slots (the 2^26 plan) 64 best; 12.6 M: 32 (61.9 against 62.9 ms per MSM);
-    // 5 - 7 M: 16 (17.2 against 17.8); 2.1 M (2^22): 8 (10.1 against 11.1).  Powers of two only: the upper levels weigh
-    // segment t by shifts.
-    const uint32_t SEG0 = reduce_seg0(P);
-    const uint32_t SEGU = (uint32_t)exp_knob("BLAZE_MSM_SEG_UPPER", 8);
-    uint32_t M = P.Bw;
-    int level = 0, shift = 0;
-    // the Horner walk and the levels of few segments run on the row law (ec_row.hip.hpp) where the curve has it
-    bool row_walk = false, row_levels = false;
-    if constexpr (USE_RR<F>) row_walk = !RR_TIGHT<typename F::RR> && exp_knob("BLAZE_FINISH_ROW", 1) != 0;
-    const uint32_t row_max = reduce_row_max();
     const uint32_t* curA = (const uint32_t*)sums;
     const uint32_t* curC = nullptr;
-    for (;;) {
-        const uint32_t SEG = level == 0 ? SEG0 : SEGU;
-        int seglog = 0;
-        while ((1u << seglog) < SEG) ++seglog;
-        uint32_t T = (M + SEG - 1) / SEG;
+    for (int level = 0; level < T.levels; ++level) {
+        const TailPlan::Level& V = T.level[level];
         DevBuf& oA = S.lvlA[level & 1];
         DevBuf& oC = S.lvlC[level & 1];
-        BLZ_TRY(oA.reserve((size_t)T * P.Wv * 4 * partial_dwords<F>()));   // (reduced-radix accumulators where the curve has them)
-        BLZ_TRY(oC.reserve((size_t)T * P.Wv * 4 * partial_dwords<F>()));
-        uint32_t nthreads = T * (uint32_t)P.Wv;
-        // few segments: one per wave on the row law, from here to the end (k_reduce_level_row)
-        if (row_walk && nthreads <= row_max) row_levels = true;
-        if (row_levels) {
-            if constexpr (USE_RR<F>) {
-                if constexpr (!RR_TIGHT<typename F::RR>) {
+        BLZ_TRY(oA.reserve((size_t)V.T * P.Wv * 4 * partial_dwords<F>()));   // (reduced-radix accumulators where the curve has them)
+        BLZ_TRY(oC.reserve((size_t)V.T * P.Wv * 4 * partial_dwords<F>()));
+        uint32_t* const outA = oA.as<uint32_t>();
+        uint32_t* const outC = oC.as<uint32_t>();
+        const uint32_t nthreads = V.T * (uint32_t)P.Wv;   // segments
+        const dim3 lanes((nthreads + 63) / 64), quads((nthreads * 4 + 63) / 64), waves(nthreads), b64(64);
+        switch (V.kind) {
+            case TailPlan::Level::ROW:
+                if constexpr (HAS_ROW<F>) {
                     if (level == 0)
-                        hipLaunchKernelGGL((k_reduce_level_row<F, true>), dim3(nthreads), dim3(64), 0, st, curA, curC, unit_off, M, SEG, T, P.Wv,
-                                           shift, oA.as<uint32_t>(), oC.as<uint32_t>());
+                        hipLaunchKernelGGL((k_reduce_level_row<F, true>), waves, b64, 0, st, curA, curC, unit_off, V.M, V.SEG, V.T, P.Wv, V.shift, outA, outC);
                     else
-                        hipLaunchKernelGGL((k_reduce_level_row<F, false>), dim3(nthreads), dim3(64), 0, st, curA, curC, unit_off, M, SEG, T, P.Wv,
-                                           shift, oA.as<uint32_t>(), oC.as<uint32_t>());
-                }
-            }
-            if (level == 0) {
-                BLZ_HIP(hipEventRecord(S.ev_l0, st), BLZ_ERR_UNKNOWN);
-                st = E.tail_stream;
-                BLZ_HIP(hipStreamWaitEvent(st, S.ev_l0, 0), BLZ_ERR_UNKNOWN);
-            }
-        } else if (level == 0) {
-            if constexpr (USE_RR<F>) {
-                if (nthreads <= (uint32_t)exp_knob("BLAZE_REDUCE_QUAD_MAX", 131072))
-                    hipLaunchKernelGGL(k_reduce_level0_quad<F>, dim3((nthreads * 4 + 63) / 64), dim3(64), 0, st, curA, unit_off, M,
-                                       SEG, T, P.Wv, oA.as<uint32_t>(), oC.as<uint32_t>());
-                else
-                    hipLaunchKernelGGL(k_reduce_level0_rr<F>, dim3((nthreads + 63) / 64), dim3(64), 0, st, curA, unit_off, M,
-                                       SEG, T, P.Wv, oA.as<uint32_t>(), oC.as<uint32_t>());
-            } else
-                hipLaunchKernelGGL((k_reduce_level<F, true>), dim3((nthreads + 63) / 64), dim3(64), 0, st, curA, curC,
-                                   unit_off, M, SEG, T, P.Wv, shift, oA.as<uint32_t>(), oC.as<uint32_t>());
+                        hipLaunchKernelGGL((k_reduce_level_row<F, false>), waves, b64, 0, st, curA, curC, unit_off, V.M, V.SEG, V.T, P.Wv, V.shift, outA, outC);
+                } else
+                    return no_tail_kernel("k_reduce_level_row");
+                break;
+            case TailPlan::Level::QUAD:
+                if constexpr (HAS_RR<F>) {
+                    if (level == 0)
+                        hipLaunchKernelGGL(k_reduce_level0_quad<F>, quads, b64, 0, st, curA, unit_off, V.M, V.SEG, V.T, P.Wv, outA, outC);
+                    else
+                        hipLaunchKernelGGL(k_reduce_level_rr<F>, quads, b64, 0, st, curA, curC, V.M, V.SEG, V.T, P.Wv, V.shift, outA, outC);
+                } else
+                    return no_tail_kernel("k_reduce_level_rr");
+                break;
+            case TailPlan::Level::RR:   // (level 0 only: plan_tail)
+                if constexpr (HAS_RR<F>) hipLaunchKernelGGL(k_reduce_level0_rr<F>, lanes, b64, 0, st, curA, unit_off, V.M, V.SEG, V.T, P.Wv, outA, outC);
+                else return no_tail_kernel("k_reduce_level0_rr");
+                break;
+            case TailPlan::Level::W32:
+                if constexpr (!HAS_RR<F>) {
+                    if (level == 0)
+                        hipLaunchKernelGGL((k_reduce_level<F, true>), lanes, b64, 0, st, curA, curC, unit_off, V.M, V.SEG, V.T, P.Wv, V.shift, outA, outC);
+                    else
+                        hipLaunchKernelGGL((k_reduce_level<F, false>), quads, b64, 0, st, curA, curC, unit_off, V.M, V.SEG, V.T, P.Wv, V.shift, outA, outC);
+                } else
+                    return no_tail_kernel("k_reduce_level");
+                break;
+        }
+        if (level == 0) {
             // the rest is a few lanes of sequential work: hand it to the tail stream, so this stream can
             // start the next task's sort while it runs
             BLZ_HIP(hipEventRecord(S.ev_l0, st), BLZ_ERR_UNKNOWN);
             st = E.tail_stream;
             BLZ_HIP(hipStreamWaitEvent(st, S.ev_l0, 0), BLZ_ERR_UNKNOWN);
-        } else {
-            if constexpr (USE_RR<F>)
-                hipLaunchKernelGGL(k_reduce_level_rr<F>, dim3((nthreads * 4 + 63) / 64), dim3(64), 0, st, curA, curC, M, SEG, T, P.Wv,
-                                   shift, oA.as<uint32_t>(), oC.as<uint32_t>());
-            else
-                hipLaunchKernelGGL((k_reduce_level<F, false>), dim3((nthreads * 4 + 63) / 64), dim3(64), 0, st, curA, curC,
-                                   unit_off, M, SEG, T, P.Wv, shift, oA.as<uint32_t>(), oC.as<uint32_t>());
         }
-        curA = oA.as<uint32_t>();
-        curC = oC.as<uint32_t>();
-        shift += seglog;
-        M = T;
-        ++level;
-        if (T == 1) break;
+        curA = outA;
+        curC = outC;
     }
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     BLZ_HIP(hipEventRecord(S.ev[3], st), BLZ_ERR_UNKNOWN);
 
-    // ---- phase 3
-    FinishPlan fp;
-    fp.W = P.W;
-    fp.logV = 0;
-    while ((1u << fp.logV) < P.Bw) ++fp.logV;
-    if (P.table) {
-        // one bucket set for all the scalar's windows (their weights are in the table's points): a single window at bit 0
-        fp.W = 1;
-        fp.v0[0] = 0;
-        fp.m[0] = (uint8_t)(P.G >> fp.logV);
-        fp.off[0] = 0;
+    // ---- phase 3: the Horner walk, on the row law (ec_row.hip.hpp) where the curve has it
+    if (T.finish_row) {
+        if constexpr (HAS_ROW<F>) hipLaunchKernelGGL(k_finish_row<F>, dim3(1), dim3(64), 0, st, curA, curC, T.fp, result);
+        else return no_tail_kernel("k_finish_row");
     } else {
-        int off = P.base_bit;
-        for (int w = 0; w < P.W; ++w) {
-            const uint32_t v0 = P.boff[w] >> fp.logV, m = (P.boff[w + 1] - P.boff[w]) >> fp.logV;
-            if (v0 > 0xffffu || m > 0xffu || off > 0xffff)
-                return fail(BLZ_ERR_UNKNOWN, "window plan outside k_finish's table range (window %d: v0=%u m=%u off=%d)", w, v0, m, off);
-            fp.v0[w] = (uint16_t)v0;
-            fp.m[w] = (uint8_t)m;
-            fp.off[w] = (uint16_t)off;
-            off += P.width[w];
-        }
-    }
-    if (row_walk) {
-        if constexpr (USE_RR<F>) {
-            if constexpr (!RR_TIGHT<typename F::RR>)
-                hipLaunchKernelGGL(k_finish_row<F>, dim3(1), dim3(64), 0, st, curA, curC, fp, E.slot_result(E.cur));
-        }
-    } else {
-        hipLaunchKernelGGL(k_finish<F>, dim3(1), dim3(64), 0, st, curA, curC, fp, E.slot_result(E.cur));
+        if constexpr (!HAS_ROW<F>) hipLaunchKernelGGL(k_finish<F>, dim3(1), dim3(64), 0, st, curA, curC, T.fp, result);
+        else return no_tail_kernel("k_finish");
     }
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     BLZ_HIP(hipEventRecord(S.ev[4], st), BLZ_ERR_UNKNOWN);
-    BLZ_TRY(copy_words_to_pinned(S.result_h, E.slot_result(E.cur), 3 * F::N, st));   // (not a copy-engine transfer: msm_engine.hpp)
+    BLZ_TRY(copy_words_to_pinned(S.result_h, result, 3 * F::N, st));   // (not a copy-engine transfer: msm_engine.hpp)
     BLZ_HIP(hipEventRecord(S.ev_done, st), BLZ_ERR_UNKNOWN);
     return BLZ_OK;
 }
@@ -1677,7 +1567,7 @@ MsmCurveOps make_ops() {
     o.run_accumulate = &run_accumulate_t<F>;
     o.merge_buckets = &merge_buckets_t<F>;
     o.run_reduce = &run_reduce_t<F>;
-    o.partial_dwords = partial_dwords<F>();
+    o.tail = TailTraits{HAS_RR<F>, HAS_ROW<F>, partial_dwords<F>()};
     o.accumulate_vgprs = &accumulate_vgprs_t<F>;
     o.build_table = &build_table_t<F>;
     o.table_scratch_bytes = &table_scratch_bytes_t<F>;

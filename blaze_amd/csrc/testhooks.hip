@@ -1,9 +1,10 @@
 // Element-wise kernels over the device field / group primitives, so tests can compare each of them
-// with the CPU oracle (include/blaze_hip.h "test hooks").  Not on the MSM/NTT product path.
+// with the CPU oracle (include/blaze_hip.h "test hooks"), and the MSM tail plan of a shape.  Not on the MSM/NTT product path.
 #include "common.hpp"
 #include "ec_rr.hip.hpp"
 #include "ec_row.hip.hpp"
 #include "poseidon_engine.hpp"
+#include "msm_engine.hpp"
 
 namespace blz {
 
@@ -613,6 +614,27 @@ int blz_test_poseidon_tree_check(int device_id, int field, const uint8_t* words,
         case BLZ_BN254: return test_pos_tree_check_t<Fr_BN254>(words, len, tree_mode, tree_height, d_input, d_records, out);
     }
     return fail(BLZ_ERR_INVALID_PARAM, "unknown field %d", field);
+}
+
+int blz_test_msm_tail_plan(int curve, int repr, uint32_t npts, int sbits, int pieces, int table_c, int bit_lo, int bit_hi, uint32_t plan_out[8],
+                           uint8_t* widths, char* text, size_t cap) {
+    if (!plan_out || !text || cap == 0) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    const MsmCurveOps* ops = msm_ops_for(curve, repr);
+    if (!ops || npts == 0) return fail(BLZ_ERR_INVALID_PARAM, "unknown curve %d or empty task", curve);
+    // the steps of MsmEngine::begin()
+    MsmPlan P;
+    BLZ_TRY(msm_task_plan(curve, npts, sbits, table_c, bit_lo, bit_hi, P, nullptr));
+    uint32_t per = 0;
+    pieces = msm_task_pieces(P, pieces, false, &per);
+    TailPlan T;
+    BLZ_TRY(plan_tail(P, ops->tail, pieces > 1, T));
+    const uint32_t out[8] = {(uint32_t)P.c, (uint32_t)P.W, (uint32_t)P.G, P.L, P.Bw, (uint32_t)P.Wv, (uint32_t)P.ebits, P.table ? 1u : 0u};
+    memcpy(plan_out, out, sizeof(out));
+    if (widths) memcpy(widths, P.width, (size_t)P.W);
+    const std::string line = describe(T);
+    if (line.size() >= cap) return fail(BLZ_ERR_INVALID_PARAM, "text buffer of %zu bytes for a line of %zu", cap, line.size());
+    memcpy(text, line.c_str(), line.size() + 1);
+    return BLZ_OK;
 }
 
 }  // extern "C"

@@ -53,6 +53,15 @@ int blz_test_field_op(int device_id, int curve, int field, int op, const uint8_t
 int blz_test_ec_op(int device_id, int curve, int op, const uint8_t* p, const uint8_t* q,
                    const uint8_t* inf_flags, uint8_t* out, uint8_t* out_inf, size_t n);
 
+/* The window plan and the tail schedule MsmEngine::begin() gives a task of npts points of sbits-bit scalars (256 / 32 / 64) on `curve`
+ * with arithmetic `repr` (0, or 1 = BN254 on 32-bit limbs), asked for in `pieces` pieces, with a window table of width table_c (0: none)
+ * and the scalar range [bit_lo, bit_hi) (0, 0: all).  Host only, no device (like blz_msm_plan); BLAZE_MSM_PLAN applies.
+ * plan_out = {c, W, G, L, Bw, Wv, ebits, table}; widths (nullable, 96 bytes): the window widths; text: the kernels behind the
+ * accumulation as one line, "units<k_combine_units passes> [hot|hot_row] fold_<none|lane|wave|row_strict|row_weak> |
+ * L0<w32|rr|quad|row> L<..> ... finish[_row]".  A plan the kernels cannot serve is an error, as it is for the task. */
+int blz_test_msm_tail_plan(int curve, int repr, uint32_t npts, int sbits, int pieces, int table_c, int bit_lo, int bit_hi, uint32_t plan_out[8],
+                           uint8_t* widths, char* text, size_t cap);
+
 /* ------------------------------------------------------------------ Poseidon (blaze_hip.h "Poseidon")
  * words / len: an instruction word stream as blz_poseidon_initialize_words takes it.
  * blz_test_poseidon_permute: the DEFINITION kernel - one lane per state, the dense textbook rounds on the 8 x 32-bit Montgomery

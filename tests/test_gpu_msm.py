@@ -1229,6 +1229,43 @@ def test_piecewise_accumulation(gpu, orc, curve, pf, monkeypatch):
         b_.free()
 
 
+# (curve, precompute factor, elements, BLAZE_MSM_PLAN, BLAZE_MSM_PIECES, the tail's schedule): the smallest default shape of every
+# distinct schedule (tests/test_msm_tail_plan.py PINNED; fold_none is served by the 2^24 / 2^26 tests)
+TAIL_SCHEDULES = [
+    ("BLS381", 1, 16, None, None, "units0 fold_row_weak | L0row finish_row"),
+    ("BLS381", 1, 1 << 12, None, None, "units2 hot_row fold_row_weak | L0row Lrow Lrow finish_row"),
+    ("BLS377", 1, 1 << 12, None, None, "units2 hot_row fold_row_weak | L0row Lrow Lrow finish_row"),
+    ("BLS381", 1, 1 << 12, None, "3", "units2 fold_wave | L0row Lrow Lrow finish_row"),
+    ("BLS381", 1, 1 << 17, None, None, "units4 hot_row fold_lane | L0quad Lrow Lrow Lrow finish_row"),
+    ("BLS381", 8, 1 << 16, None, None, "units4 fold_row_strict | L0quad Lrow Lrow Lrow Lrow Lrow finish_row"),
+    ("BLS381", 1, 1 << 13, "c=18", None, "units3 fold_lane | L0rr Lquad Lrow Lrow Lrow Lrow finish_row"),
+    ("BN254", 1, 1 << 10, None, None, "units2 hot fold_wave | L0quad Lquad finish"),
+    ("BN254", 1, 1 << 16, None, None, "units3 hot fold_lane | L0quad Lquad Lquad Lquad finish"),
+    ("BN254", 1, 1 << 14, "c=18", None, "units3 fold_lane | L0rr Lquad Lquad Lquad Lquad Lquad finish"),
+    ("BN254", 8, 1 << 9, None, None, "units2 fold_lane | L0w32 Lw32 Lw32 finish"),
+]
+
+
+@pytest.mark.parametrize("curve,pf,n,plan,pieces,schedule", TAIL_SCHEDULES,
+                         ids=[f"{r[0]}-pf{r[1]}-{r[2]}" + (f"-{r[3]}" if r[3] else "") + (f"-p{r[4]}" if r[4] else "") for r in TAIL_SCHEDULES])
+def test_every_tail_schedule_is_served(gpu, orc, curve, pf, n, plan, pieces, schedule, monkeypatch):
+    """Every schedule plan_tail() (msm.hip) can name - each fold, hot-fold, reduce-level and finish kernel on each group law -
+    runs once through the ordinary client: the shape gets the pinned schedule, and the result is the oracle's, byte for byte."""
+    if plan:
+        monkeypatch.setenv("BLAZE_MSM_PLAN", plan)
+    if pieces:
+        monkeypatch.setenv("BLAZE_MSM_PIECES", pieces)
+    out = (C.c_uint32 * 8)()
+    text = C.create_string_buffer(256)
+    blaze_amd._lib.check(blaze_amd.aux().blz_test_msm_tail_plan(pyref.CURVES[curve]["id"], int(curve == "BN254" and pf == 8), n * pf, 256 if pf == 1 else 32,
+                                                                int(pieces or 1), 0, 0, 0, out, None, text, len(text)))
+    assert text.value.decode() == schedule
+    pts, sc, exp = orc.input_generator(curve, n, pf, 9100 + pf)
+    cl = msm_client(curve, pf)
+    assert run_msm(cl, pts, sc, n) == exp
+    cl.close()
+
+
 @pytest.mark.parametrize("curve,pf,n", [("BLS381", 1, 70001), ("BLS377", 8, 9000), ("BN254", 1, 33333), ("BN254", 8, 4100)])
 def test_dma_pieces_host_buffers(gpu, orc, curve, pf, n, monkeypatch):
     """DMA mode with host buffers and a task already armed: the task is enqueued piece by piece while its bytes cross the
