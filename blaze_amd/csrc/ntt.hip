@@ -701,6 +701,72 @@ int blz_ntt_vec_op(blz_ntt* h, int op, size_t buf_dst, const blz_vec_arg* a, con
     return BLZ_OK;
 }
 
+// Folds along the buffer (include/blaze_hip.h; kernels and the workspace's layout: ntt_fold.hip.hpp).  The protocol of
+// blz_ntt_vec_op: everything is checked before anything is enqueued, nothing waits for the device, and the workspace is
+// `scratch` - n x 32 bytes that only an op of this handle uses, and none can be in flight.
+// d_out / d_total: 32 bytes checked like an operand's d_ptr (a one-word operand), and kept off the words of every d_ptr operand
+static int ntt_fold_out(blz_ntt* h, const char* name, void* p, const blz_vec_arg* a, const blz_vec_arg* b) {
+    const blz_vec_arg as_arg{p, 0u, 0u, 1u};
+    NttVecArg unused{};
+    uint32_t reads = 0;
+    BLZ_TRY(ntt_vec_operand(h, name, &as_arg, unused, reads));
+    for (const blz_vec_arg* v : {a, b}) {
+        if (!v || !v->d_ptr) continue;
+        const char *lo = (const char*)v->d_ptr, *hi = lo + v->count * 32, *q = (const char*)p;
+        if (q < hi && q + 32 > lo) return fail(BLZ_ERR_INVALID_PARAM, "%s overlaps the words of a d_ptr operand", name);
+    }
+    return BLZ_OK;
+}
+
+int blz_ntt_vec_reduce(blz_ntt* h, int op, const blz_vec_arg* a, const blz_vec_arg* b, void* d_out) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (op < 0 || op >= NTT_FOLD_OPS) return fail(BLZ_ERR_INVALID_PARAM, "unknown reduction %d", op);
+    const bool takes_b = op != BLZ_FOLD_SUM;
+    if (!a || (b != nullptr) != takes_b)
+        return fail(BLZ_ERR_INVALID_PARAM, "reduction %d takes operands a%s, and the other must be NULL", op, takes_b ? ", b" : "");
+    if (op == BLZ_FOLD_EVAL && (!b->d_ptr || b->count != 1))
+        return fail(BLZ_ERR_INVALID_PARAM, "BLZ_FOLD_EVAL takes the point as one device word: b.d_ptr != NULL, b.count == 1");
+    if (!d_out) return fail(BLZ_ERR_INVALID_PARAM, "null d_out");
+    BLZ_NTT_LIVE(h);
+    if (h->in_flight) return fail(BLZ_ERR_INVALID_PARAM, "a transform or an op on the buffers is already running; call wait_result first");
+    BLZ_TRY(use_device(h->device));
+    NttVecArg va{}, vb{};
+    uint32_t reads = 0;
+    BLZ_TRY(ntt_vec_operand(h, "a", a, va, reads));
+    if (takes_b) BLZ_TRY(ntt_vec_operand(h, "b", b, vb, reads));
+    BLZ_TRY(ntt_fold_out(h, "d_out", d_out, a, b));
+    BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
+    BLZ_TRY(h->ops->vec_reduce(h->stream, op, (uint32_t*)d_out, va, takes_b ? vb : va, 1ull << h->logn, h->scratch.as<uint32_t>()));
+    BLZ_HIP(hipEventRecord(h->ev1, h->stream), BLZ_ERR_UNKNOWN);
+    h->in_flight = true;
+    h->in_flight_buf = -1;   // no transform buffer is written
+    h->in_flight_reads = reads;
+    return BLZ_OK;
+}
+
+int blz_ntt_vec_scan(blz_ntt* h, int op, uint32_t flags, size_t buf_dst, const blz_vec_arg* a, void* d_total) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (op < 0 || op >= NTT_SCAN_OPS) return fail(BLZ_ERR_INVALID_PARAM, "unknown scan %d", op);
+    if (flags & ~BLZ_SCAN_EXCLUSIVE) return fail(BLZ_ERR_INVALID_PARAM, "unknown scan flags 0x%x", flags);
+    if (buf_dst > 1) return fail(BLZ_ERR_INVALID_PARAM, "buf_dst must be 0 or 1");
+    if (!a) return fail(BLZ_ERR_INVALID_PARAM, "a scan takes operand a");
+    BLZ_NTT_LIVE(h);
+    if (h->in_flight) return fail(BLZ_ERR_INVALID_PARAM, "a transform or an op on the buffers is already running; call wait_result first");
+    BLZ_TRY(use_device(h->device));
+    NttVecArg va{};
+    uint32_t reads = 0;
+    BLZ_TRY(ntt_vec_operand(h, "a", a, va, reads));
+    if (d_total) BLZ_TRY(ntt_fold_out(h, "d_total", d_total, a, nullptr));
+    BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
+    BLZ_TRY(h->ops->vec_scan(h->stream, op, flags, h->buf[buf_dst].as<uint32_t>(), va, 1ull << h->logn, (uint32_t*)d_total,
+                             h->scratch.as<uint32_t>()));
+    BLZ_HIP(hipEventRecord(h->ev1, h->stream), BLZ_ERR_UNKNOWN);
+    h->in_flight = true;
+    h->in_flight_buf = (int)buf_dst;
+    h->in_flight_reads = reads & ~(1u << buf_dst);
+    return BLZ_OK;
+}
+
 int blz_ntt_stream(blz_ntt* h, void** hip_stream, int* device_id) {
     if (!h || !hip_stream) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
     if (device_id) *device_id = h->device;

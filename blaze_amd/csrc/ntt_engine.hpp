@@ -76,6 +76,9 @@ struct NttVecArg {
 };
 constexpr int NTT_VEC_OPS = 6;               // enum blz_vec_op: ADD SUB MUL MULADD MULSUB INV
 constexpr uint64_t NTT_VEC_INV_TILE = 1024;  // batch inversion: elements per block (256 lanes x 4); one 32-byte total per tile
+constexpr int NTT_FOLD_OPS = 3;              // enum blz_fold_op: SUM DOT EVAL
+constexpr int NTT_SCAN_OPS = 2;              // enum blz_scan_op: SUM PROD
+constexpr uint64_t NTT_FOLD_TILE = 1024;     // prefix scans: elements per block (256 lanes x 4 consecutive); one 32-byte total per tile
 
 // per-field entry points.  Field ids follow enum blz_curve: the scalar field Fr of that curve.
 struct NttFieldOps {
@@ -100,6 +103,13 @@ struct NttFieldOps {
     // dst[e] = op(a, b, c)[e], e < n (enum blz_vec_op; b / c ignored by the ops that do not take them).  dst may be an operand.
     // totals: ceil(n / NTT_VEC_INV_TILE) x 32 bytes of device memory for the batch inversion's tile totals
     int (*vec_op)(hipStream_t st, int op, uint32_t* dst, NttVecArg a, NttVecArg b, NttVecArg c, uint64_t n, uint32_t* totals);
+    // Folds along the buffer (blz_ntt_vec_reduce / blz_ntt_vec_scan; kernels and the workspace's layout: ntt_fold.hip.hpp).
+    // ws: n x 32 bytes of device memory nothing else uses while the op runs
+    // out (32 bytes) = the fold of a (and b) over e < n (enum blz_fold_op; EVAL: b is the one-word point)
+    int (*vec_reduce)(hipStream_t st, int op, uint32_t* out, NttVecArg a, NttVecArg b, uint64_t n, uint32_t* ws);
+    // dst[e] = the running fold of a (enum blz_scan_op, flags: BLZ_SCAN_EXCLUSIVE); total (32 bytes, nullable) = the fold of all n.
+    // dst may be a.p
+    int (*vec_scan)(hipStream_t st, int op, uint32_t flags, uint32_t* dst, NttVecArg a, uint64_t n, uint32_t* total, uint32_t* ws);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

@@ -5,6 +5,7 @@
 #include "field.hip.hpp"
 #include "ntt_rr.hip.hpp"
 #include "ntt_vec.hip.hpp"
+#include "ntt_fold.hip.hpp"
 
 namespace blz {
 
@@ -513,6 +514,8 @@ NttFieldOps make_ntt_ops() {
     o.coset_tables = &ntt_coset_tables_t<Fr>;
     o.coset_unfold = &ntt_coset_unfold_t<Fr>;
     o.vec_op = &ntt_vec_op_t<Fr>;
+    o.vec_reduce = &ntt_vec_reduce_t<Fr>;
+    o.vec_scan = &ntt_vec_scan_t<Fr>;
     return o;
 }
 

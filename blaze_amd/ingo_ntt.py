@@ -41,6 +41,9 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
     BITREV_INPUT = 4     # BLZ_NTT_BITREV_INPUT
     BITREV_OUTPUT = 8    # BLZ_NTT_BITREV_OUTPUT
     ADD, SUB, MUL, MULADD, MULSUB, INV = range(6)   # enum blz_vec_op
+    FOLD_SUM, FOLD_DOT, FOLD_EVAL = range(3)        # enum blz_fold_op
+    SCAN_SUM, SCAN_PROD = range(2)                  # enum blz_scan_op
+    SCAN_EXCLUSIVE = 1                              # BLZ_SCAN_EXCLUSIVE
 
     def __init__(self, _ptype: NTT, dclient: DriverClient, log_size: int = NTT_LOG_SIZE, inverse: bool = False,
                  field: str = "BLS381", flags: int = 0, root: Optional[int] = None):
@@ -150,6 +153,28 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         args = [self._vec_arg(x) for x in (a, b, c)]
         check(lib().blz_ntt_vec_op(self._h, int(op), dst, *[None if v is None else C.byref(v) for v in args]))
         self._vec_keep = (a, b, c)
+
+    def vec_reduce(self, op: int, a, b=None, out: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """One value out of a vector (include/blaze_hip.h blz_ntt_vec_reduce): FOLD_SUM sum a[p], FOLD_DOT sum a[p] b[p],
+        FOLD_EVAL sum a[p] z^p with z the one-word DeviceBuffer `b` (0^0 = 1).  Operands as for vec_op.  Returns the 32-byte
+        DeviceBuffer the canonical result lands in (`out`, or a fresh one) once wait_result() has finished the op; the
+        transform buffers named are only read."""
+        if out is None:
+            out = DeviceBuffer(self.driver_client.id, NTT_WORD_SIZE)
+        args = [self._vec_arg(x) for x in (a, b)]
+        check(lib().blz_ntt_vec_reduce(self._h, int(op), *[None if v is None else C.byref(v) for v in args], out.ptr))
+        self._vec_keep = (a, b, out)
+        return out
+
+    def vec_scan(self, op: int, dst: int, a, exclusive: bool = False, total: Optional[DeviceBuffer] = None) -> None:
+        """Prefix scan along the buffer (blz_ntt_vec_scan): transform buffer `dst`[p] = a[0] o .. o a[p] (SCAN_SUM, SCAN_PROD),
+        or with exclusive=True the identity at p = 0 and a[0] o .. o a[p - 1] after it - an exclusive SCAN_PROD of a one-word
+        DeviceBuffer z writes the powers z^p.  `a` may name `dst` (in place).  `total` (a 32-byte DeviceBuffer) receives the
+        fold of all n elements.  Finished by wait_result()."""
+        va = self._vec_arg(a)
+        check(lib().blz_ntt_vec_scan(self._h, int(op), self.SCAN_EXCLUSIVE if exclusive else 0, dst,
+                                     None if va is None else C.byref(va), None if total is None else total.ptr))
+        self._vec_keep = (a, total)
 
     def scalar(self, value: int) -> DeviceBuffer:
         """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""

@@ -256,6 +256,15 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
     void vec_op(blz_vec_op op, size_t dst, const blz_vec_arg* a, const blz_vec_arg* b = nullptr, const blz_vec_arg* c = nullptr) {
         check(blz_ntt_vec_op(h_, (int)op, dst, a, b, c));
     }
+    // folds along the buffer (blz_ntt_vec_reduce / blz_ntt_vec_scan), enqueued the same way.  vec_reduce: 32 bytes of device
+    // memory d_out = sum a, sum a b, or sum a[p] z^p with z = the one-word operand b.  vec_scan: buffer dst = the running sum /
+    // product of a (flags: BLZ_SCAN_EXCLUSIVE), d_total (nullable) = the fold of all n elements
+    void vec_reduce(blz_fold_op op, const blz_vec_arg* a, const blz_vec_arg* b, void* d_out) {
+        check(blz_ntt_vec_reduce(h_, (int)op, a, b, d_out));
+    }
+    void vec_scan(blz_scan_op op, uint32_t flags, size_t dst, const blz_vec_arg* a, void* d_total = nullptr) {
+        check(blz_ntt_vec_scan(h_, (int)op, flags, dst, a, d_total));
+    }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

@@ -434,6 +434,40 @@ typedef struct blz_vec_arg {
                             position p of the op reads element p & (count - 1).  d_ptr == NULL: 0 or n */
 } blz_vec_arg;
 int blz_ntt_vec_op(blz_ntt* h, int op, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c);
+/* Reductions and prefix scans on resident buffers: the folds ALONG the buffer that blz_ntt_vec_op, position by position,
+ * cannot express - a polynomial evaluated at a challenge point, an inner product, a sum check (one value out of a vector);
+ * the grand-product column Z[p + 1] = Z[p] num[p] / den[p], a lookup argument's running sums, the powers z^p (a running
+ * product or sum).  Over the handle's field, on the n = 2^log_size positions p = 0 .. n - 1.
+ *   Values: every input word is any 256-bit value and counts as its residue; every output word is canonical (< r),
+ *   little-endian.  Nothing is special-cased for zeros: a zero (or r, 2r ...) in a product scan makes every later position 0
+ *   (BLZ_VEC_INV, which maps 0 to 0, is the only op that treats zeros apart).
+ *   Operands: those of blz_ntt_vec_op, checked by the same code - a transform buffer, or `count` device words read at
+ *   p & (count - 1).  The ops see buffer POSITIONS: the handle's BLZ_NTT_BITREV_* flags and its coset shift play no part.
+ *   BLZ_FOLD_SUM takes no b.  BLZ_FOLD_EVAL takes the point z as b with d_ptr != NULL and count == 1; z stays on the device,
+ *   the host never reads it; 0^0 = 1, so z = 0 gives a[0].
+ *   Scan: inclusive dst[p] = a[0] o .. o a[p]; with BLZ_SCAN_EXCLUSIVE dst[0] = the identity (0 for SUM, 1 for PROD) and
+ *   dst[p] = a[0] o .. o a[p - 1].  dst is the transform buffer buf_dst and may be the buffer a names (in place).  Hence an
+ *   exclusive BLZ_SCAN_PROD of a one-word operand z writes the powers dst[p] = z^p.
+ *   d_out / d_total: 32 bytes of device memory on the handle's device, 16-byte aligned, checked like an operand's d_ptr,
+ *   not overlapping the words of a d_ptr operand, written only by the op.  d_total may be NULL; otherwise it receives the
+ *   fold of all n elements (the last inclusive value, whatever the flag).
+ *   Protocol: that of blz_ntt_vec_op.  Everything is checked before anything is enqueued; the op runs on the compute stream
+ *   and the call returns without waiting for the device; blz_ntt_wait_result finishes it, blz_ntt_last_kernel_ms then reports
+ *   it, blz_ntt_reset drops it.  While a scan is in flight buf_dst may not be read, written or exchanged.  A reduce writes no
+ *   transform buffer: the buffers it reads may be read but not written or exchanged, a buffer it does not name stays free.
+ *   While either is in flight blz_ntt_start_process, blz_ntt_set_coset, blz_ntt_vec_op, blz_ntt_vec_reduce and
+ *   blz_ntt_vec_scan are refused.  Memory behind d_ptr, d_out and d_total stays valid (d_ptr: unwritten) until
+ *   blz_ntt_wait_result returns.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing: null handle, unknown op, unknown flag bits, buf_dst > 1, a missing or surplus
+ *   operand, EVAL with b naming a transform buffer or with count != 1, null d_out, a d_out / d_total that is not such
+ *   memory or overlaps a d_ptr operand, and any operand error of blz_ntt_vec_op. */
+enum blz_fold_op { BLZ_FOLD_SUM = 0,    /* out = sum_p a[p]                              */
+                   BLZ_FOLD_DOT = 1,    /* out = sum_p a[p] * b[p]                       */
+                   BLZ_FOLD_EVAL = 2 }; /* out = sum_p a[p] * z^p, z = b (count must be 1; 0^0 = 1) */
+int blz_ntt_vec_reduce(blz_ntt* h, int op, const blz_vec_arg* a, const blz_vec_arg* b, void* d_out);
+enum blz_scan_op { BLZ_SCAN_SUM = 0, BLZ_SCAN_PROD = 1 };
+#define BLZ_SCAN_EXCLUSIVE 1u
+int blz_ntt_vec_scan(blz_ntt* h, int op, uint32_t flags, size_t buf_dst, const blz_vec_arg* a, void* d_total);
 /* NTTBanks::preprocess / postprocess (ntt_data.rs:80-156) as device permutations, for byte
  * compatibility with bank files of the FPGA flow; n = 2^log_size elements (log_size >= 10), 16 banks
  * contiguous (n/16 elements each); 2^27 uses the reference's 512 groups x 256 block pairs, smaller sizes

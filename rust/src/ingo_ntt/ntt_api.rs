@@ -142,6 +142,28 @@ impl NTTClient {
         check(blz_ntt_vec_op(self.h, op as std::os::raw::c_int, dst, &ra, p(&rb), p(&rc)))
     }
 
+    /// One value out of a vector (blaze_hip.h blz_ntt_vec_reduce): `d_out` (32 bytes of device memory) = sum a, sum a * b, or
+    /// sum a\[p\] z^p with z the one-word operand `b`, by `op` (`FoldOp`).  Enqueued like a transform: `wait_result` finishes it.
+    ///
+    /// # Safety
+    /// As for `vec_op`; `d_out` too stays allocated until `wait_result` (or `reset_engine`) returns.
+    pub unsafe fn vec_reduce(&self, op: FoldOp, a: VecOperand, b: Option<VecOperand>, d_out: *mut std::os::raw::c_void) -> Result<()> {
+        let (ra, rb) = (a.raw(), b.map(|v| v.raw()));
+        let pb = rb.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg);
+        check(blz_ntt_vec_reduce(self.h, op as std::os::raw::c_int, &ra, pb, d_out))
+    }
+
+    /// Prefix scan along the buffer (blz_ntt_vec_scan): transform buffer `dst`\[p\] = a\[0\] o .. o a\[p\], or with `exclusive`
+    /// the identity at p = 0 and a\[0\] o .. o a\[p - 1\] after it; `d_total` (null, or 32 bytes of device memory) = the fold of
+    /// all n elements.  `a` may name `dst`.
+    ///
+    /// # Safety
+    /// As for `vec_reduce`.
+    pub unsafe fn vec_scan(&self, op: ScanOp, exclusive: bool, dst: usize, a: VecOperand, d_total: *mut std::os::raw::c_void) -> Result<()> {
+        let ra = a.raw();
+        check(blz_ntt_vec_scan(self.h, op as std::os::raw::c_int, if exclusive { 1 } else { 0 }, dst, &ra, d_total))
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
@@ -157,6 +179,23 @@ pub enum VecOp {
     MulAdd = 3,
     MulSub = 4,
     Inv = 5,
+}
+
+/// `enum blz_fold_op`
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum FoldOp {
+    Sum = 0,
+    Dot = 1,
+    Eval = 2,
+}
+
+/// `enum blz_scan_op`
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum ScanOp {
+    Sum = 0,
+    Prod = 1,
 }
 
 /// An operand of `NTTClient::vec_op`: a transform buffer of the client (0 | 1), or `count` 32-byte device words (a power of two
