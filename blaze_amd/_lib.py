@@ -113,6 +113,7 @@ _SIGS = {
     "blz_ntt_vec_op": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg)]),
     "blz_ntt_vec_reduce": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.c_void_p]),
+    "blz_ntt_vec_horner": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_banks_preprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
     "blz_ntt_banks_postprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
     "blz_poseidon_new": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

@@ -767,6 +767,31 @@ int blz_ntt_vec_scan(blz_ntt* h, int op, uint32_t flags, size_t buf_dst, const b
     return BLZ_OK;
 }
 
+int blz_ntt_vec_horner(blz_ntt* h, uint32_t flags, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* z, void* d_total) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (flags & ~(BLZ_HORNER_EXCLUSIVE | BLZ_HORNER_REVERSE)) return fail(BLZ_ERR_INVALID_PARAM, "unknown weighted-scan flags 0x%x", flags);
+    if (buf_dst > 1) return fail(BLZ_ERR_INVALID_PARAM, "buf_dst must be 0 or 1");
+    if (!a || !z) return fail(BLZ_ERR_INVALID_PARAM, "a weighted scan takes operands a and z");
+    if (!z->d_ptr || z->count != 1)
+        return fail(BLZ_ERR_INVALID_PARAM, "a weighted scan takes the multiplier as one device word: z.d_ptr != NULL, z.count == 1");
+    BLZ_NTT_LIVE(h);
+    if (h->in_flight) return fail(BLZ_ERR_INVALID_PARAM, "a transform or an op on the buffers is already running; call wait_result first");
+    BLZ_TRY(use_device(h->device));
+    NttVecArg va{}, vz{};
+    uint32_t reads = 0;
+    BLZ_TRY(ntt_vec_operand(h, "a", a, va, reads));
+    BLZ_TRY(ntt_vec_operand(h, "z", z, vz, reads));
+    if (d_total) BLZ_TRY(ntt_fold_out(h, "d_total", d_total, a, z));
+    BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
+    BLZ_TRY(h->ops->vec_horner(h->stream, flags, h->buf[buf_dst].as<uint32_t>(), va, vz, 1ull << h->logn, (uint32_t*)d_total,
+                               h->scratch.as<uint32_t>()));
+    BLZ_HIP(hipEventRecord(h->ev1, h->stream), BLZ_ERR_UNKNOWN);
+    h->in_flight = true;
+    h->in_flight_buf = (int)buf_dst;
+    h->in_flight_reads = reads & ~(1u << buf_dst);
+    return BLZ_OK;
+}
+
 int blz_ntt_stream(blz_ntt* h, void** hip_stream, int* device_id) {
     if (!h || !hip_stream) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
     if (device_id) *device_id = h->device;

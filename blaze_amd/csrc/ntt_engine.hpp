@@ -110,6 +110,10 @@ struct NttFieldOps {
     // dst[e] = the running fold of a (enum blz_scan_op, flags: BLZ_SCAN_EXCLUSIVE); total (32 bytes, nullable) = the fold of all n.
     // dst may be a.p
     int (*vec_scan)(hipStream_t st, int op, uint32_t flags, uint32_t* dst, NttVecArg a, uint64_t n, uint32_t* total, uint32_t* ws);
+    // Weighted scan (blz_ntt_vec_horner; kernels and the workspace's layout: ntt_horner.hip.hpp): dst[p] = a[p] + z dst[p - 1],
+    // flags: BLZ_HORNER_EXCLUSIVE | BLZ_HORNER_REVERSE; z: one device word; total (32 bytes, nullable) = the last inclusive value.
+    // dst may be a.p
+    int (*vec_horner)(hipStream_t st, uint32_t flags, uint32_t* dst, NttVecArg a, NttVecArg z, uint64_t n, uint32_t* total, uint32_t* ws);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

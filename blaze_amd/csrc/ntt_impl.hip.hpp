@@ -6,6 +6,7 @@
 #include "ntt_rr.hip.hpp"
 #include "ntt_vec.hip.hpp"
 #include "ntt_fold.hip.hpp"
+#include "ntt_horner.hip.hpp"
 
 namespace blz {
 
@@ -516,6 +517,7 @@ NttFieldOps make_ntt_ops() {
     o.vec_op = &ntt_vec_op_t<Fr>;
     o.vec_reduce = &ntt_vec_reduce_t<Fr>;
     o.vec_scan = &ntt_vec_scan_t<Fr>;
+    o.vec_horner = &ntt_vec_horner_t<Fr>;
     return o;
 }
 

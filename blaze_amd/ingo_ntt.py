@@ -44,6 +44,7 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
     FOLD_SUM, FOLD_DOT, FOLD_EVAL = range(3)        # enum blz_fold_op
     SCAN_SUM, SCAN_PROD = range(2)                  # enum blz_scan_op
     SCAN_EXCLUSIVE = 1                              # BLZ_SCAN_EXCLUSIVE
+    HORNER_EXCLUSIVE, HORNER_REVERSE = 1, 2         # BLZ_HORNER_*
 
     def __init__(self, _ptype: NTT, dclient: DriverClient, log_size: int = NTT_LOG_SIZE, inverse: bool = False,
                  field: str = "BLS381", flags: int = 0, root: Optional[int] = None):
@@ -175,6 +176,24 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         check(lib().blz_ntt_vec_scan(self._h, int(op), self.SCAN_EXCLUSIVE if exclusive else 0, dst,
                                      None if va is None else C.byref(va), None if total is None else total.ptr))
         self._vec_keep = (a, total)
+
+    def vec_horner(self, dst: int, a, z: DeviceBuffer, exclusive: bool = False, reverse: bool = False,
+                   total: Optional[DeviceBuffer] = None) -> None:
+        """Weighted (Horner) scan along the buffer (blz_ntt_vec_horner): transform buffer `dst`[p] = a[p] + z dst[p - 1], with
+        reverse=True a[p] + z dst[p + 1]; exclusive=True shifts the result by one position and puts 0 at the open end.  z is a
+        one-word DeviceBuffer (scalar()); `a` may name `dst` (in place).  `total` (a 32-byte DeviceBuffer) receives the last
+        inclusive value - with reverse=True that is a(z).  Finished by wait_result()."""
+        va, vz = self._vec_arg(a), self._vec_arg(z)
+        flags = (self.HORNER_EXCLUSIVE if exclusive else 0) | (self.HORNER_REVERSE if reverse else 0)
+        check(lib().blz_ntt_vec_horner(self._h, flags, dst, None if va is None else C.byref(va), None if vz is None else C.byref(vz),
+                                       None if total is None else total.ptr))
+        self._vec_keep = (a, z, total)
+
+    def vec_divide(self, dst: int, a, z: DeviceBuffer, rem: Optional[DeviceBuffer] = None) -> None:
+        """Division by X - z: transform buffer `dst` = the n coefficients of the quotient of a(X) = sum a[p] X^p by X - z (the top
+        one is 0), `rem` (a 32-byte DeviceBuffer) = the remainder a(z).  A reverse, exclusive vec_horner."""
+        self.vec_horner(dst, a, z, exclusive=True, reverse=True, total=rem)
+        self._vec_keep = (a, z, rem)
 
     def scalar(self, value: int) -> DeviceBuffer:
         """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""

@@ -265,6 +265,14 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
     void vec_scan(blz_scan_op op, uint32_t flags, size_t dst, const blz_vec_arg* a, void* d_total = nullptr) {
         check(blz_ntt_vec_scan(h_, (int)op, flags, dst, a, d_total));
     }
+    // weighted scan (blz_ntt_vec_horner): buffer dst[p] = a[p] + z dst[p - 1] (flags: BLZ_HORNER_EXCLUSIVE | BLZ_HORNER_REVERSE), z one
+    // device word, d_total (nullable) = the last inclusive value.  vec_divide: dst = the quotient of a(X) by X - z, d_rem = a(z)
+    void vec_horner(uint32_t flags, size_t dst, const blz_vec_arg* a, const blz_vec_arg* z, void* d_total = nullptr) {
+        check(blz_ntt_vec_horner(h_, flags, dst, a, z, d_total));
+    }
+    void vec_divide(size_t dst, const blz_vec_arg* a, const blz_vec_arg* z, void* d_rem = nullptr) {
+        vec_horner(BLZ_HORNER_EXCLUSIVE | BLZ_HORNER_REVERSE, dst, a, z, d_rem);
+    }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

@@ -468,6 +468,32 @@ int blz_ntt_vec_reduce(blz_ntt* h, int op, const blz_vec_arg* a, const blz_vec_a
 enum blz_scan_op { BLZ_SCAN_SUM = 0, BLZ_SCAN_PROD = 1 };
 #define BLZ_SCAN_EXCLUSIVE 1u
 int blz_ntt_vec_scan(blz_ntt* h, int op, uint32_t flags, size_t buf_dst, const blz_vec_arg* a, void* d_total);
+/* Weighted (Horner) scan on resident buffers: the recurrence dst[p] = a[p] + z dst[p -+ 1] with a one-word multiplier z, in
+ * either direction, inclusive or exclusive - the half of a KZG-style opening that blz_ntt_vec_reduce(BLZ_FOLD_EVAL) leaves:
+ * the witness polynomial q(X) = (f(X) - f(z)) / (X - z) by synthetic division.  Over the handle's field, on the n = 2^log_size
+ * buffer POSITIONS (the BLZ_NTT_BITREV_* flags and the coset shift play no part).
+ *   flags 0                        dst[p] = a[p] + z dst[p - 1] = sum_{j <= p} a[j] z^(p - j)
+ *   BLZ_HORNER_EXCLUSIVE           dst[p] = sum_{j < p} a[j] z^(p - 1 - j), dst[0] = 0
+ *   BLZ_HORNER_REVERSE             dst[p] = a[p] + z dst[p + 1] = sum_{j >= p} a[j] z^(j - p)
+ *   BLZ_HORNER_REVERSE | EXCLUSIVE dst[p] = sum_{j > p} a[j] z^(j - p - 1), dst[n - 1] = 0: the n coefficients of the quotient
+ *                                  of a(X) by X - z (EXCLUSIVE alone: the same for a polynomial stored top coefficient first)
+ *   d_total (nullable) receives the last inclusive value whatever the flags: forward sum_j a[j] z^(n - 1 - j), reverse
+ *   sum_j a[j] z^j = a(z), the division's remainder.  0^0 = 1 and nothing is special-cased: with z = 0 the inclusive scan
+ *   copies a and the exclusive scan shifts it by one position; z = 1 gives prefix / suffix sums.
+ *   Values: every input word is any 256-bit value and counts as its residue; every output word is canonical, little-endian.
+ *   Operands: a as for blz_ntt_vec_op (a transform buffer, or `count` device words read at p & (count - 1)); dst is the
+ *   transform buffer buf_dst and may be the buffer a names.  z follows BLZ_FOLD_EVAL's rule: d_ptr != NULL, count == 1, and the
+ *   host never reads it.  d_total: as for blz_ntt_vec_scan, and off the words of a and of z.
+ *   Protocol: that of blz_ntt_vec_scan.  Everything is checked before anything is enqueued; the op runs on the compute stream and
+ *   the call returns; blz_ntt_wait_result finishes it, blz_ntt_last_kernel_ms then reports it, blz_ntt_reset drops it.  While it
+ *   is in flight buf_dst may not be read, written or exchanged, a buffer that is only read may be read, and
+ *   blz_ntt_start_process, blz_ntt_set_coset, blz_ntt_vec_op, blz_ntt_vec_reduce, blz_ntt_vec_scan and blz_ntt_vec_horner are
+ *   refused (as blz_ntt_vec_horner is while any of those is in flight).
+ *   BLZ_ERR_INVALID_PARAM, changing nothing: null handle, flag bits other than the two, buf_dst > 1, a null a or z, a z that
+ *   names a transform buffer or has count != 1, a bad d_total, and any operand error of blz_ntt_vec_op. */
+#define BLZ_HORNER_EXCLUSIVE 1u
+#define BLZ_HORNER_REVERSE   2u
+int blz_ntt_vec_horner(blz_ntt* h, uint32_t flags, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* z, void* d_total);
 /* NTTBanks::preprocess / postprocess (ntt_data.rs:80-156) as device permutations, for byte
  * compatibility with bank files of the FPGA flow; n = 2^log_size elements (log_size >= 10), 16 banks
  * contiguous (n/16 elements each); 2^27 uses the reference's 512 groups x 256 block pairs, smaller sizes

@@ -113,6 +113,7 @@ extern "C" {
     pub fn blz_ntt_vec_op(h: *mut BlzNtt, op: c_int, buf_dst: usize, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg) -> c_int;
     pub fn blz_ntt_vec_reduce(h: *mut BlzNtt, op: c_int, a: *const BlzVecArg, b: *const BlzVecArg, d_out: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_scan(h: *mut BlzNtt, op: c_int, flags: u32, buf_dst: usize, a: *const BlzVecArg, d_total: *mut c_void) -> c_int;
+    pub fn blz_ntt_vec_horner(h: *mut BlzNtt, flags: u32, buf_dst: usize, a: *const BlzVecArg, z: *const BlzVecArg, d_total: *mut c_void) -> c_int;
 
     // ---- Poseidon tree: PoseidonClient (ingo_hash::poseidon_api)
     pub fn blz_poseidon_new(device_id: c_int, field: c_int, out: *mut *mut BlzPoseidon) -> c_int;

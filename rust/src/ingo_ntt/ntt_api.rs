@@ -164,6 +164,29 @@ impl NTTClient {
         check(blz_ntt_vec_scan(self.h, op as std::os::raw::c_int, if exclusive { 1 } else { 0 }, dst, &ra, d_total))
     }
 
+    /// Weighted (Horner) scan along the buffer (blz_ntt_vec_horner): transform buffer `dst`\[p\] = a\[p\] + z dst\[p - 1\], with
+    /// `reverse` a\[p\] + z dst\[p + 1\]; `exclusive` shifts the result by one position and puts 0 at the open end.  `z` is one
+    /// device word (`VecOperand::Words { count: 1, .. }`); `d_total` (null, or 32 bytes of device memory) = the last inclusive
+    /// value, with `reverse` a(z).  `a` may name `dst`.
+    ///
+    /// # Safety
+    /// As for `vec_reduce`.
+    pub unsafe fn vec_horner(&self, exclusive: bool, reverse: bool, dst: usize, a: VecOperand, z: VecOperand,
+                             d_total: *mut std::os::raw::c_void) -> Result<()> {
+        let (ra, rz) = (a.raw(), z.raw());
+        let flags = (if exclusive { 1 } else { 0 }) | (if reverse { 2 } else { 0 });
+        check(blz_ntt_vec_horner(self.h, flags, dst, &ra, &rz, d_total))
+    }
+
+    /// Division by X - z: transform buffer `dst` = the n coefficients of the quotient of a(X) = sum a\[p\] X^p by X - z (the top
+    /// one is 0), `d_rem` (null, or 32 bytes of device memory) = the remainder a(z).  A reverse, exclusive `vec_horner`.
+    ///
+    /// # Safety
+    /// As for `vec_reduce`.
+    pub unsafe fn vec_divide(&self, dst: usize, a: VecOperand, z: VecOperand, d_rem: *mut std::os::raw::c_void) -> Result<()> {
+        self.vec_horner(true, true, dst, a, z, d_rem)
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
