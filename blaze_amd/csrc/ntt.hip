@@ -14,6 +14,7 @@
 // Data stay in plain canonical form; only twiddles are in Montgomery form (mont_mul(x, tR) = x t),
 // so there is no conversion pass.  Algorithmic traffic 2 x 4 GiB; this 3-pass form moves 3x that.
 #include <atomic>
+#include <initializer_list>
 #include <string>
 #include <thread>
 #include <vector>
@@ -235,7 +236,7 @@ int blz_ntt_new_ex3(int device_id, int field, int log_size, uint32_t flags, cons
     const int inverse = (flags & BLZ_NTT_INVERSE) ? 1 : 0;
     const NttFieldOps* ops = ntt_ops_for(field);
     if (!ops) return fail(BLZ_ERR_INVALID_PARAM, "unknown field %d", field);
-    if (log_size < 1 || log_size > 27) return fail(BLZ_ERR_INVALID_PARAM, "log_size %d out of range [1,27]", log_size);
+    if (log_size < 1 || log_size > NTT_MAX_LOG) return fail(BLZ_ERR_INVALID_PARAM, "log_size %d out of range [1,%d]", log_size, NTT_MAX_LOG);
     if (log_size > ops->two_adicity)
         return fail(BLZ_ERR_INVALID_PARAM, "log_size %d exceeds the two-adicity %d of the field", log_size, ops->two_adicity);
     BLZ_TRY(use_device(device_id));
@@ -636,44 +637,91 @@ int blz_ntt_reset(blz_ntt* h) {
     return BLZ_OK;
 }
 
-// Element-wise ops on the transform buffers (include/blaze_hip.h).  Everything is checked before anything is enqueued; the op
-// then runs like a transform: compute stream, ev0 .. ev1, finished by blz_ntt_wait_result.  The batch inversion's tile totals
-// live in `scratch`, which only a transform of this handle uses - and none can be in flight.
-static int ntt_vec_operand(blz_ntt* h, const char* name, const blz_vec_arg* v, NttVecArg& out, uint32_t& reads) {
+// Ops on the transform buffers (include/blaze_hip.h: blz_ntt_vec_op, _reduce, _scan, _horner; kernels and their workspace:
+// ntt_vec.hip.hpp, ntt_fold.hip.hpp, ntt_horner.hip.hpp).  An op runs like a transform: compute stream, ev0 .. ev1, finished by
+// blz_ntt_wait_result.  Everything is checked before anything is enqueued and nothing waits for the device.  The workspace is
+// `scratch`, n x 32 bytes that only a transform or an op of this handle uses - and none can be in flight.  An entry point
+// checks its own arguments, then walks this protocol: begin, resolve, enqueue.
+extern "C++" {   // (enqueue is a template)
+struct NttVecCall {
+    blz_ntt* h;
     const uint64_t n = 1ull << h->logn;
-    if (v->reserved != 0) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: reserved must be 0", name);
-    if (!v->d_ptr) {
-        if (v->buf > 1) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: buf must be 0 or 1", name);
-        if (v->count != 0 && v->count != n)
-            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: a transform buffer holds %llu elements, count says %llu", name,
-                        (unsigned long long)n, (unsigned long long)v->count);
-        out = NttVecArg{h->buf[v->buf].as<uint32_t>(), n - 1};
-        reads |= 1u << v->buf;
+    uint32_t* const ws = h->scratch.as<uint32_t>();
+    uint32_t reads = 0;   // bit b = transform buffer b is an operand
+    struct Operand { const char* name; const blz_vec_arg* v; NttVecArg* out; };   // v == nullptr: the op does not take it
+
+    int begin() {
+        BLZ_NTT_LIVE(h);
+        if (h->in_flight) return fail(BLZ_ERR_INVALID_PARAM, "a transform or an op on the buffers is already running; call wait_result first");
+        return use_device(h->device);
+    }
+
+    int operand(const char* name, const blz_vec_arg* v, NttVecArg& out) {
+        if (v->reserved != 0) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: reserved must be 0", name);
+        if (!v->d_ptr) {
+            if (v->buf > 1) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: buf must be 0 or 1", name);
+            if (v->count != 0 && v->count != n)
+                return fail(BLZ_ERR_INVALID_PARAM, "operand %s: a transform buffer holds %llu elements, count says %llu", name,
+                            (unsigned long long)n, (unsigned long long)v->count);
+            out = NttVecArg{h->buf[v->buf].as<uint32_t>(), n - 1};
+            reads |= 1u << v->buf;
+            return BLZ_OK;
+        }
+        if (v->count == 0 || (v->count & (v->count - 1)) != 0 || v->count > n)
+            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: count %llu is not a power of two in [1, %llu]", name,
+                        (unsigned long long)v->count, (unsigned long long)n);
+        if (((uintptr_t)v->d_ptr & 15u) != 0) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not 16-byte aligned", name);
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, v->d_ptr) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not memory the runtime knows", name);
+        }
+        if (at.type != hipMemoryTypeDevice || at.device != h->device)
+            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not device memory of device %d", name, h->device);
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)v->d_ptr) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not inside a device allocation", name);
+        }
+        if ((const char*)v->d_ptr + v->count * 32 > (const char*)base + size)
+            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: %llu elements run past the end of the allocation d_ptr points into", name,
+                        (unsigned long long)v->count);
+        out = NttVecArg{(const uint32_t*)v->d_ptr, v->count - 1};
         return BLZ_OK;
     }
-    if (v->count == 0 || (v->count & (v->count - 1)) != 0 || v->count > n)
-        return fail(BLZ_ERR_INVALID_PARAM, "operand %s: count %llu is not a power of two in [1, %llu]", name,
-                    (unsigned long long)v->count, (unsigned long long)n);
-    if (((uintptr_t)v->d_ptr & 15u) != 0) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not 16-byte aligned", name);
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, v->d_ptr) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not memory the runtime knows", name);
+
+    // The operands in order, then the one-word output (d_out / d_total; nullptr: none): 32 bytes checked like an operand's
+    // d_ptr, and kept off the words of every d_ptr operand.
+    int resolve(std::initializer_list<Operand> ops, const char* out_name = nullptr, void* d_out = nullptr) {
+        for (const Operand& o : ops)
+            if (o.v) BLZ_TRY(operand(o.name, o.v, *o.out));
+        if (!d_out) return BLZ_OK;
+        const blz_vec_arg as_arg{d_out, 0u, 0u, 1u};
+        NttVecArg unused{};
+        BLZ_TRY(operand(out_name, &as_arg, unused));
+        for (const Operand& o : ops) {
+            if (!o.v || !o.v->d_ptr) continue;
+            const char *lo = (const char*)o.v->d_ptr, *hi = lo + o.v->count * 32, *q = (const char*)d_out;
+            if (q < hi && q + 32 > lo) return fail(BLZ_ERR_INVALID_PARAM, "%s overlaps the words of a d_ptr operand", out_name);
+        }
+        return BLZ_OK;
     }
-    if (at.type != hipMemoryTypeDevice || at.device != h->device)
-        return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not device memory of device %d", name, h->device);
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)v->d_ptr) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not inside a device allocation", name);
+
+    // buf_dst: the transform buffer the op writes (dispatch is handed its words), -1: none
+    template <class Dispatch>
+    int enqueue(int buf_dst, Dispatch&& dispatch) {
+        BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
+        BLZ_TRY(dispatch(buf_dst < 0 ? nullptr : h->buf[buf_dst].as<uint32_t>()));
+        BLZ_HIP(hipEventRecord(h->ev1, h->stream), BLZ_ERR_UNKNOWN);
+        h->in_flight = true;
+        h->in_flight_buf = buf_dst;
+        // read-ONLY buffers: the written one is in_flight_buf's to refuse; a reduce writes none and keeps all its read bits
+        h->in_flight_reads = buf_dst < 0 ? reads : reads & ~(1u << buf_dst);
+        return BLZ_OK;
     }
-    if ((const char*)v->d_ptr + v->count * 32 > (const char*)base + size)
-        return fail(BLZ_ERR_INVALID_PARAM, "operand %s: %llu elements run past the end of the allocation d_ptr points into", name,
-                    (unsigned long long)v->count);
-    out = NttVecArg{(const uint32_t*)v->d_ptr, v->count - 1};
-    return BLZ_OK;
-}
+};
+}  // extern "C++"
 
 int blz_ntt_vec_op(blz_ntt* h, int op, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c) {
     if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
@@ -683,39 +731,13 @@ int blz_ntt_vec_op(blz_ntt* h, int op, size_t buf_dst, const blz_vec_arg* a, con
     if (!a || (b != nullptr) != takes_b || (c != nullptr) != takes_c)
         return fail(BLZ_ERR_INVALID_PARAM, "element-wise op %d takes operands a%s%s, and the others must be NULL", op, takes_b ? ", b" : "",
                     takes_c ? ", c" : "");
-    BLZ_NTT_LIVE(h);
-    if (h->in_flight) return fail(BLZ_ERR_INVALID_PARAM, "a transform or an element-wise op is already running; call wait_result first");
-    BLZ_TRY(use_device(h->device));
+    NttVecCall call{h};
+    BLZ_TRY(call.begin());
     NttVecArg va{}, vb{}, vc{};
-    uint32_t reads = 0;
-    BLZ_TRY(ntt_vec_operand(h, "a", a, va, reads));
-    if (takes_b) BLZ_TRY(ntt_vec_operand(h, "b", b, vb, reads));
-    if (takes_c) BLZ_TRY(ntt_vec_operand(h, "c", c, vc, reads));
-    BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
-    BLZ_TRY(h->ops->vec_op(h->stream, op, h->buf[buf_dst].as<uint32_t>(), va, takes_b ? vb : va, takes_c ? vc : va, 1ull << h->logn,
-                           h->scratch.as<uint32_t>()));
-    BLZ_HIP(hipEventRecord(h->ev1, h->stream), BLZ_ERR_UNKNOWN);
-    h->in_flight = true;
-    h->in_flight_buf = (int)buf_dst;
-    h->in_flight_reads = reads & ~(1u << buf_dst);
-    return BLZ_OK;
-}
-
-// Folds along the buffer (include/blaze_hip.h; kernels and the workspace's layout: ntt_fold.hip.hpp).  The protocol of
-// blz_ntt_vec_op: everything is checked before anything is enqueued, nothing waits for the device, and the workspace is
-// `scratch` - n x 32 bytes that only an op of this handle uses, and none can be in flight.
-// d_out / d_total: 32 bytes checked like an operand's d_ptr (a one-word operand), and kept off the words of every d_ptr operand
-static int ntt_fold_out(blz_ntt* h, const char* name, void* p, const blz_vec_arg* a, const blz_vec_arg* b) {
-    const blz_vec_arg as_arg{p, 0u, 0u, 1u};
-    NttVecArg unused{};
-    uint32_t reads = 0;
-    BLZ_TRY(ntt_vec_operand(h, name, &as_arg, unused, reads));
-    for (const blz_vec_arg* v : {a, b}) {
-        if (!v || !v->d_ptr) continue;
-        const char *lo = (const char*)v->d_ptr, *hi = lo + v->count * 32, *q = (const char*)p;
-        if (q < hi && q + 32 > lo) return fail(BLZ_ERR_INVALID_PARAM, "%s overlaps the words of a d_ptr operand", name);
-    }
-    return BLZ_OK;
+    BLZ_TRY(call.resolve({{"a", a, &va}, {"b", b, &vb}, {"c", c, &vc}}));
+    return call.enqueue((int)buf_dst, [&](uint32_t* dst) {
+        return h->ops->vec_op(h->stream, op, dst, va, takes_b ? vb : va, takes_c ? vc : va, call.n, call.ws);
+    });
 }
 
 int blz_ntt_vec_reduce(blz_ntt* h, int op, const blz_vec_arg* a, const blz_vec_arg* b, void* d_out) {
@@ -727,21 +749,11 @@ int blz_ntt_vec_reduce(blz_ntt* h, int op, const blz_vec_arg* a, const blz_vec_a
     if (op == BLZ_FOLD_EVAL && (!b->d_ptr || b->count != 1))
         return fail(BLZ_ERR_INVALID_PARAM, "BLZ_FOLD_EVAL takes the point as one device word: b.d_ptr != NULL, b.count == 1");
     if (!d_out) return fail(BLZ_ERR_INVALID_PARAM, "null d_out");
-    BLZ_NTT_LIVE(h);
-    if (h->in_flight) return fail(BLZ_ERR_INVALID_PARAM, "a transform or an op on the buffers is already running; call wait_result first");
-    BLZ_TRY(use_device(h->device));
+    NttVecCall call{h};
+    BLZ_TRY(call.begin());
     NttVecArg va{}, vb{};
-    uint32_t reads = 0;
-    BLZ_TRY(ntt_vec_operand(h, "a", a, va, reads));
-    if (takes_b) BLZ_TRY(ntt_vec_operand(h, "b", b, vb, reads));
-    BLZ_TRY(ntt_fold_out(h, "d_out", d_out, a, b));
-    BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
-    BLZ_TRY(h->ops->vec_reduce(h->stream, op, (uint32_t*)d_out, va, takes_b ? vb : va, 1ull << h->logn, h->scratch.as<uint32_t>()));
-    BLZ_HIP(hipEventRecord(h->ev1, h->stream), BLZ_ERR_UNKNOWN);
-    h->in_flight = true;
-    h->in_flight_buf = -1;   // no transform buffer is written
-    h->in_flight_reads = reads;
-    return BLZ_OK;
+    BLZ_TRY(call.resolve({{"a", a, &va}, {"b", b, &vb}}, "d_out", d_out));
+    return call.enqueue(-1, [&](uint32_t*) { return h->ops->vec_reduce(h->stream, op, (uint32_t*)d_out, va, takes_b ? vb : va, call.n, call.ws); });
 }
 
 int blz_ntt_vec_scan(blz_ntt* h, int op, uint32_t flags, size_t buf_dst, const blz_vec_arg* a, void* d_total) {
@@ -750,21 +762,11 @@ int blz_ntt_vec_scan(blz_ntt* h, int op, uint32_t flags, size_t buf_dst, const b
     if (flags & ~BLZ_SCAN_EXCLUSIVE) return fail(BLZ_ERR_INVALID_PARAM, "unknown scan flags 0x%x", flags);
     if (buf_dst > 1) return fail(BLZ_ERR_INVALID_PARAM, "buf_dst must be 0 or 1");
     if (!a) return fail(BLZ_ERR_INVALID_PARAM, "a scan takes operand a");
-    BLZ_NTT_LIVE(h);
-    if (h->in_flight) return fail(BLZ_ERR_INVALID_PARAM, "a transform or an op on the buffers is already running; call wait_result first");
-    BLZ_TRY(use_device(h->device));
+    NttVecCall call{h};
+    BLZ_TRY(call.begin());
     NttVecArg va{};
-    uint32_t reads = 0;
-    BLZ_TRY(ntt_vec_operand(h, "a", a, va, reads));
-    if (d_total) BLZ_TRY(ntt_fold_out(h, "d_total", d_total, a, nullptr));
-    BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
-    BLZ_TRY(h->ops->vec_scan(h->stream, op, flags, h->buf[buf_dst].as<uint32_t>(), va, 1ull << h->logn, (uint32_t*)d_total,
-                             h->scratch.as<uint32_t>()));
-    BLZ_HIP(hipEventRecord(h->ev1, h->stream), BLZ_ERR_UNKNOWN);
-    h->in_flight = true;
-    h->in_flight_buf = (int)buf_dst;
-    h->in_flight_reads = reads & ~(1u << buf_dst);
-    return BLZ_OK;
+    BLZ_TRY(call.resolve({{"a", a, &va}}, "d_total", d_total));
+    return call.enqueue((int)buf_dst, [&](uint32_t* dst) { return h->ops->vec_scan(h->stream, op, flags, dst, va, call.n, (uint32_t*)d_total, call.ws); });
 }
 
 int blz_ntt_vec_horner(blz_ntt* h, uint32_t flags, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* z, void* d_total) {
@@ -774,22 +776,11 @@ int blz_ntt_vec_horner(blz_ntt* h, uint32_t flags, size_t buf_dst, const blz_vec
     if (!a || !z) return fail(BLZ_ERR_INVALID_PARAM, "a weighted scan takes operands a and z");
     if (!z->d_ptr || z->count != 1)
         return fail(BLZ_ERR_INVALID_PARAM, "a weighted scan takes the multiplier as one device word: z.d_ptr != NULL, z.count == 1");
-    BLZ_NTT_LIVE(h);
-    if (h->in_flight) return fail(BLZ_ERR_INVALID_PARAM, "a transform or an op on the buffers is already running; call wait_result first");
-    BLZ_TRY(use_device(h->device));
+    NttVecCall call{h};
+    BLZ_TRY(call.begin());
     NttVecArg va{}, vz{};
-    uint32_t reads = 0;
-    BLZ_TRY(ntt_vec_operand(h, "a", a, va, reads));
-    BLZ_TRY(ntt_vec_operand(h, "z", z, vz, reads));
-    if (d_total) BLZ_TRY(ntt_fold_out(h, "d_total", d_total, a, z));
-    BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
-    BLZ_TRY(h->ops->vec_horner(h->stream, flags, h->buf[buf_dst].as<uint32_t>(), va, vz, 1ull << h->logn, (uint32_t*)d_total,
-                               h->scratch.as<uint32_t>()));
-    BLZ_HIP(hipEventRecord(h->ev1, h->stream), BLZ_ERR_UNKNOWN);
-    h->in_flight = true;
-    h->in_flight_buf = (int)buf_dst;
-    h->in_flight_reads = reads & ~(1u << buf_dst);
-    return BLZ_OK;
+    BLZ_TRY(call.resolve({{"a", a, &va}, {"z", z, &vz}}, "d_total", d_total));
+    return call.enqueue((int)buf_dst, [&](uint32_t* dst) { return h->ops->vec_horner(h->stream, flags, dst, va, vz, call.n, (uint32_t*)d_total, call.ws); });
 }
 
 int blz_ntt_stream(blz_ntt* h, void** hip_stream, int* device_id) {

@@ -68,6 +68,8 @@ struct NttGeom {
                      // index bitrev(p)): folded into the wire pass's loads / the last pass's stores
 };
 
+constexpr int NTT_MAX_LOG = 27;   // the largest log_size a handle accepts (blz_ntt_new*)
+
 // Element-wise ops on resident buffers (blz_ntt_vec_op; kernels: ntt_vec.hip.hpp).  An operand is `mask + 1` (a power of two)
 // 32-byte words at p; position e of the op reads word e & mask.
 struct NttVecArg {

@@ -20,10 +20,8 @@
 //   k_fold_scan_down  the tile again with a carry-in: the lane's running values, a 256-wide Kogge-Stone scan of the lanes' totals
 //                     in LDS (8 steps), the carry applied to the lane's four values.  Every lane reads what it owns before it
 //                     writes it, and owns it alone: dst may be the buffer a names.
-//   The totals are scanned (exclusively, in place) by the same two kernels, WIRE = false: at most 1024 totals by one block of
-//   k_fold_scan_down, more (n > 2^20: up to 2^17 totals at 2^27) by a second level - k_fold_scan_up over the totals, one block
-//   over the <= 128 second-level totals, k_fold_scan_down over the totals with those as carries.  No chain is longer than
-//   3 + 8 + 1 combines per level.
+//   The totals are scanned (exclusively, in place) by the same two kernels, WIRE = false, level by level: scan_ladder.  No
+//   chain is longer than 3 + 8 + 1 combines per level.
 //   PROD works in Montgomery form: a raw product chain would pick up a power of 1 / R that depends on the position.  Words are
 //   converted on load (mont(x, R^2) is below 2m for any 256-bit x); the way back costs one product per LANE, not per word: the
 //   lane's carry-in c R becomes c (a product by the integer 1) and mont(c, v R) = c v is plain already; totals stay in
@@ -33,9 +31,10 @@
 //
 // WORKSPACE: the handle's `scratch`, n x 32 bytes, n = 2^logn, logn >= 1.
 //   reduce: blocks = min(ceil(n / 256), 2048) partials.  ceil(n / 256) <= n for every n >= 1.
-//   scan:   n <= 1024: none (one block, no carry).  Else T = n / 1024 totals, and for T > 1024 (n >= 2^21) T / 1024 second-level
-//           totals behind them: T + T / 1024 = n / 2^10 + n / 2^20 < n.
+//   scan:   scan_plan lays it out, scan_ws_words counts it, and a static_assert holds it within n words.
 #pragma once
+#include <type_traits>
+
 #include "ntt_vec.hip.hpp"
 
 namespace blz {
@@ -49,33 +48,27 @@ static_assert(VEC_THREADS == 1 << FOLD_LOG_THREADS, "the powers of z are indexed
 constexpr int FOLD_POWERS = 20;   // z^(2^i), i < 20: the largest is the stride of 2048 blocks x 256 lanes
 static_assert(VEC_MAX_BLOCKS * VEC_THREADS == 1u << (FOLD_POWERS - 1), "z^S of the widest grid is the last power");
 
-BLZ_DEV void fold_copy32(uint32_t* dst, const uint32_t* src) {   // 32 bytes by two lanes, 16 each
-    if (threadIdx.x < 2) reinterpret_cast<uint4*>(dst)[threadIdx.x] = reinterpret_cast<const uint4*>(src)[threadIdx.x];
-}
-
-// pw[i] = z^(2^i) in Montgomery form, i < FOLD_POWERS (LDS); every lane calls it, lane 0 squares
+// ---- what the blocks of a fold, a scan and a weighted scan share
+// pw[i] = z^(2^i) in Montgomery form, i < npow: the squaring chain; ONE lane calls it
 template <class Fr>
-BLZ_DEV void fold_powers(uint32_t* pw, const uint32_t* z) {
-    if (threadIdx.x == 0) {
-        Fp<Fr> p;
-        fp_load(p, z);
-        fp_to_mont(p, p);
-        fp_store(pw, p);
+BLZ_DEV void fold_square_chain(uint32_t* pw, const uint32_t* z, int npow) {
+    Fp<Fr> p;
+    fp_load(p, z);
+    fp_to_mont(p, p);
+    fp_store(pw, p);
 #pragma unroll 1
-        for (int i = 1; i < FOLD_POWERS; ++i) {
-            fp_sqr(p, p);
-            fp_store(pw + i * 8, p);
-        }
+    for (int i = 1; i < npow; ++i) {
+        fp_sqr(p, p);
+        fp_store(pw + i * 8, p);
     }
-    __syncthreads();
 }
 
-// the block's accumulators -> x[0] in LDS.  EVAL: x[t] += z^(w 2^base) x[t + w], so x[0] = sum_t (z^(2^base))^t acc_t
-template <class Fr, bool EVAL>
-BLZ_DEV void fold_tree(uint32_t* x, const uint32_t* pw, int base, const Fp<Fr>& acc) {
+// The lanes' 256 values -> x[0] in LDS: x[t] = combine(x[t], x[t + w], log2 w) for w = 128 .. 1.  Every lane calls it.
+template <class Fr, class Combine>
+BLZ_DEV void fold_block_tree(uint32_t* x, const Fp<Fr>& v, Combine&& combine) {
     using E = Fp<Fr>;
     const uint32_t t = threadIdx.x;
-    fp_store(x + t * 8, acc);
+    fp_store(x + t * 8, v);
     __syncthreads();
     int lw = FOLD_LOG_THREADS - 1;
 #pragma unroll 1
@@ -84,16 +77,31 @@ BLZ_DEV void fold_tree(uint32_t* x, const uint32_t* pw, int base, const Fp<Fr>& 
             E l, r;
             fp_load(l, x + t * 8);
             fp_load(r, x + (t + w) * 8);
-            if constexpr (EVAL) {
-                E zw;
-                fp_load(zw, pw + (base + lw) * 8);
-                fp_mul(r, r, zw);
-            }
-            fp_add(l, l, r);
+            combine(l, r, lw);
             fp_store(x + t * 8, l);
         }
         __syncthreads();
     }
+}
+
+// pw[i] = z^(2^i) in Montgomery form, i < FOLD_POWERS (LDS); every lane calls it, lane 0 squares
+template <class Fr>
+BLZ_DEV void fold_powers(uint32_t* pw, const uint32_t* z) {
+    if (threadIdx.x == 0) fold_square_chain<Fr>(pw, z, FOLD_POWERS);
+    __syncthreads();
+}
+
+// the block's accumulators -> x[0] in LDS.  EVAL: x[t] += z^(w 2^base) x[t + w], so x[0] = sum_t (z^(2^base))^t acc_t
+template <class Fr, bool EVAL>
+BLZ_DEV void fold_tree(uint32_t* x, const uint32_t* pw, int base, const Fp<Fr>& acc) {
+    fold_block_tree<Fr>(x, acc, [&](Fp<Fr>& l, Fp<Fr>& r, int lw) {
+        if constexpr (EVAL) {
+            Fp<Fr> zw;
+            fp_load(zw, pw + (base + lw) * 8);
+            fp_mul(r, r, zw);
+        }
+        fp_add(l, l, r);
+    });
 }
 
 // partial[block] = the fold of the positions the block's lanes own (DOT: with the stray 1 / R; EVAL: short of the block's weight)
@@ -138,7 +146,7 @@ __global__ __launch_bounds__(VEC_THREADS) void k_fold_part(uint32_t* partial, Nt
         }
     }
     fold_tree<Fr, OP == FOLD_EVAL>(x, pw, 0, acc);
-    fold_copy32(partial + (size_t)blockIdx.x * 8, x);
+    vec_copy32(partial + (size_t)blockIdx.x * 8, x);
 }
 
 // out = the fold of `count` partials (a power of two, <= VEC_MAX_BLOCKS), canonical; one block
@@ -226,20 +234,8 @@ __global__ __launch_bounds__(VEC_THREADS) void k_fold_scan_up(uint32_t* totals, 
     scan_load<Fr, OP, WIRE>(v, a, (uint64_t)blockIdx.x * NTT_FOLD_TILE + (uint64_t)t * FOLD_PER_LANE, count);
 #pragma unroll
     for (int j = 1; j < FOLD_PER_LANE; ++j) scan_combine<Fr, OP>(v[0], v[0], v[j]);
-    fp_store(x + t * 8, v[0]);
-    __syncthreads();
-#pragma unroll 1
-    for (uint32_t w = VEC_THREADS / 2; w >= 1; w >>= 1) {
-        if (t < w) {
-            E l, r;
-            fp_load(l, x + t * 8);
-            fp_load(r, x + (t + w) * 8);
-            scan_combine<Fr, OP>(l, l, r);
-            fp_store(x + t * 8, l);
-        }
-        __syncthreads();
-    }
-    fold_copy32(totals + (size_t)blockIdx.x * 8, x);
+    fold_block_tree<Fr>(x, v[0], [](E& l, const E& r, int) { scan_combine<Fr, OP>(l, l, r); });
+    vec_copy32(totals + (size_t)blockIdx.x * 8, x);
 }
 
 // dst[e] = carry[tile] o a[tile's first] o .. o a[e] (exclusive: .. o a[e - 1]), e < count; carry == nullptr: the identity (the
@@ -273,13 +269,8 @@ __global__ __launch_bounds__(VEC_THREADS) void k_fold_scan_down(uint32_t* dst, N
     if (carry) fp_load(c, carry + (size_t)blockIdx.x * 8); else scan_identity<Fr, OP>(c);
     if (t > 0) fp_load(below, x + (t - 1) * 8); else scan_identity<Fr, OP>(below);
     scan_combine<Fr, OP>(c, c, below);
-    if constexpr (WIRE && OP == SCAN_PROD) {
-        // the way back from Montgomery form, once per lane: c / R times an element's v R is their plain product
-        E one;
-#pragma unroll
-        for (int k = 0; k < Fr::N; ++k) one.v[k] = k == 0 ? 1u : 0u;
-        fp_mul(c, c, one);
-    }
+    // the way back from Montgomery form, once per lane: c / R times an element's v R is their plain product
+    if constexpr (WIRE && OP == SCAN_PROD) vec_strip_mont(c);
     E last = c;   // the value before the lane's first element; then the inclusive value of each
 #pragma unroll
     for (int j = 0; j < FOLD_PER_LANE; ++j) {
@@ -322,28 +313,68 @@ int ntt_vec_reduce_t(hipStream_t st, int op, uint32_t* out, NttVecArg a, NttVecA
     return BLZ_OK;
 }
 
+// ---- the ladder of a tiled scan (the scans here, the weighted scans of ntt_horner.hip.hpp)
+// One tile: a single down launch.  More: up over the tiles, the totals scanned exclusively in place - by one block while they
+// fill one tile, else through a second level (n > 2^20; at most 128 totals of the totals at 2^27) -, down over the tiles with
+// the totals as carries.  scan_plan alone lays the workspace out: `tiles` totals, `tiles2` behind them, the op's own at `free`.
+struct ScanPlan {
+    uint64_t tiles = 1, tiles2 = 0, words = 0;   // tiles2 == 0: no second level; words: the 32-byte words the levels take
+    uint32_t *t1 = nullptr, *t2 = nullptr, *free = nullptr;
+};
+constexpr ScanPlan scan_plan(uint64_t n, uint32_t* ws) {   // ws == nullptr: the counts only
+    ScanPlan p;
+    p.tiles = (n + NTT_FOLD_TILE - 1) / NTT_FOLD_TILE;
+    if (p.tiles == 1) return p;   // one block, no carry, no workspace
+    p.tiles2 = p.tiles > NTT_FOLD_TILE ? (p.tiles + NTT_FOLD_TILE - 1) / NTT_FOLD_TILE : 0;
+    p.words = p.tiles + p.tiles2;
+    if (ws) p.t1 = ws, p.t2 = ws + p.tiles * 8, p.free = ws + p.words * 8;
+    return p;
+}
+// the words of workspace a scan of 2^logn elements takes (a weighted scan keeps logn powers of z at `free`): n exist
+constexpr uint64_t scan_ws_words(int logn, bool horner) {
+    const ScanPlan p = scan_plan(1ull << logn, nullptr);
+    return p.words + (horner && p.tiles > 1 ? (uint64_t)logn : 0);
+}
+constexpr bool scan_ws_fits(int logn) {   // ... for every size up to 2^logn, and one block scans the top level
+    return logn < 1 || (scan_ws_words(logn, true) <= 1ull << logn && scan_plan(1ull << logn, nullptr).tiles2 <= NTT_FOLD_TILE &&
+                        scan_ws_fits(logn - 1));
+}
+static_assert(scan_ws_fits(NTT_MAX_LOG), "the handle's scratch (n words) holds every level of a scan and a weighted scan's powers");
+
+struct ScanLevel {   // 0 = the wire (a -> dst), 1 = the totals, 2 = the totals of the totals (both in place)
+    int level; NttVecArg src; uint32_t* dst; uint64_t count;
+    dim3 grid() const { return dim3((unsigned)((count + NTT_FOLD_TILE - 1) / NTT_FOLD_TILE)); }   // a block per tile
+};
+// up(wire, level, totals): one total per tile of the level;  down(wire, level, carry): the level's scan, carry nullable.
+// `wire` is std::true_type at level 0 and std::false_type above: the kernels' WIRE.
+template <class Up, class Down>
+void scan_ladder(const ScanPlan& p, uint32_t* dst, NttVecArg a, uint64_t n, Up&& up, Down&& down) {
+    constexpr std::true_type wire{};
+    constexpr std::false_type totals{};
+    const uint32_t* const none = nullptr;
+    const ScanLevel l0{0, a, dst, n}, l1{1, {p.t1, ~0ull}, p.t1, p.tiles}, l2{2, {p.t2, ~0ull}, p.t2, p.tiles2};
+    if (p.tiles == 1) return down(wire, l0, none);
+    up(wire, l0, p.t1);
+    if (p.tiles2 != 0) {
+        up(totals, l1, p.t2);
+        down(totals, l2, none);
+    }
+    down(totals, l1, p.tiles2 != 0 ? (const uint32_t*)p.t2 : none);
+    down(wire, l0, (const uint32_t*)p.t1);
+}
+
 template <class Fr, int OP>
 void scan_launch(hipStream_t st, uint32_t* dst, NttVecArg a, uint64_t n, uint32_t exclusive, uint32_t* total, uint32_t* ws) {
-    const dim3 thr(VEC_THREADS), one(1);
-    const uint64_t tiles = (n + NTT_FOLD_TILE - 1) / NTT_FOLD_TILE;
-    if (tiles == 1) {
-        hipLaunchKernelGGL((k_fold_scan_down<Fr, OP, true>), one, thr, 0, st, dst, a, (const uint32_t*)nullptr, n, exclusive, total);
-        return;
-    }
-    uint32_t* const t1 = ws;   // `tiles` totals, then their exclusive scan in place
-    const NttVecArg a1{t1, ~0ull};
-    hipLaunchKernelGGL((k_fold_scan_up<Fr, OP, true>), dim3((unsigned)tiles), thr, 0, st, t1, a, n);
-    if (tiles <= NTT_FOLD_TILE) {
-        hipLaunchKernelGGL((k_fold_scan_down<Fr, OP, false>), one, thr, 0, st, t1, a1, (const uint32_t*)nullptr, tiles, 1u, (uint32_t*)nullptr);
-    } else {
-        const uint64_t tiles2 = (tiles + NTT_FOLD_TILE - 1) / NTT_FOLD_TILE;   // <= 128 at 2^27: one block scans them
-        uint32_t* const t2 = ws + tiles * 8;
-        const NttVecArg a2{t2, ~0ull};
-        hipLaunchKernelGGL((k_fold_scan_up<Fr, OP, false>), dim3((unsigned)tiles2), thr, 0, st, t2, a1, tiles);
-        hipLaunchKernelGGL((k_fold_scan_down<Fr, OP, false>), one, thr, 0, st, t2, a2, (const uint32_t*)nullptr, tiles2, 1u, (uint32_t*)nullptr);
-        hipLaunchKernelGGL((k_fold_scan_down<Fr, OP, false>), dim3((unsigned)tiles2), thr, 0, st, t1, a1, (const uint32_t*)t2, tiles, 1u, (uint32_t*)nullptr);
-    }
-    hipLaunchKernelGGL((k_fold_scan_down<Fr, OP, true>), dim3((unsigned)tiles), thr, 0, st, dst, a, (const uint32_t*)t1, n, exclusive, total);
+    const dim3 thr(VEC_THREADS);
+    scan_ladder(
+        scan_plan(n, ws), dst, a, n,
+        [&](auto wire, const ScanLevel& l, uint32_t* totals) {
+            hipLaunchKernelGGL((k_fold_scan_up<Fr, OP, decltype(wire)::value>), l.grid(), thr, 0, st, totals, l.src, l.count);
+        },
+        [&](auto wire, const ScanLevel& l, const uint32_t* carry) {   // the levels above the wire: exclusive, no total
+            hipLaunchKernelGGL((k_fold_scan_down<Fr, OP, decltype(wire)::value>), l.grid(), thr, 0, st, l.dst, l.src, carry, l.count,
+                               l.level ? 1u : exclusive, l.level ? nullptr : total);
+        });
 }
 
 template <class Fr>

@@ -19,7 +19,7 @@
 //                  yields the four outputs with no per-position power.  Every lane reads what it owns before it writes it, and
 //                  owns it alone: dst may be the buffer a names, in both directions.
 //   Z = z^(2^base) is the level's multiplier: the tiles' totals obey the same recurrence with Z = z^1024 (exclusive, in place,
-//   WIRE = false), by one block for at most 1024 totals and by a second level (Z = z^(2^20)) from n = 2^21 on, as the scans do.
+//   WIRE = false) and theirs with Z = z^(2^20), along the scans' ladder (scan_ladder, ntt_fold.hip.hpp).
 //   Totals stay in logical order; REVERSE only mirrors the wire loads and stores (contiguous still, descending).
 //   A block scans only as many lanes as hold elements: ceil(log2(lanes)) Kogge-Stone steps.  The largest power any block reads
 //   is therefore z^(2^(logn - 1)) - in the one block over the top level's totals.
@@ -28,10 +28,8 @@
 //   occupies one (9 wave-products per tile, not 255 / 64), and so does the carry's product.
 //   Nothing is special-cased for zeros: 0^0 = 1 because position p's own term is never multiplied.
 //
-// WORKSPACE: the handle's `scratch`, n x 32 bytes, n = 2^logn, logn >= 1.
-//   n <= 1024: none (one block, no carry; lane 0 squares the <= 9 powers into LDS).
-//   n >= 2048: T = n / 2^10 totals, for n >= 2^21 T / 2^10 second-level totals behind them, then logn powers:
-//              n / 2^10 + n / 2^20 + logn <= n  (n = 2048: 2 + 0 + 11).
+// WORKSPACE: the handle's `scratch`.  n <= 1024: none (one block, no carry; lane 0 squares the <= 9 powers into LDS).  Else the
+//   scans' levels and, behind them, the logn powers: scan_plan and scan_ws_words (ntt_fold.hip.hpp), bounded there.
 #pragma once
 #include "ntt_fold.hip.hpp"
 
@@ -45,16 +43,7 @@ constexpr int HORNER_SLOTS = 1 + FOLD_LOG_THREADS;   // LDS: slot 0 = Z, slot 1 
 // pw[i] = z^(2^i) in Montgomery form, i < npow
 template <class Fr>
 __global__ __launch_bounds__(VEC_THREADS) void k_horner_pow(uint32_t* pw, const uint32_t* z, int npow) {
-    if (threadIdx.x != 0) return;
-    Fp<Fr> p;
-    fp_load(p, z);
-    fp_to_mont(p, p);
-    fp_store(pw, p);
-#pragma unroll 1
-    for (int i = 1; i < npow; ++i) {
-        fp_sqr(p, p);
-        fp_store(pw + i * 8, p);
-    }
+    if (threadIdx.x == 0) fold_square_chain<Fr>(pw, z, npow);
 }
 
 // The block's powers -> LDS: slot 0 = Z = z^(2^base), slot 1 + k = Z^(4 2^k) for k < ks.  pwg: k_horner_pow's table, or nullptr
@@ -128,22 +117,12 @@ __global__ __launch_bounds__(VEC_THREADS) void k_horner_up(uint32_t* totals, Ntt
 #pragma unroll
         for (int j = 1; j < FOLD_PER_LANE; ++j) horner_step<Fr>(v[0], z1, v[j]);
     }
-    fp_store(x + t * 8, v[0]);
-    __syncthreads();
-    int lw = FOLD_LOG_THREADS - 1;
-#pragma unroll 1
-    for (uint32_t w = VEC_THREADS / 2; w >= 1; w >>= 1, --lw) {
-        if (t < w) {
-            E l, r, zw;
-            fp_load(l, x + t * 8);
-            fp_load(r, x + (t + w) * 8);
-            fp_load(zw, pw + (1 + lw) * 8);   // the right half spans 4 w positions
-            horner_step<Fr>(l, zw, r);
-            fp_store(x + t * 8, l);
-        }
-        __syncthreads();
-    }
-    fold_copy32(totals + (size_t)blockIdx.x * 8, x);
+    fold_block_tree<Fr>(x, v[0], [&](E& l, const E& r, int lw) {
+        E zw;
+        fp_load(zw, pw + (1 + lw) * 8);   // the right half spans 4 w positions
+        horner_step<Fr>(l, zw, r);
+    });
+    vec_copy32(totals + (size_t)blockIdx.x * 8, x);
 }
 
 // dst[e] = carry[tile] Z^(e - tile's first + 1) + sum_{tile's first <= j <= e} a[j] Z^(e - j) (exclusive: the value of e - 1; the
@@ -221,34 +200,21 @@ __global__ __launch_bounds__(VEC_THREADS) void k_horner_down(uint32_t* dst, NttV
 
 template <class Fr>
 int ntt_vec_horner_t(hipStream_t st, uint32_t flags, uint32_t* dst, NttVecArg a, NttVecArg z, uint64_t n, uint32_t* total, uint32_t* ws) {
-    const dim3 thr(VEC_THREADS), one(1);
-    const uint32_t rev = flags & HORNER_REVERSE;
-    const uint32_t* const no_carry = nullptr;
-    uint32_t* const no_total = nullptr;
-    const uint64_t tiles = (n + NTT_FOLD_TILE - 1) / NTT_FOLD_TILE;
-    if (tiles == 1) {
-        hipLaunchKernelGGL((k_horner_down<Fr, true>), one, thr, 0, st, dst, a, no_carry, n, flags, total, z.p, no_carry, 0);
-    } else {
-        const uint64_t tiles2 = tiles > NTT_FOLD_TILE ? tiles / NTT_FOLD_TILE : 0;   // <= 128 at 2^27: one block scans them
-        uint32_t* const t1 = ws;                  // `tiles` totals, then their exclusive scan in place
-        uint32_t* const t2 = t1 + tiles * 8;      // `tiles2` totals of the totals, likewise
-        uint32_t* const pw = t2 + tiles2 * 8;     // z^(2^i), i < logn
-        const NttVecArg a1{t1, ~0ull}, a2{t2, ~0ull};
-        const uint32_t ex = HORNER_EXCLUSIVE;
-        const int l1 = HORNER_LOG_TILE, l2 = 2 * HORNER_LOG_TILE;
-        hipLaunchKernelGGL((k_horner_pow<Fr>), one, dim3(64), 0, st, pw, z.p, fold_log2(n));
-        hipLaunchKernelGGL((k_horner_up<Fr, true>), dim3((unsigned)tiles), thr, 0, st, t1, a, n, rev, (const uint32_t*)pw, 0);
-        if (tiles2 == 0) {
-            hipLaunchKernelGGL((k_horner_down<Fr, false>), one, thr, 0, st, t1, a1, no_carry, tiles, ex, no_total, z.p, (const uint32_t*)pw, l1);
-        } else {
-            hipLaunchKernelGGL((k_horner_up<Fr, false>), dim3((unsigned)tiles2), thr, 0, st, t2, a1, tiles, 0u, (const uint32_t*)pw, l1);
-            hipLaunchKernelGGL((k_horner_down<Fr, false>), one, thr, 0, st, t2, a2, no_carry, tiles2, ex, no_total, z.p, (const uint32_t*)pw, l2);
-            hipLaunchKernelGGL((k_horner_down<Fr, false>), dim3((unsigned)tiles2), thr, 0, st, t1, a1, (const uint32_t*)t2, tiles, ex, no_total,
-                               z.p, (const uint32_t*)pw, l1);
-        }
-        hipLaunchKernelGGL((k_horner_down<Fr, true>), dim3((unsigned)tiles), thr, 0, st, dst, a, (const uint32_t*)t1, n, flags, total, z.p,
-                           (const uint32_t*)pw, 0);
-    }
+    const dim3 thr(VEC_THREADS);
+    const ScanPlan p = scan_plan(n, ws);
+    const uint32_t* const pw = p.free;   // z^(2^i), i < logn, behind the levels; none for a single tile, which squares its own
+    if (pw) hipLaunchKernelGGL((k_horner_pow<Fr>), dim3(1), dim3(64), 0, st, p.free, z.p, fold_log2(n));
+    // level l runs on Z = z^(2^(10 l)); above the wire: forward, exclusive, no total
+    scan_ladder(
+        p, dst, a, n,
+        [&](auto wire, const ScanLevel& l, uint32_t* totals) {
+            hipLaunchKernelGGL((k_horner_up<Fr, decltype(wire)::value>), l.grid(), thr, 0, st, totals, l.src, l.count,
+                               l.level ? 0u : flags & HORNER_REVERSE, pw, l.level * HORNER_LOG_TILE);
+        },
+        [&](auto wire, const ScanLevel& l, const uint32_t* carry) {
+            hipLaunchKernelGGL((k_horner_down<Fr, decltype(wire)::value>), l.grid(), thr, 0, st, l.dst, l.src, carry, l.count,
+                               l.level ? (uint32_t)HORNER_EXCLUSIVE : flags, l.level ? nullptr : total, z.p, pw, l.level * HORNER_LOG_TILE);
+        });
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     return BLZ_OK;
 }

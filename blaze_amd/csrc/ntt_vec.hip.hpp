@@ -51,6 +51,18 @@ BLZ_DEV void vec_mul(Fp<P>& r, const Fp<P>& a, const Fp<P>& b) {
     fp_mul(r, a, bm);
 }
 
+// r = r / R: the product by the integer 1 strips one Montgomery factor
+template <class P>
+BLZ_DEV void vec_strip_mont(Fp<P>& r) {
+    const Fp<P> one{{1u}};
+    fp_mul(r, r, one);
+}
+
+// one 32-byte word between LDS and global memory by two lanes, 16 bytes each; every lane calls it
+BLZ_DEV void vec_copy32(uint32_t* dst, const uint32_t* src) {
+    if (threadIdx.x < 2) reinterpret_cast<uint4*>(dst)[threadIdx.x] = reinterpret_cast<const uint4*>(src)[threadIdx.x];
+}
+
 enum { VEC_ADD = 0, VEC_SUB = 1, VEC_MUL = 2, VEC_MULADD = 3, VEC_MULSUB = 4, VEC_INV = 5 };   // enum blz_vec_op
 
 // the five arithmetic ops: one element per lane per step, 2 x 16 bytes per operand, a wave touches 2 KiB contiguous
@@ -138,10 +150,7 @@ __global__ __launch_bounds__(VEC_THREADS) void k_vec_inv_up(uint32_t* totals, Nt
     __shared__ __attribute__((aligned(16))) uint32_t tree[2 * VEC_THREADS * 8];
     E x[VEC_INV_PER_LANE], pre[VEC_INV_PER_LANE];
     (void)vec_inv_climb<Fr, false>(tree, a, (uint64_t)blockIdx.x * NTT_VEC_INV_TILE, n, x, pre);
-    if (threadIdx.x < 2) {   // node 1, 32 bytes: two lanes, 16 bytes each
-        const uint4* s = reinterpret_cast<const uint4*>(vec_node(tree, 1));
-        reinterpret_cast<uint4*>(totals + (size_t)blockIdx.x * 8)[threadIdx.x] = s[threadIdx.x];
-    }
+    vec_copy32(totals + (size_t)blockIdx.x * 8, vec_node(tree, 1));
 }
 
 // m - 2, the exponent of Fermat's inversion
@@ -191,12 +200,10 @@ __global__ __launch_bounds__(VEC_THREADS) void k_vec_inv_mid(uint32_t* totals, u
             fp_mul(pre[k], pre[k - 1], tk);
         }
     }
-    E inv, one;
+    E inv;
     vec_inv_fermat(inv, pre[VEC_MID_GROUP - 1]);
-#pragma unroll
-    for (int k = 0; k < Fr::N; ++k) one.v[k] = k == 0 ? 1u : 0u;
-    fp_mul(inv, inv, one);
-    fp_mul(inv, inv, one);
+    vec_strip_mont(inv);
+    vec_strip_mont(inv);
 #pragma unroll
     for (int k = VEC_MID_GROUP - 1; k >= 1; --k) {
         if (k < cnt) {
@@ -219,7 +226,7 @@ __global__ __launch_bounds__(VEC_THREADS) void k_vec_inv_down(uint32_t* dst, con
     const uint64_t base = (uint64_t)blockIdx.x * NTT_VEC_INV_TILE;
     E x[VEC_INV_PER_LANE], pre[VEC_INV_PER_LANE];
     const uint32_t zero = vec_inv_climb<Fr, true>(tree, a, base, n, x, pre);
-    if (t < 2) reinterpret_cast<uint4*>(vec_node(inv, 1))[t] = reinterpret_cast<const uint4*>(totals + (size_t)blockIdx.x * 8)[t];
+    vec_copy32(vec_node(inv, 1), totals + (size_t)blockIdx.x * 8);
     __syncthreads();
     // root to leaves: the inverse of a node is the inverse of its parent times its sibling
     for (uint32_t w = 1; w <= VEC_THREADS / 2; w <<= 1) {

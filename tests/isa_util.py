@@ -8,6 +8,12 @@ import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _read(*parts):
+    """The text of a file of the repository, by its path from the root."""
+    return open(os.path.join(ROOT, *parts)).read()
 
 
 def tools_available() -> bool:
@@ -40,6 +46,13 @@ def kernel_vgprs(lib_path: str) -> dict:
     notes = disassemble_library(lib_path, "llvm-readelf", "--notes")
     # (a kernel's map is sorted by key: .name comes before .vgpr_count, and no other key of the map ends in 'name')
     return {n: int(v) for n, v in re.findall(r"^\s+\.name:\s+(\S+)\n(?:(?!\s+\.name:).*\n)*?\s+\.vgpr_count:\s+(\d+)", notes, re.M)}
+
+
+def kernel_scratch(lib_path: str) -> dict:
+    """{mangled kernel name: .private_segment_fixed_size}, from the same notes."""
+    notes = disassemble_library(lib_path, "llvm-readelf", "--notes")
+    return {n: int(v) for n, v in re.findall(
+        r"^\s+\.name:\s+(\S+)\n(?:(?!\s+\.name:).*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", notes, re.M)}
 
 
 def function_instructions(text: str, mangled: str):

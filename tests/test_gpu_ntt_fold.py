@@ -11,36 +11,14 @@ import pytest
 import blaze_amd
 from blaze_amd import DeviceBuffer, DriverClientError
 from blaze_amd._lib import BlzVecArg
-from blaze_amd.driver_client import DriverClient
-from blaze_amd.ingo_ntt import NTT, NTTClient, NTTInput, NttInit
+from blaze_amd.ingo_ntt import NTTClient, NTTInput
+from ntt_vec_util import FIELDS, GENERATOR, _client, _dev, _edges, _pack, _transform, _unpack, _word, _words
 from oracle import pyref
 
 pytestmark = pytest.mark.gpu
-FIELDS = ["BLS381", "BLS377", "BN254"]
-GENERATOR = {"BLS381": 7, "BLS377": 22, "BN254": 5}   # the fields' multiplicative generators
-TOP = (1 << 256) - 1
 TILE = 1024   # csrc/ntt_engine.hpp NTT_FOLD_TILE: positions per block of a scan
 SUM, DOT, EVAL = NTTClient.FOLD_SUM, NTTClient.FOLD_DOT, NTTClient.FOLD_EVAL
 SSUM, SPROD = NTTClient.SCAN_SUM, NTTClient.SCAN_PROD
-
-
-def _pack(vals):
-    return b"".join(v.to_bytes(32, "little") for v in vals)
-
-
-def _unpack(data):
-    data = bytes(data)
-    return [int.from_bytes(data[i: i + 32], "little") for i in range(0, len(data), 32)]
-
-
-def _words(seed, count):
-    """Random 256-bit words, no top-byte mask: more than half of them are >= r in every field."""
-    raw = random.Random(seed).randbytes(32 * count)
-    return [int.from_bytes(raw[i: i + 32], "little") for i in range(0, len(raw), 32)]
-
-
-def _edges(r):
-    return [0, 1, r - 1, r, r + 1, TOP]
 
 
 def _inputs(field, n, seed):
@@ -55,20 +33,6 @@ def _inputs(field, n, seed):
 
 def _nonzero(vals, r):
     return [v if v % r else 1 for v in vals]
-
-
-def _client(field, logn, **kw):
-    return NTTClient(NTT.Ntt, DriverClient(0), log_size=logn, field=field, **kw)
-
-
-def _dev(data):
-    d = DeviceBuffer(0, len(data))
-    d.upload(data)
-    return d
-
-
-def _word(d):
-    return int.from_bytes(bytes(d.download(32)), "little")
 
 
 def _reduce(cl, op, a, b=None, out=None):
@@ -244,12 +208,6 @@ def test_exclusive_product_scan_of_one_word_writes_its_powers(gpu, field):
     dz.free()
     total.free()
     cl.close()
-
-
-def _transform(cl, buf):
-    cl.initialize(NttInit())
-    cl.start_process(buf)
-    cl.wait_result()
 
 
 @pytest.mark.parametrize("field", ["BLS381", "BN254"])

@@ -12,32 +12,14 @@ import pytest
 import blaze_amd
 from blaze_amd import DeviceBuffer, DriverClientError
 from blaze_amd._lib import BlzVecArg
-from blaze_amd.driver_client import DriverClient
-from blaze_amd.ingo_ntt import NTT, NTTClient, NTTInput, NttInit
+from blaze_amd.ingo_ntt import NTTClient, NTTInput
+from ntt_vec_util import FIELDS, GENERATOR, TOP, _client, _dev, _pack, _transform, _unpack, _word, _words
 from oracle import pyref
 
 pytestmark = pytest.mark.gpu
-FIELDS = ["BLS381", "BLS377", "BN254"]
-GENERATOR = {"BLS381": 7, "BLS377": 22, "BN254": 5}   # the fields' multiplicative generators
-TOP = (1 << 256) - 1
 EX, REV = NTTClient.HORNER_EXCLUSIVE, NTTClient.HORNER_REVERSE
 EVAL, SSUM = NTTClient.FOLD_EVAL, NTTClient.SCAN_SUM
 MODES = [(False, False), (True, False), (False, True), (True, True)]   # (exclusive, reverse)
-
-
-def _pack(vals):
-    return b"".join(v.to_bytes(32, "little") for v in vals)
-
-
-def _unpack(data):
-    data = bytes(data)
-    return [int.from_bytes(data[i: i + 32], "little") for i in range(0, len(data), 32)]
-
-
-def _words(seed, count):
-    """Random 256-bit words, no top-byte mask: more than half of them are >= r in every field."""
-    raw = random.Random(seed).randbytes(32 * count)
-    return [int.from_bytes(raw[i: i + 32], "little") for i in range(0, len(raw), 32)]
 
 
 def _inputs(field, n, seed):
@@ -47,20 +29,6 @@ def _inputs(field, n, seed):
     for i, e in enumerate([0, 1, r - 1, r, r + 1, TOP][:n]):
         a[i] = e
     return a
-
-
-def _client(field, logn, **kw):
-    return NTTClient(NTT.Ntt, DriverClient(0), log_size=logn, field=field, **kw)
-
-
-def _dev(data):
-    d = DeviceBuffer(0, len(data))
-    d.upload(data)
-    return d
-
-
-def _word(d):
-    return int.from_bytes(bytes(d.download(32)), "little")
 
 
 def _want(a, z, r, exclusive, reverse):
@@ -226,12 +194,6 @@ def test_second_level_of_the_totals(gpu):
     cl.close()
     for d in (dz, total):
         d.free()
-
-
-def _transform(cl, buf):
-    cl.initialize(NttInit())
-    cl.start_process(buf)
-    cl.wait_result()
 
 
 @pytest.mark.parametrize("field", ["BLS381", "BN254"])

@@ -9,14 +9,11 @@ import pytest
 import blaze_amd
 from blaze_amd import DeviceBuffer, DriverClientError
 from blaze_amd._lib import BlzVecArg
-from blaze_amd.driver_client import DriverClient
-from blaze_amd.ingo_ntt import NTT, NTTClient, NTTInput, NttInit, VEC_INV_TILE
+from blaze_amd.ingo_ntt import NTTClient, NTTInput, VEC_INV_TILE
+from ntt_vec_util import FIELDS, GENERATOR, TOP, _client, _dev, _edges, _pack, _transform, _unpack, _words
 from oracle import pyref
 
 pytestmark = pytest.mark.gpu
-FIELDS = ["BLS381", "BLS377", "BN254"]
-GENERATOR = {"BLS381": 7, "BLS377": 22, "BN254": 5}   # the fields' multiplicative generators
-TOP = (1 << 256) - 1
 OPS = {
     NTTClient.ADD: lambda x, y, z, r: (x + y) % r,
     NTTClient.SUB: lambda x, y, z, r: (x - y) % r,
@@ -27,25 +24,6 @@ OPS = {
 TAKES_C = (NTTClient.MULADD, NTTClient.MULSUB)
 
 
-def _pack(vals):
-    return b"".join(v.to_bytes(32, "little") for v in vals)
-
-
-def _unpack(data):
-    data = bytes(data)
-    return [int.from_bytes(data[i: i + 32], "little") for i in range(0, len(data), 32)]
-
-
-def _words(seed, count):
-    """Random 256-bit words, no top-byte mask: more than half of them are >= r in every field."""
-    raw = random.Random(seed).randbytes(32 * count)
-    return [int.from_bytes(raw[i: i + 32], "little") for i in range(0, len(raw), 32)]
-
-
-def _edges(r):
-    return [0, 1, r - 1, r, r + 1, TOP]
-
-
 def _inputs(field, n, seed):
     """a, b, c: the 6 x 6 x 6 combinations of the edge words first (as far as n reaches), random 256-bit words behind them."""
     r = pyref.CURVES[field]["r"]
@@ -54,16 +32,6 @@ def _inputs(field, n, seed):
     for i in range(min(n, 216)):
         a[i], b[i], c[i] = e[i % 6], e[(i // 6) % 6], e[(i // 36) % 6]
     return a, b, c
-
-
-def _client(field, logn, **kw):
-    return NTTClient(NTT.Ntt, DriverClient(0), log_size=logn, field=field, **kw)
-
-
-def _dev(data):
-    d = DeviceBuffer(0, len(data))
-    d.upload(data)
-    return d
 
 
 def _run(cl, op, dst, a, b=None, c=None):
@@ -242,12 +210,6 @@ def test_batch_inverse_many_tiles(gpu, field, logn):
     assert max(y) < r
     bad = [p for p in range(n) if (x[p] * y[p] % r != 1 if x[p] % r else y[p] != 0)]
     assert not bad, (len(bad), bad[:8])
-
-
-def _transform(cl, buf):
-    cl.initialize(NttInit())
-    cl.start_process(buf)
-    cl.wait_result()
 
 
 @pytest.mark.parametrize("field", ["BLS381", "BN254"])

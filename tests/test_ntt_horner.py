@@ -9,17 +9,11 @@ import re
 import pytest
 
 import blaze_amd
-from isa_util import disassemble_library, kernel_vgprs, tools_available
+from isa_util import ROOT, _read, kernel_scratch, kernel_vgprs, tools_available
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 LIB = os.environ.get("BLAZE_HIP_LIB") or os.path.join(ROOT, "blaze_amd", "lib", "libblaze_hip.so")
 
 FIELDS = ("9Fr_BLS381", "9Fr_BLS377", "8Fr_BN254")
-
-
-def _read(*parts):
-    return open(os.path.join(ROOT, *parts)).read()
 
 
 def test_entry_point_in_every_layer():
@@ -61,10 +55,7 @@ def test_entry_point_in_every_layer():
 def code():
     if not tools_available():
         pytest.skip("ROCm LLVM tools not installed")
-    notes = disassemble_library(LIB, "llvm-readelf", "--notes")
-    scratch = {n: int(v) for n, v in re.findall(
-        r"^\s+\.name:\s+(\S+)\n(?:(?!\s+\.name:).*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", notes, re.M)}
-    return kernel_vgprs(LIB), scratch
+    return kernel_vgprs(LIB), kernel_scratch(LIB)
 
 
 def test_horner_kernels_stay_out_of_scratch_and_within_128_vgprs(code):

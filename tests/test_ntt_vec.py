@@ -10,20 +10,14 @@ import re
 import pytest
 
 import blaze_amd
-from isa_util import count, disassemble_library, function_instructions, kernel_vgprs, loops, tools_available
+from isa_util import ROOT, _read, count, disassemble_library, function_instructions, kernel_scratch, kernel_vgprs, loops, tools_available
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 LIB = os.environ.get("BLAZE_HIP_LIB") or os.path.join(ROOT, "blaze_amd", "lib", "libblaze_hip.so")
 
 FIELDS = ("9Fr_BLS381", "9Fr_BLS377", "8Fr_BN254")
 EW = "_ZN3blz8k_vec_ewINS_{f}ELi{op}EEEvPjNS_9NttVecArgES3_S3_m"
 NINV = "_ZN3blz10k_ntt_ninvINS_{f}EEEvPji"
 TOL = 8   # test_isa_counts.py's tolerance
-
-
-def _read(*parts):
-    return open(os.path.join(ROOT, *parts)).read()
 
 
 def test_entry_point_and_struct_in_every_layer():
@@ -69,10 +63,7 @@ def code():
     if not tools_available():
         pytest.skip("ROCm LLVM tools not installed")
     text = disassemble_library(LIB)
-    notes = disassemble_library(LIB, "llvm-readelf", "--notes")
-    scratch = {n: int(v) for n, v in re.findall(
-        r"^\s+\.name:\s+(\S+)\n(?:(?!\s+\.name:).*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", notes, re.M)}
-    return text, kernel_vgprs(LIB), scratch
+    return text, kernel_vgprs(LIB), kernel_scratch(LIB)
 
 
 def test_vec_kernels_stay_out_of_scratch_and_within_128_vgprs(code):
