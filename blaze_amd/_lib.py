@@ -39,6 +39,11 @@ class BlzVecArg(C.Structure):
     _fields_ = [("d_ptr", C.c_void_p), ("buf", C.c_uint32), ("reserved", C.c_uint32), ("count", C.c_uint64)]
 
 
+class BlzVecView(C.Structure):
+    """struct blz_vec_view (include/blaze_hip.h): the source positions blz_ntt_vec_gather reads."""
+    _fields_ = [("offset", C.c_uint64), ("stride", C.c_uint64), ("len", C.c_uint64)]
+
+
 # every exported symbol of include/blaze_hip.h: name -> (restype, argtypes)
 _u8p = C.c_void_p
 _SIGS = {
@@ -114,6 +119,7 @@ _SIGS = {
     "blz_ntt_vec_reduce": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_horner": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_void_p]),
+    "blz_ntt_vec_gather": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecView)]),
     "blz_ntt_banks_preprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
     "blz_ntt_banks_postprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
     "blz_poseidon_new": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

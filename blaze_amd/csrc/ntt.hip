@@ -637,8 +637,8 @@ int blz_ntt_reset(blz_ntt* h) {
     return BLZ_OK;
 }
 
-// Ops on the transform buffers (include/blaze_hip.h: blz_ntt_vec_op, _reduce, _scan, _horner; kernels and their workspace:
-// ntt_vec.hip.hpp, ntt_fold.hip.hpp, ntt_horner.hip.hpp).  An op runs like a transform: compute stream, ev0 .. ev1, finished by
+// Ops on the transform buffers (include/blaze_hip.h: blz_ntt_vec_op, _reduce, _scan, _horner, _gather; kernels and their workspace:
+// ntt_vec.hip.hpp, ntt_fold.hip.hpp, ntt_horner.hip.hpp, ntt_gather.hip.hpp).  An op runs like a transform: compute stream, ev0 .. ev1, finished by
 // blz_ntt_wait_result.  Everything is checked before anything is enqueued and nothing waits for the device.  The workspace is
 // `scratch`, n x 32 bytes that only a transform or an op of this handle uses - and none can be in flight.  An entry point
 // checks its own arguments, then walks this protocol: begin, resolve, enqueue.
@@ -648,7 +648,8 @@ struct NttVecCall {
     const uint64_t n = 1ull << h->logn;
     uint32_t* const ws = h->scratch.as<uint32_t>();
     uint32_t reads = 0;   // bit b = transform buffer b is an operand
-    struct Operand { const char* name; const blz_vec_arg* v; NttVecArg* out; };   // v == nullptr: the op does not take it
+    // v == nullptr: the op does not take it; max_count: the most device words it may hold, 0: the handle's n
+    struct Operand { const char* name; const blz_vec_arg* v; NttVecArg* out; uint64_t max_count = 0; };
 
     int begin() {
         BLZ_NTT_LIVE(h);
@@ -656,7 +657,7 @@ struct NttVecCall {
         return use_device(h->device);
     }
 
-    int operand(const char* name, const blz_vec_arg* v, NttVecArg& out) {
+    int operand(const char* name, const blz_vec_arg* v, NttVecArg& out, uint64_t max_count) {
         if (v->reserved != 0) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: reserved must be 0", name);
         if (!v->d_ptr) {
             if (v->buf > 1) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: buf must be 0 or 1", name);
@@ -667,9 +668,9 @@ struct NttVecCall {
             reads |= 1u << v->buf;
             return BLZ_OK;
         }
-        if (v->count == 0 || (v->count & (v->count - 1)) != 0 || v->count > n)
+        if (v->count == 0 || (v->count & (v->count - 1)) != 0 || v->count > max_count)
             return fail(BLZ_ERR_INVALID_PARAM, "operand %s: count %llu is not a power of two in [1, %llu]", name,
-                        (unsigned long long)v->count, (unsigned long long)n);
+                        (unsigned long long)v->count, (unsigned long long)max_count);
         if (((uintptr_t)v->d_ptr & 15u) != 0) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not 16-byte aligned", name);
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, v->d_ptr) != hipSuccess) {
@@ -695,11 +696,11 @@ struct NttVecCall {
     // d_ptr, and kept off the words of every d_ptr operand.
     int resolve(std::initializer_list<Operand> ops, const char* out_name = nullptr, void* d_out = nullptr) {
         for (const Operand& o : ops)
-            if (o.v) BLZ_TRY(operand(o.name, o.v, *o.out));
+            if (o.v) BLZ_TRY(operand(o.name, o.v, *o.out, o.max_count ? o.max_count : n));
         if (!d_out) return BLZ_OK;
         const blz_vec_arg as_arg{d_out, 0u, 0u, 1u};
         NttVecArg unused{};
-        BLZ_TRY(operand(out_name, &as_arg, unused));
+        BLZ_TRY(operand(out_name, &as_arg, unused, n));
         for (const Operand& o : ops) {
             if (!o.v || !o.v->d_ptr) continue;
             const char *lo = (const char*)o.v->d_ptr, *hi = lo + o.v->count * 32, *q = (const char*)d_out;
@@ -781,6 +782,31 @@ int blz_ntt_vec_horner(blz_ntt* h, uint32_t flags, size_t buf_dst, const blz_vec
     NttVecArg va{}, vz{};
     BLZ_TRY(call.resolve({{"a", a, &va}, {"z", z, &vz}}, "d_total", d_total));
     return call.enqueue((int)buf_dst, [&](uint32_t* dst) { return h->ops->vec_horner(h->stream, flags, dst, va, vz, call.n, (uint32_t*)d_total, call.ws); });
+}
+
+// In place (a's words overlap the destination buffer) a lane would overwrite what another still reads: the gather goes into
+// `scratch` and a copy on the same stream brings it back - twice the traffic, no allocation, the buffers stay where they are.
+int blz_ntt_vec_gather(blz_ntt* h, size_t buf_dst, const blz_vec_arg* a, const blz_vec_view* v) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (buf_dst > 1) return fail(BLZ_ERR_INVALID_PARAM, "buf_dst must be 0 or 1");
+    if (!a || !v) return fail(BLZ_ERR_INVALID_PARAM, "a gather takes operand a and a view");
+    NttVecCall call{h};
+    BLZ_TRY(call.begin());
+    NttVecArg va{};
+    BLZ_TRY(call.resolve({{"a", a, &va, 1ull << NTT_MAX_LOG}}));
+    const uint64_t count = va.mask + 1;
+    if (v->offset >= count)
+        return fail(BLZ_ERR_INVALID_PARAM, "view: offset %llu is not below the source's %llu elements", (unsigned long long)v->offset,
+                    (unsigned long long)count);
+    if (v->len > call.n)
+        return fail(BLZ_ERR_INVALID_PARAM, "view: len %llu is above the handle's %llu positions", (unsigned long long)v->len,
+                    (unsigned long long)call.n);
+    return call.enqueue((int)buf_dst, [&](uint32_t* dst) -> int {
+        const bool in_place = va.p < dst + call.n * 8 && dst < va.p + count * 8;
+        BLZ_TRY(h->ops->vec_gather(h->stream, in_place ? call.ws : dst, va, v->offset, v->stride & va.mask, v->len, call.n));
+        if (in_place) BLZ_HIP(hipMemcpyAsync(dst, call.ws, ntt_bytes(h), hipMemcpyDeviceToDevice, h->stream), BLZ_ERR_UNKNOWN);
+        return BLZ_OK;
+    });
 }
 
 int blz_ntt_stream(blz_ntt* h, void** hip_stream, int* device_id) {

@@ -116,6 +116,10 @@ struct NttFieldOps {
     // flags: BLZ_HORNER_EXCLUSIVE | BLZ_HORNER_REVERSE; z: one device word; total (32 bytes, nullable) = the last inclusive value.
     // dst may be a.p
     int (*vec_horner)(hipStream_t st, uint32_t flags, uint32_t* dst, NttVecArg a, NttVecArg z, uint64_t n, uint32_t* total, uint32_t* ws);
+    // Gather (blz_ntt_vec_gather; kernels: ntt_gather.hip.hpp): dst[p] = a[(offset + stride p) & a.mask] for p < len, 0 for
+    // len <= p < n; a may hold more than n words.  offset <= a.mask, stride reduced modulo a.mask + 1, len <= n.  dst must NOT
+    // overlap a's words
+    int (*vec_gather)(hipStream_t st, uint32_t* dst, NttVecArg a, uint64_t offset, uint64_t stride, uint64_t len, uint64_t n);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

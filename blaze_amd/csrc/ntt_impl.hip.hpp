@@ -7,6 +7,7 @@
 #include "ntt_vec.hip.hpp"
 #include "ntt_fold.hip.hpp"
 #include "ntt_horner.hip.hpp"
+#include "ntt_gather.hip.hpp"
 
 namespace blz {
 
@@ -518,6 +519,7 @@ NttFieldOps make_ntt_ops() {
     o.vec_reduce = &ntt_vec_reduce_t<Fr>;
     o.vec_scan = &ntt_vec_scan_t<Fr>;
     o.vec_horner = &ntt_vec_horner_t<Fr>;
+    o.vec_gather = &ntt_vec_gather_t<Fr>;
     return o;
 }
 

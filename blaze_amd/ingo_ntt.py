@@ -6,7 +6,7 @@ import enum
 from dataclasses import dataclass
 from typing import Optional
 
-from ._lib import BlzVecArg, DeviceBuffer, buf_ptr, check, lib
+from ._lib import BlzVecArg, BlzVecView, DeviceBuffer, buf_ptr, check, lib
 from .driver_client import DriverClient, DriverPrimitive
 
 NTT_LOG_SIZE = 27  # ntt_data.rs:65: NTT_SIZE = 2^27
@@ -194,6 +194,38 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         one is 0), `rem` (a 32-byte DeviceBuffer) = the remainder a(z).  A reverse, exclusive vec_horner."""
         self.vec_horner(dst, a, z, exclusive=True, reverse=True, total=rem)
         self._vec_keep = (a, z, rem)
+
+    def vec_gather(self, dst: int, a, offset: int = 0, stride: int = 1, length: Optional[int] = None) -> None:
+        """Gather along the buffer (blz_ntt_vec_gather): transform buffer `dst`[p] = a[(offset + stride p) mod count] for
+        p < length and 0 for length <= p < n.  `a` is a transform buffer (count = n; `dst` itself: in place, through the
+        client's scratch at twice the traffic) or a DeviceBuffer of count = nbytes / 32 words, a power of two that may exceed n
+        (up to 2^27).  A negative offset or stride is taken modulo count (stride -1 walks backwards); length=None means
+        min(count, n).  Every output word is canonical.  Finished by wait_result()."""
+        va = self._vec_arg(a)
+        n = 1 << self.log_size
+        count = n if va is None or not va.d_ptr else int(va.count)
+        m = count or 1   # (a count of 0 is the library's to refuse)
+        offset, stride = int(offset), int(stride)
+        view = BlzVecView(offset % m if offset < 0 else offset, stride % m if stride < 0 else stride,
+                          min(count, n) if length is None else int(length))
+        check(lib().blz_ntt_vec_gather(self._h, dst, None if va is None else C.byref(va), C.byref(view)))
+        self._vec_keep = (a,)
+
+    def vec_rotate(self, dst: int, a, k: int) -> None:
+        """Rotation: transform buffer `dst`[p] = a[(p + k) mod n], k of either sign - on the domain, rotating the values of
+        Z(X) by 1 gives those of Z(wX); on a 4n coset, by 4.  `a` is a transform buffer or a DeviceBuffer of n words.  A
+        vec_gather with stride 1."""
+        n = 1 << self.log_size
+        if isinstance(a, DeviceBuffer) and a.nbytes != self.nbytes:
+            raise ValueError(f"a rotation takes n = {n} words, the DeviceBuffer holds {a.nbytes // NTT_WORD_SIZE}")
+        self.vec_gather(dst, a, offset=int(k) % n, stride=1, length=n)
+        self._vec_keep = (a,)
+
+    def vec_extend(self, dst: int, a: DeviceBuffer) -> None:
+        """Low-degree extension: transform buffer `dst` = the m <= n words of the DeviceBuffer `a` (m a power of two) with
+        zeros above them - n coefficients into a 4n client.  A vec_gather with length = m."""
+        self.vec_gather(dst, a, offset=0, stride=1, length=a.nbytes // NTT_WORD_SIZE)
+        self._vec_keep = (a,)
 
     def scalar(self, value: int) -> DeviceBuffer:
         """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""

@@ -273,6 +273,20 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
     void vec_divide(size_t dst, const blz_vec_arg* a, const blz_vec_arg* z, void* d_rem = nullptr) {
         vec_horner(BLZ_HORNER_EXCLUSIVE | BLZ_HORNER_REVERSE, dst, a, z, d_rem);
     }
+    // gather (blz_ntt_vec_gather): buffer dst[p] = a[(offset + stride p) mod count] for p < len, 0 above; a may hold up to 2^27
+    // words, and may name dst (in place, through the handle's scratch at twice the traffic).  view(offset, stride, len) builds
+    // the struct.  vec_rotate: dst[p] = a[(p + k) mod n], k of either sign, a of n words.  vec_extend: dst = the count <= n
+    // device words at d_ptr, zero above
+    static blz_vec_view view(uint64_t offset, uint64_t stride, uint64_t len) { return blz_vec_view{offset, stride, len}; }
+    void vec_gather(size_t dst, const blz_vec_arg* a, const blz_vec_view& v) { check(blz_ntt_vec_gather(h_, dst, a, &v)); }
+    void vec_rotate(size_t dst, const blz_vec_arg* a, int64_t k) {
+        const int64_t n = int64_t(nbytes_ / 32);
+        vec_gather(dst, a, view(uint64_t(((k % n) + n) % n), 1, uint64_t(n)));
+    }
+    void vec_extend(size_t dst, const void* d_ptr, uint64_t count) {
+        const blz_vec_arg a = words(d_ptr, count);
+        vec_gather(dst, &a, view(0, 1, count));
+    }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

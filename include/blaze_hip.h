@@ -430,8 +430,9 @@ typedef struct blz_vec_arg {
     const void* d_ptr;   /* NULL: the handle's transform buffer `buf`; else device memory on the handle's device */
     uint32_t buf;        /* 0 | 1, read only when d_ptr == NULL */
     uint32_t reserved;   /* must be 0 */
-    uint64_t count;      /* d_ptr != NULL: number of 32-byte elements, a power of two, 1 <= count <= n;
-                            position p of the op reads element p & (count - 1).  d_ptr == NULL: 0 or n */
+    uint64_t count;      /* d_ptr != NULL: number of 32-byte elements, a power of two, 1 <= count <= n (the source of
+                            blz_ntt_vec_gather: <= 2^27); position p of the op reads element p & (count - 1).
+                            d_ptr == NULL: 0 or n */
 } blz_vec_arg;
 int blz_ntt_vec_op(blz_ntt* h, int op, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c);
 /* Reductions and prefix scans on resident buffers: the folds ALONG the buffer that blz_ntt_vec_op, position by position,
@@ -494,6 +495,40 @@ int blz_ntt_vec_scan(blz_ntt* h, int op, uint32_t flags, size_t buf_dst, const b
 #define BLZ_HORNER_EXCLUSIVE 1u
 #define BLZ_HORNER_REVERSE   2u
 int blz_ntt_vec_horner(blz_ntt* h, uint32_t flags, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* z, void* d_total);
+/* Gathers on resident buffers: the one op that moves an element to another POSITION, or between vectors of different length -
+ * what every other op, reading position p (or p & (count - 1)) and writing position p, cannot do.  With it the steps of a
+ * PLONK-style quotient stay on the device: Z(wX) next to Z(X) (a rotation by 1 on the domain, by 4 on the 4n coset), a
+ * low-degree extension (n coefficients into a 4n handle, zero above), the low n coefficients of a 4n result back into an n
+ * handle, the values on H out of the evaluations on the 4n domain (every 4th position).  Over the handle's field, by buffer
+ * POSITION (the BLZ_NTT_BITREV_* flags and the coset shift play no part), with n = 2^log_size:
+ *   dst[p] = a[(offset + stride p) mod count]   for p <  len
+ *   dst[p] = 0                                  for len <= p < n
+ *   Values: every source word is any 256-bit value and counts as its residue; every output word is canonical, little-endian:
+ *   a canonicalising copy.
+ *   Source a: a transform buffer (d_ptr == NULL, count 0 or n: count = n) or `count` device words, checked as for
+ *   blz_ntt_vec_op with ONE difference: count may exceed n, up to 2^27 (the largest log_size a handle accepts), so that a 4n
+ *   vector feeds an n handle.
+ *   Index: count is a power of two, so the index is (offset + stride * p) & (count - 1) in 64-bit arithmetic (the wrap at 2^64
+ *   is harmless) and nothing is special-cased: stride = count - 1 walks backwards (a reversal with offset = count - 1), stride
+ *   = 0 broadcasts one word, len > count tiles the source, an even stride reads some words more than once.  A stride that is 1
+ *   modulo count (rotation, extension, slice) reads the source contiguously apart from the wrap; any other stride reads it as
+ *   the memory system serves words `stride` apart.
+ *   In place: a may name buf_dst.  A gather cannot be done lane by lane, so it then goes through the handle's scratch (n x 32
+ *   bytes, nothing else is in flight) and is copied to the buffer on the same stream: twice the traffic of buffer 0 -> buffer
+ *   1.  Nothing is allocated and the buffers stay where they are.
+ *   Protocol: that of blz_ntt_vec_scan.  Everything is checked before anything is enqueued; the op runs on the compute stream and
+ *   the call returns without waiting for the device; blz_ntt_wait_result finishes it, blz_ntt_last_kernel_ms then reports it,
+ *   blz_ntt_reset drops it.  While it is in flight buf_dst may not be read, written or exchanged, a buffer that is only read
+ *   may be read, and every transform, blz_ntt_set_coset and op on the buffers is refused (as blz_ntt_vec_gather is while any
+ *   of those is in flight).  Memory behind d_ptr stays valid and unwritten until blz_ntt_wait_result returns.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing: null handle, null a or v, buf_dst > 1, offset >= count, len > n, and any operand
+ *   error of blz_ntt_vec_op (reserved != 0 among them) with the count bound raised to 2^27. */
+typedef struct blz_vec_view {
+    uint64_t offset;   /* source element that destination position 0 reads; offset < count */
+    uint64_t stride;   /* source step per destination position, taken modulo count */
+    uint64_t len;      /* positions p < len read the source, positions len <= p < n become 0; len <= n */
+} blz_vec_view;
+int blz_ntt_vec_gather(blz_ntt* h, size_t buf_dst, const blz_vec_arg* a, const blz_vec_view* v);
 /* NTTBanks::preprocess / postprocess (ntt_data.rs:80-156) as device permutations, for byte
  * compatibility with bank files of the FPGA flow; n = 2^log_size elements (log_size >= 10), 16 banks
  * contiguous (n/16 elements each); 2^27 uses the reference's 512 groups x 256 block pairs, smaller sizes

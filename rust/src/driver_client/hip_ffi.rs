@@ -27,6 +27,15 @@ pub struct BlzVecArg {
     pub reserved: u32,
     pub count: u64,
 }
+/// `struct blz_vec_view`: the source positions `blz_ntt_vec_gather` reads - destination position p < `len` takes source element
+/// (`offset` + `stride` p) mod count, positions from `len` up become 0.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct BlzVecView {
+    pub offset: u64,
+    pub stride: u64,
+    pub len: u64,
+}
 
 pub const BLZ_COMM_ID_BYTES: usize = 128;
 
@@ -114,6 +123,7 @@ extern "C" {
     pub fn blz_ntt_vec_reduce(h: *mut BlzNtt, op: c_int, a: *const BlzVecArg, b: *const BlzVecArg, d_out: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_scan(h: *mut BlzNtt, op: c_int, flags: u32, buf_dst: usize, a: *const BlzVecArg, d_total: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_horner(h: *mut BlzNtt, flags: u32, buf_dst: usize, a: *const BlzVecArg, z: *const BlzVecArg, d_total: *mut c_void) -> c_int;
+    pub fn blz_ntt_vec_gather(h: *mut BlzNtt, buf_dst: usize, a: *const BlzVecArg, v: *const BlzVecView) -> c_int;
 
     // ---- Poseidon tree: PoseidonClient (ingo_hash::poseidon_api)
     pub fn blz_poseidon_new(device_id: c_int, field: c_int, out: *mut *mut BlzPoseidon) -> c_int;

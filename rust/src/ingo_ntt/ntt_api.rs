@@ -187,6 +187,37 @@ impl NTTClient {
         self.vec_horner(true, true, dst, a, z, d_rem)
     }
 
+    /// Gather along the buffer (blz_ntt_vec_gather): transform buffer `dst`\[p\] = a\[(offset + stride p) mod count\] for
+    /// p < `len` and 0 for `len` <= p < n.  `a` is a transform buffer (count = n; `dst` itself: in place, through the client's
+    /// scratch at twice the traffic) or `count` device words, a power of two that may exceed n (up to 2^27).  `stride` is taken
+    /// modulo count: count - 1 walks backwards, 0 broadcasts one word.  Every output word is canonical.
+    ///
+    /// # Safety
+    /// As for `vec_op`.
+    pub unsafe fn vec_gather(&self, dst: usize, a: VecOperand, offset: u64, stride: u64, len: u64) -> Result<()> {
+        let (ra, view) = (a.raw(), BlzVecView { offset, stride, len });
+        check(blz_ntt_vec_gather(self.h, dst, &ra, &view))
+    }
+
+    /// Rotation: transform buffer `dst`\[p\] = a\[(p + k) mod n\], k of either sign; `a` holds n words.  On the domain,
+    /// rotating the values of Z(X) by 1 gives those of Z(wX); on a 4n coset, by 4.  A `vec_gather` with stride 1.
+    ///
+    /// # Safety
+    /// As for `vec_op`.
+    pub unsafe fn vec_rotate(&self, dst: usize, a: VecOperand, k: i64) -> Result<()> {
+        let n = (self.nbytes / NTT_WORD_SIZE) as u64;
+        self.vec_gather(dst, a, k.rem_euclid(n as i64) as u64, 1, n)
+    }
+
+    /// Low-degree extension: transform buffer `dst` = the `count` <= n device words at `d_ptr` with zeros above them (n
+    /// coefficients into a 4n client).  A `vec_gather` with len = count.
+    ///
+    /// # Safety
+    /// As for `vec_op`.
+    pub unsafe fn vec_extend(&self, dst: usize, d_ptr: *const std::os::raw::c_void, count: u64) -> Result<()> {
+        self.vec_gather(dst, VecOperand::Words { d_ptr, count }, 0, 1, count)
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
