@@ -776,12 +776,19 @@ size_t MsmEngine::table_scratch_bytes(int W) const { return msm_ops_for(curve, r
 
 // do the hidden sort's waves (sv VGPRs) fit on a SIMD beside the accumulation's (av VGPRs each, as many as fit)?  Measured: the
 // sort runs beside 2 x 200 + 72 = 472 registers and waits for the accumulation to END behind 2 x 208 + 72 = 488.
-static bool sort_fits_beside(int av, int sv) {
+// LDS (reasoned from the allocation rules, not measured like the register bound): the accumulation's blocks are 128 lanes, so `waves` of its waves per SIMD are 2 x waves blocks per CU; one block of the
+// sort has to fit in what they leave of the CU's 160 KiB (allocations taken in steps of 1 KiB).  A sort block that does not
+// fit is not an error either: it waits until the accumulation's blocks drain from a CU, that is for its end.
+bool msm_sort_fits_beside(int av, int sv, int al, int sl) {
+    if (av <= 0 || sv <= 0) return true;
     const int a = (av + 7) & ~7, s = (sv + 7) & ~7;
     int waves = 512 / a;
     if (waves > 4) waves = 4;
     if (waves < 1) waves = 1;
-    return waves * a + s <= 512 - 32;
+    if (waves * a + s > 512 - 32) return false;
+    if (al <= 0 || sl <= 0) return true;   // no LDS on one side (or not known): nothing to share
+    const int ak = (al + 1023) >> 10, sk = (sl + 1023) >> 10;
+    return 2 * waves * ak + sk <= 160;
 }
 
 static const int kScalarFieldBits[3] = {253, 255, 254};  // bit length of r (BLS12-377 / 381 / BN254)
@@ -878,10 +885,9 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
     const MsmSlot& O = slots[(slot + 1) % MSM_QUEUE_DEPTH];
     bool s3 = P.table || (hide_env != 0 && nslices == 1 && msm_sort3_ok(P, sbits));   // (a table task has no other sort)
     bool fits = true;
-    // (a build whose register counts cannot be read is taken to fit; k_accumulate_cont shares k_accumulate's register cap)
+    // (a build whose register and LDS counts cannot be read is taken to fit; k_accumulate_cont shares k_accumulate's register cap)
     auto sort_fits = [&](bool table) {
-        const int av = ops->accumulate_vgprs(), sv = msm_sort3_max_vgprs(table);
-        return !(av > 0 && sv > 0 && !sort_fits_beside(av, sv));
+        return msm_sort_fits_beside(ops->accumulate_vgprs(), msm_sort3_max_vgprs(table), ops->accumulate_lds(), msm_sort3_max_lds(table));
     };
     if (s3 && hide_env == 1 && !P.table) {
         // the three-level sort gives one block a whole level-2 bin: fine for the near-uniform digits of real scalars, a
@@ -899,6 +905,7 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
         // (the SIMD runs as many accumulation waves as their allocation admits: two of the reduced-radix kernels', three of
         // the 32-bit-limb kernel's, whose allocation is padded to 136 for exactly this purpose)
         // A table plan's largest kernel (k3t_l3<true>: 78 VGPRs, allocated as 80) fits with nothing to spare: 2 x 200 + 80 = 480.
+        // The same goes for LDS: the BLS accumulation's four blocks per CU hold 4 x 16 KiB, the sort's largest block 83 KiB.
         fits = sort_fits(P.table);
         if (!fits && !P.table) s3 = false;   // (a table task has no other sort: it then sorts in the open)
     }

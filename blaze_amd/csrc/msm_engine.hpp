@@ -231,6 +231,10 @@ int msm_sort_lds(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits);
 // window-table plans (P.table: shared bucket set, entries = point * W + window).  msm_sort3_ok: does the plan qualify
 bool msm_sort3_ok(const MsmPlan& P, int sbits);
 int msm_sort3_max_vgprs(bool table);   // the largest register count among the kernels of that kind of plan (0 if unknown)
+int msm_sort3_max_lds(bool table);     // ... and the largest LDS allocation of one block, in bytes (0 if unknown)
+// do the hidden sort's blocks (sv VGPRs per lane, sl bytes of LDS per block) fit on a CU beside the accumulation's (av VGPRs,
+// al bytes of LDS per block of 128 lanes)?  msm.hip; a count that is not known (<= 0) is taken to fit.
+bool msm_sort_fits_beside(int av, int sv, int al, int sl);
 int msm_sort3(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits);
 int msm_sort_lds_scatter(MsmEngine& E);
 // the whole sort stage of a small task (digits, bucket scan, entries, unit lists, stats) in one block (msm_sort_tiny.hip)
@@ -252,6 +256,7 @@ struct MsmCurveOps {
     TailTraits tail;
     // VGPRs of k_accumulate as compiled (hipFuncGetAttributes): what the hidden sort has to fit beside
     int (*accumulate_vgprs)();
+    int (*accumulate_lds)();   // ... and the LDS bytes of one of its blocks
     // window table of npts wire-format points (msm_impl.hip.hpp k_build_window_table): table[i W + j] = 2^(base_shift + c j) P_i in the
     // Montgomery point format, on `st`; scratch: table_scratch_bytes(W) bytes; *flag (device u32) is set when a multiple came
     // out as infinity

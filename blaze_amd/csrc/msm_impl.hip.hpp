@@ -418,6 +418,70 @@ BLZ_DEV void store_xyzz(uint32_t* base, size_t idx, const XYZZ<F>& a) {
     fp_store(q + 3 * F::N, a.zzz);
 }
 
+// The accumulation's gather of unpacked 128-byte points (the BLS base fields), as whole lines through LDS.  load_affine_rr
+// is seven global_load_dwordx4 per lane, each touching 64 lines and 64 pages per wave: 448 line and page look-ups for a
+// wave's 64 points.  Here eight consecutive lanes fetch one point's line, 16 bytes each, straight into LDS
+// (global_load_lds_dwordx4): instruction k = 0..7 fetches the lines owned by lanes 8g + k, lane (g, r) piece r of it.  The
+// hardware writes lane l's piece at base + 16 l, so instruction k's image is [g][r] and lane 8g + k finds its point as seven
+// contiguous pieces at piece k * 64 + g * 8.  64 look-ups per wave-gather; tools/gather_bw.hip prices the bare pattern
+// (profiles/gather_lines.txt).  EVERY lane of the wave has to execute every load - a lane that sits out leaves a hole in
+// another lane's point - so the callers keep their control flow wave-uniform around acc_lines_issue.
+template <class F>
+constexpr bool acc_gather_lines() {
+    if constexpr (USE_RR<F>) return !rr_point_packed<F>() && MONT_STRIDE<F> == 32 && F::RR::NL == 14;
+    else return false;
+}
+constexpr int ACC_IMG_PIECES = 512;   // 16-byte pieces of a wave's image: 64 lines of 8 (8 KiB)
+// `lds`: the image's LDS address as a wave-uniform scalar (acc_image_base).  An owner's line address reaches its group
+// through ds_swizzle (lane = (lane & 0x18) | k within each half of the wave): no address registers, no VALU work but the
+// one add of the lane's own piece.
+template <int K>
+BLZ_DEV void acc_lines_issue_one(uint32_t lds, uint32_t lo, uint32_t hi, uint32_t piece) {
+    constexpr int pattern = (K << 5) | 0x18;
+    const uint32_t olo = (uint32_t)__builtin_amdgcn_ds_swizzle((int)lo, pattern);
+    const uint32_t ohi = (uint32_t)__builtin_amdgcn_ds_swizzle((int)hi, pattern);
+    const uint64_t src = (((uint64_t)ohi << 32) | olo) + piece;
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)(uintptr_t)(lds + K * 1024), 16, 0, 0);
+}
+BLZ_DEV void acc_lines_issue(uint32_t lds, const uint32_t* pts, uint32_t idx) {
+    const uint64_t line = (uint64_t)(uintptr_t)pts + (uint64_t)idx * 128u;
+    const uint32_t lo = (uint32_t)line, hi = (uint32_t)(line >> 32), piece = (threadIdx.x & 7u) * 16u;
+    acc_lines_issue_one<0>(lds, lo, hi, piece); acc_lines_issue_one<1>(lds, lo, hi, piece);
+    acc_lines_issue_one<2>(lds, lo, hi, piece); acc_lines_issue_one<3>(lds, lo, hi, piece);
+    acc_lines_issue_one<4>(lds, lo, hi, piece); acc_lines_issue_one<5>(lds, lo, hi, piece);
+    acc_lines_issue_one<6>(lds, lo, hi, piece); acc_lines_issue_one<7>(lds, lo, hi, piece);
+}
+BLZ_DEV uint32_t acc_image_base(const uint4* img) {
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)img);
+}
+// the lane's own point out of the image.  Nothing orders an LDS read behind a pending load-to-LDS but the issuing wave's
+// own vmcnt; and the reads have returned before the caller's next acc_lines_issue overwrites the image.
+template <class Q>
+BLZ_DEV void acc_lines_read(AffineRR<Q>& a, const uint4* img) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint4* q4 = img + (lane & 7u) * 64 + (lane >> 3) * 8;
+    uint32_t w[2 * Q::NL];
+    // (vmcnt(0) as the builtin, so that the compiler's own wait counting sees it: the rare P + P branch reloads the accumulator
+    // from scratch, and with those loads still pending at the loop's head in its books it put a vmcnt(0) of its own in front
+    // of the accumulator's first use - right behind the gather's issue, whose latency the addition is there to cover)
+    // 0x0F70 is vmcnt(0) alone in the gfx9 layout of s_waitcnt's immediate: vmcnt = bits 3:0 and 15:14, expcnt = 6:4 and
+    // lgkmcnt = 11:8 left at their maxima (no wait).  gfx10 and later lay the field out differently.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "acc_lines_read: the s_waitcnt immediate is written in the gfx9 encoding"
+#endif
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < 2 * Q::NL / 4; ++i) {
+        uint4 v = q4[i];
+        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < Q::NL; ++i) { a.x.v[i] = w[i]; a.y.v[i] = w[Q::NL + i]; }
+}
+
 // NOTE on __launch_bounds__(T, 3) below: the out-of-line group-law routines (pt_mdbl, pt_add, pt_dbl,
 // quad_*) are compiled once per translation unit with the register budget of their MOST permissive
 // caller, and a kernel's VGPR count is the maximum over its callees.  One kernel left at the default
@@ -464,22 +528,34 @@ BLZ_DEV void accumulate_body(const uint32_t* __restrict__ pts, const uint32_t* _
                              uint32_t* __restrict__ sums, bool first) {
     // the grid covers the host's upper bound of the unit count; the real count is on the device (stats[0])
     uint32_t t = blockIdx.x * 128u + threadIdx.x;
-    if (t >= stats[0]) return;
-    const uint32_t u = unit_order[t];  // units of equal run length sit in the same wave
-    uint32_t g = unit_bucket[u];
-    const uint32_t u0 = unit_off[g];
-    uint32_t k = u - u0;
-    uint32_t start = off[g] + k * L;
-    uint32_t end = off[g + 1];
-    if (end - start > L) end = start + L;
+#if BLZ_ACC_RR_WAVES == 2
+    constexpr bool LINES = acc_gather_lines<F>();
+#else
+    constexpr bool LINES = false;
+#endif
+    // (the line gather needs every lane of a wave that has any unit at all: there, a lane without one is a predicate)
+    const uint32_t nunits = stats[0];
+    if ((LINES ? t & ~63u : t) >= nunits) return;
+    const bool live = t < nunits;
+    uint32_t g = 0, start = 0, end = 0;
     uint32_t* dst = partial;
-    size_t didx = u;
+    size_t didx = 0;
     bool resume = false;
-    if constexpr (CONT) {
-        if (unit_off[g + 1] - u0 == 1) {
-            dst = sums;
-            didx = g;
-            resume = !first;
+    if (live) {
+        const uint32_t u = unit_order[t];  // units of equal run length sit in the same wave
+        g = unit_bucket[u];
+        const uint32_t u0 = unit_off[g];
+        const uint32_t k = u - u0;
+        start = off[g] + k * L;
+        end = off[g + 1];
+        if (end - start > L) end = start + L;
+        didx = u;
+        if constexpr (CONT) {
+            if (unit_off[g + 1] - u0 == 1) {
+                dst = sums;
+                didx = g;
+                resume = !first;
+            }
         }
     }
     if constexpr (USE_RR<F>) {
@@ -490,6 +566,64 @@ BLZ_DEV void accumulate_body(const uint32_t* __restrict__ pts, const uint32_t* _
         ptrr_set_inf(acc);
         if constexpr (CONT) {
             if (resume) ptrr_load(acc, sums, g);
+        }
+        if constexpr (LINES) {
+            // The POINT of entry j + 1 is prefetched into the wave's LDS image (no registers), the INDEX of entry j + 2 into
+            // `en`.  A lane that has run out of entries - or never had a unit - fetches point 0 and adds nothing; the loop runs
+            // to the wave's longest run (units are ordered by length, so most waves end together).
+            __shared__ uint4 images[2 * ACC_IMG_PIECES];
+            const uint4* img = images + (threadIdx.x >> 6) * ACC_IMG_PIECES;
+            const uint32_t lds = acc_image_base(img);
+            uint32_t j = start;
+            uint32_t e = j < end ? entries[j] : 0u;            // the entry whose point is in flight or in the image
+            uint32_t en = j + 1 < end ? entries[j + 1] : 0u;   // the entry after `e`
+            acc_lines_issue(lds, pts, BLZ_PT_IDX(e));
+            if (live && start == end) ptrr_store(dst, didx, acc);   // (no unit is empty; were one, this is its sum)
+#ifndef BLZ_ACC_NO_AADD
+            // the run's first two points are both affine: a cheaper addition than the mixed one (ptrr_aadd).  Both come
+            // through the image; a lane that stays out (a run of one, a resumed bucket) fetches its first point again.
+            const bool aadd = (!CONT || first) && end - start >= 2;
+            if (__any(aadd)) {
+                AffineRR<Q> p0, p1;
+                acc_lines_read(p0, img);
+                const bool neg0 = (e & 0x80000000u) != 0;
+                const uint32_t e1 = aadd ? en : e;
+                acc_lines_issue(lds, pts, BLZ_PT_IDX(e1));
+                if (aadd) {
+                    j = start + 2;
+                    e = j < end ? entries[j] : 0u;
+                    en = j + 1 < end ? entries[j + 1] : 0u;
+                }
+                acc_lines_read(p1, img);
+                if (__any(j < end)) acc_lines_issue(lds, pts, BLZ_PT_IDX(e));
+                if (aadd) {
+                    ptrr_aadd<Q, 1>(acc, p0, neg0, p1, (e1 & 0x80000000u) != 0);
+                    if (j == end) ptrr_store(dst, didx, acc);
+                }
+            }
+#endif
+            // A lane stores its sum with its run's last addition and then goes on adding point 0 to a sum nobody reads: the
+            // addition is the wave's either way, and an addition under a lane predicate costs the loop 56 register copies.
+            // (A lane that never had a unit adds point 0 to infinity and then to itself, so a wave with such lanes - the last
+            // one of a launch, or one whose runs differ in length - takes the out-of-line P + P branch once.  A handful of
+            // waves per launch.)
+            // The eight loads go out BEFORE the addition, right behind the read-out, not after its first product pair: they
+            // hold no registers (the two of an address die with each load), so there is nothing to gain from issuing them
+            // later, and in front of the addition they stay outside its divergent branches (infinity restart, P + P), which
+            // a load that needs every lane could not be inside of.  The whole addition covers their latency.
+            while (__any(j < end)) {
+                AffineRR<Q> cur;
+                acc_lines_read(cur, img);
+                const bool neg = (e & 0x80000000u) != 0;
+                const bool more = j + 1 < end;
+                e = more ? en : 0u;
+                if (__any(more)) acc_lines_issue(lds, pts, BLZ_PT_IDX(e));
+                if (j + 2 < end) en = entries[j + 2];
+                ptrr_madd<Q, 1>(acc, cur, neg);
+                ++j;
+                if (j == end) ptrr_store(dst, didx, acc);
+            }
+            return;
         }
         uint32_t e = entries[start];
 #if BLZ_ACC_RR_WAVES == 2
@@ -1558,6 +1692,15 @@ int accumulate_vgprs_t() {
     }
     return a.numRegs;
 }
+template <class F>
+int accumulate_lds_t() {
+    hipFuncAttributes a;
+    if (hipFuncGetAttributes(&a, (const void*)k_accumulate<F>) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return (int)a.sharedSizeBytes;
+}
 
 template <class F>
 MsmCurveOps make_ops() {
@@ -1569,6 +1712,7 @@ MsmCurveOps make_ops() {
     o.run_reduce = &run_reduce_t<F>;
     o.tail = TailTraits{HAS_RR<F>, HAS_ROW<F>, partial_dwords<F>()};
     o.accumulate_vgprs = &accumulate_vgprs_t<F>;
+    o.accumulate_lds = &accumulate_lds_t<F>;
     o.build_table = &build_table_t<F>;
     o.table_scratch_bytes = &table_scratch_bytes_t<F>;
     o.combine = &combine_t<F>;

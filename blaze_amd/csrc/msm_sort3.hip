@@ -1,8 +1,9 @@
 // Three-level digit sort with a small footprint, built to run UNDERNEATH another task's bucket accumulation.
 //
-// k_accumulate (2 waves x 200 VGPRs per SIMD, no LDS) leaves 112 VGPRs per SIMD, four wave slots and the whole LDS of
-// every CU idle, and ~85 % of the memory system: the digit sort of the NEXT task (msm_sort.hip: 10.9 ms of a 122 ms
-// step at 2^26) fits in there - if its kernels fit.  The two-level sort's do not (512 / 1024-thread blocks holding 16 - 24
+// k_accumulate (2 waves x 200 VGPRs per SIMD) leaves 112 VGPRs per SIMD and most of the memory system idle (measured on
+// the kernel that used no LDS: ~85 % of the bandwidth).  The BLS kernels now stage their gathers in 4 x 16 KiB of LDS per CU,
+// which by the allocation arithmetic leaves 96 of a CU's 160 KiB; the other kernels use none.  The digit sort of the NEXT
+// task (msm_sort.hip: 10.9 ms of a 122 ms step at 2^26) fits in there - if its kernels fit.  The two-level sort's do not (512 / 1024-thread blocks holding 16 - 24
 // entries per lane in registers), and shrinking them shrinks the runs they write: with 1024-way splits a 256-thread
 // block produces pieces of one or two entries, the memory system drowns in lone stores, and the accumulation above it
 // slows down by more than the sort costs alone (round 2 measured exactly that: profiles/r02_sort_under_accumulate.txt).
@@ -10,13 +11,14 @@
 // writes pieces of 24 - 32 entries, 256 threads per block, wave priority raised (at equal priority the accumulation's
 // older waves starve the sort's).  Registers as compiled for gfx950: the plain plan's kernels <= 72 VGPRs
 // (k3_l1_scatter 72, k3_l3 70), the table plan's <= 78 (k3t_l3<true> 78, k3_l1_scatter 72, k3t_l3<false> 54).  The sort
-// hides only while MsmEngine::begin()'s sort_fits_beside holds: 2 x 200 + 72 = 472 of the 480 registers a SIMD hands
+// hides only while msm_sort_fits_beside (msm.hip) holds: 2 x 200 + 72 = 472 of the 480 registers a SIMD hands
 // out, and 2 x 200 + 80 (78 is allocated as 80) = 480 with nothing to spare; tests/test_isa_counts.py holds these bounds.
+// And its largest block's LDS (k3_l1_scatter: 83 KiB) beside the accumulation's four blocks per CU: 64 + 83 of 160 KiB.
 //
 // ONE family of kernels, two geometries (S3Geom: plain window plans, S3TGeom: window-table plans).  Plain plan:
 //   bucket g (flat over the windows)  =  level-1 bin (g >> 14)  |  level-2 digit (7 bits)  |  level-3 digit (7 bits)
 //   k3_l1_count    scalars -> LDS histogram over the <= 2048 level-1 bins -> cnt1
-//   k3_l1_scatter  3072 scalars per block parked in LDS (lane-private, word-major: the block's register file stays
+//   k3_l1_scatter  2048 scalars per block parked in LDS (lane-private, word-major: the block's register file stays
 //                  free), window by window: digits, LDS rank, bin-major stage, slot-major copy-out of
 //                  (index | sign : u32, low 14 bits of the bucket : u16) grouped by level-1 bin
 //   k3_l2_count / k3_l2_scatter   per slice of 4096 entries of a level-1 bin: 128-way split by the middle 7 bits;
@@ -36,8 +38,13 @@ namespace blz {
 constexpr int S3_THREADS = 256;
 constexpr int S3_SH1 = 14;                      // level-1 bin = bucket >> 14
 constexpr int S3_SH2 = 7;                       // level-2 bin = bucket >> 7
-constexpr int S3_T = 12;                        // scalars per lane of the level-1 scatter
-constexpr int S3_PB = S3_THREADS * S3_T;        // 3072 points per block: 96 KiB of scalars + 24 KiB of stage
+// (8, not 12: k_accumulate's BLS kernels now stage their points in 16 KiB of LDS per block, four blocks per CU, and a level-1
+// block of 123 KiB no longer fits beside them in the CU's 160 KiB)
+#ifndef BLZ_S3_T   // (A/B builds: make EXTRA=-DBLZ_S3_T=12)
+#define BLZ_S3_T 8
+#endif
+constexpr int S3_T = BLZ_S3_T;                  // scalars per lane of the level-1 scatter
+constexpr int S3_PB = S3_THREADS * S3_T;        // 2048 points per block: 64 KiB of scalars + 16 KiB of stage
 constexpr uint32_t S3_SLICE2 = 4096;            // entries per level-2 work item (16 per lane)
 constexpr int S3_T2 = S3_SLICE2 / S3_THREADS;
 constexpr int S3_T3 = 28;                       // level 3: entries per lane held in registers
@@ -724,38 +731,46 @@ bool msm_sort3_ok(const MsmPlan& P, int sbits) {
     return true;
 }
 
-int msm_sort3_max_vgprs(bool table) {
+// what the kernels of that kind of plan need at most: registers, and LDS bytes per block (static + what the launch adds)
+static constexpr size_t s3_lds1(int nw) { return (size_t)((nw + 2) * S3_PB + 3 * 256) * 4; }   // k3_l1_scatter's dynamic LDS
+struct S3Need { int vgprs, lds; };
+static S3Need s3_needs(bool table) {
     using L2 = S3Geom::L2;
-    static const void* const plain_ks[] = {(const void*)k3_l1_count<S3Geom, 8>, (const void*)k3_l1_scatter<S3Geom, 8>,
-                                           (const void*)k3_l1_count<S3Geom, 1>, (const void*)k3_l1_scatter<S3Geom, 1>,
-                                           (const void*)k3_l1_count<S3Geom, 2>, (const void*)k3_l1_scatter<S3Geom, 2>,
-                                           (const void*)k3_l2_count<L2>, (const void*)k3_l2_scatter<L2>, (const void*)k3_l3};
-    static const void* const table_ks[] = {(const void*)k3_l1_count<S3TGeom, 8>, (const void*)k3_l1_scatter<S3TGeom, 8>,
-                                           (const void*)k3_l2_count<S3TGeom>, (const void*)k3_l2_scatter<S3TGeom>,
-                                           (const void*)k3t_l3<true>, (const void*)k3t_l3<false>};
-    static int cached[2] = {-1, -1};
-    int& c = cached[table ? 1 : 0];
-    if (c >= 0) return c;
-    const void* const* ks = table ? table_ks : plain_ks;
+    struct K { const void* f; size_t dyn; };
+    static const K plain_ks[] = {{(const void*)k3_l1_count<S3Geom, 8>, 0}, {(const void*)k3_l1_scatter<S3Geom, 8>, s3_lds1(8)},
+                                 {(const void*)k3_l1_count<S3Geom, 1>, 0}, {(const void*)k3_l1_scatter<S3Geom, 1>, s3_lds1(1)},
+                                 {(const void*)k3_l1_count<S3Geom, 2>, 0}, {(const void*)k3_l1_scatter<S3Geom, 2>, s3_lds1(2)},
+                                 {(const void*)k3_l2_count<L2>, 0}, {(const void*)k3_l2_scatter<L2>, 0}, {(const void*)k3_l3, 0}};
+    static const K table_ks[] = {{(const void*)k3_l1_count<S3TGeom, 8>, 0}, {(const void*)k3_l1_scatter<S3TGeom, 8>, s3_lds1(8)},
+                                 {(const void*)k3_l2_count<S3TGeom>, 0}, {(const void*)k3_l2_scatter<S3TGeom>, 0},
+                                 {(const void*)k3t_l3<true>, (size_t)S3_R3 * 4}, {(const void*)k3t_l3<false>, (size_t)S3T_IMG * 4}};
+    static S3Need cached[2] = {{-1, -1}, {-1, -1}};
+    S3Need& c = cached[table ? 1 : 0];
+    if (c.vgprs >= 0) return c;
+    const K* ks = table ? table_ks : plain_ks;
     const size_t n = table ? sizeof(table_ks) / sizeof(*table_ks) : sizeof(plain_ks) / sizeof(*plain_ks);
-    int mx = 0;
+    S3Need mx = {0, 0};
     for (size_t i = 0; i < n; ++i) {
         hipFuncAttributes a;
-        if (hipFuncGetAttributes(&a, ks[i]) != hipSuccess) {
+        if (hipFuncGetAttributes(&a, ks[i].f) != hipSuccess) {
             (void)hipGetLastError();
-            return c = 0;
+            return c = S3Need{0, 0};
         }
-        if (a.numRegs > mx) mx = a.numRegs;
+        if (a.numRegs > mx.vgprs) mx.vgprs = a.numRegs;
+        const int lds = (int)(a.sharedSizeBytes + ks[i].dyn);
+        if (lds > mx.lds) mx.lds = lds;
     }
     return c = mx;
 }
+int msm_sort3_max_vgprs(bool table) { return s3_needs(table).vgprs; }
+int msm_sort3_max_lds(bool table) { return s3_needs(table).lds; }
 
 // level 1 of a task: count, scan of the bins, scatter
 template <class Geom, int NW>
 static int s3_level1(hipStream_t st, const uint32_t* sc, uint32_t npts, const Geom& g, uint32_t* cnt1, uint32_t* off1, uint32_t* cur1,
                      uint32_t* i1_idx, uint16_t* i1_rem) {
     const dim3 blk(S3_THREADS);
-    const size_t lds1 = (size_t)((NW + 2) * S3_PB + 3 * 256) * 4;
+    const size_t lds1 = s3_lds1(NW);
     hipLaunchKernelGGL((k3_l1_count<Geom, NW>), dim3((npts + S3_CNT_PTS - 1) / S3_CNT_PTS), blk, 0, st, sc, npts, g, cnt1);
     hipLaunchKernelGGL(k3_scan_small, dim3(1), blk, 0, st, cnt1, g.NB1, off1, cur1, g.prio);
     BLZ_TRY(ensure_dynamic_lds((const void*)k3_l1_scatter<Geom, NW>, (int)lds1));

@@ -637,4 +637,8 @@ int blz_test_msm_tail_plan(int curve, int repr, uint32_t npts, int sbits, int pi
     return BLZ_OK;
 }
 
+int blz_test_sort_fits_beside(int acc_vgprs, int sort_vgprs, int acc_lds, int sort_lds) {
+    return msm_sort_fits_beside(acc_vgprs, sort_vgprs, acc_lds, sort_lds) ? 1 : 0;
+}
+
 }  // extern "C"

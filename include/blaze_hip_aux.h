@@ -62,6 +62,11 @@ int blz_test_ec_op(int device_id, int curve, int op, const uint8_t* p, const uin
 int blz_test_msm_tail_plan(int curve, int repr, uint32_t npts, int sbits, int pieces, int table_c, int bit_lo, int bit_hi, uint32_t plan_out[8],
                            uint8_t* widths, char* text, size_t cap);
 
+/* MsmEngine::begin()'s test for hiding a task's digit sort under another task's accumulation: 1 when a block of the sort (sort_vgprs
+ * registers per lane, sort_lds bytes of LDS) fits on a CU beside the accumulation's blocks of 128 lanes (acc_vgprs, acc_lds), else 0.
+ * Host only.  A count <= 0 is "not known" and is taken to fit. */
+int blz_test_sort_fits_beside(int acc_vgprs, int sort_vgprs, int acc_lds, int sort_lds);
+
 /* ------------------------------------------------------------------ Poseidon (blaze_hip.h "Poseidon")
  * words / len: an instruction word stream as blz_poseidon_initialize_words takes it.
  * blz_test_poseidon_permute: the DEFINITION kernel - one lane per state, the dense textbook rounds on the 8 x 32-bit Montgomery
