@@ -44,6 +44,11 @@ class BlzVecView(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("stride", C.c_uint64), ("len", C.c_uint64)]
 
 
+class BlzVecCsr(C.Structure):
+    """struct blz_vec_csr (include/blaze_hip.h): the sparse matrix blz_ntt_vec_spmv multiplies by, CSR arrays in device memory."""
+    _fields_ = [("d_row_ptr", C.c_void_p), ("d_col", C.c_void_p), ("d_val", C.c_void_p), ("rows", C.c_uint64), ("nnz", C.c_uint64)]
+
+
 # every exported symbol of include/blaze_hip.h: name -> (restype, argtypes)
 _u8p = C.c_void_p
 _SIGS = {
@@ -120,6 +125,7 @@ _SIGS = {
     "blz_ntt_vec_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_horner": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_gather": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecView)]),
+    "blz_ntt_vec_spmv": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecCsr)]),
     "blz_ntt_banks_preprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
     "blz_ntt_banks_postprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
     "blz_poseidon_new": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

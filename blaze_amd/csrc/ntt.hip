@@ -13,7 +13,9 @@
 // launches: the powers of g ride on the passes' own factors (ntt_engine.hpp NttCoset).
 // Data stay in plain canonical form; only twiddles are in Montgomery form (mont_mul(x, tR) = x t),
 // so there is no conversion pass.  Algorithmic traffic 2 x 4 GiB; this 3-pass form moves 3x that.
+#include <algorithm>
 #include <atomic>
+#include <cstdio>
 #include <initializer_list>
 #include <string>
 #include <thread>
@@ -637,8 +639,8 @@ int blz_ntt_reset(blz_ntt* h) {
     return BLZ_OK;
 }
 
-// Ops on the transform buffers (include/blaze_hip.h: blz_ntt_vec_op, _reduce, _scan, _horner, _gather; kernels and their workspace:
-// ntt_vec.hip.hpp, ntt_fold.hip.hpp, ntt_horner.hip.hpp, ntt_gather.hip.hpp).  An op runs like a transform: compute stream, ev0 .. ev1, finished by
+// Ops on the transform buffers (include/blaze_hip.h: blz_ntt_vec_op, _reduce, _scan, _horner, _gather, _spmv; kernels and their workspace:
+// ntt_vec.hip.hpp, ntt_fold.hip.hpp, ntt_horner.hip.hpp, ntt_gather.hip.hpp, ntt_spmv.hip.hpp).  An op runs like a transform: compute stream, ev0 .. ev1, finished by
 // blz_ntt_wait_result.  Everything is checked before anything is enqueued and nothing waits for the device.  The workspace is
 // `scratch`, n x 32 bytes that only a transform or an op of this handle uses - and none can be in flight.  An entry point
 // checks its own arguments, then walks this protocol: begin, resolve, enqueue.
@@ -657,6 +659,29 @@ struct NttVecCall {
         return use_device(h->device);
     }
 
+    // The pointer half of every check: `bytes` bytes at p are device memory of the handle's device, inside one allocation, and p
+    // is aligned.  who / field name the argument ("operand a" / "d_ptr"); units x unit is what would run past the end
+    int device_range(const char* who, const char* field, const void* p, uint64_t bytes, unsigned align, uint64_t units, const char* unit) {
+        if (((uintptr_t)p & (align - 1u)) != 0) return fail(BLZ_ERR_INVALID_PARAM, "%s: %s is not %u-byte aligned", who, field, align);
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(BLZ_ERR_INVALID_PARAM, "%s: %s is not memory the runtime knows", who, field);
+        }
+        if (at.type != hipMemoryTypeDevice || at.device != h->device)
+            return fail(BLZ_ERR_INVALID_PARAM, "%s: %s is not device memory of device %d", who, field, h->device);
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(BLZ_ERR_INVALID_PARAM, "%s: %s is not inside a device allocation", who, field);
+        }
+        if ((const char*)p + bytes > (const char*)base + size)
+            return fail(BLZ_ERR_INVALID_PARAM, "%s: %llu %s run past the end of the allocation %s points into", who,
+                        (unsigned long long)units, unit, field);
+        return BLZ_OK;
+    }
+
     int operand(const char* name, const blz_vec_arg* v, NttVecArg& out, uint64_t max_count) {
         if (v->reserved != 0) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: reserved must be 0", name);
         if (!v->d_ptr) {
@@ -671,23 +696,9 @@ struct NttVecCall {
         if (v->count == 0 || (v->count & (v->count - 1)) != 0 || v->count > max_count)
             return fail(BLZ_ERR_INVALID_PARAM, "operand %s: count %llu is not a power of two in [1, %llu]", name,
                         (unsigned long long)v->count, (unsigned long long)max_count);
-        if (((uintptr_t)v->d_ptr & 15u) != 0) return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not 16-byte aligned", name);
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, v->d_ptr) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not memory the runtime knows", name);
-        }
-        if (at.type != hipMemoryTypeDevice || at.device != h->device)
-            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not device memory of device %d", name, h->device);
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)v->d_ptr) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: d_ptr is not inside a device allocation", name);
-        }
-        if ((const char*)v->d_ptr + v->count * 32 > (const char*)base + size)
-            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: %llu elements run past the end of the allocation d_ptr points into", name,
-                        (unsigned long long)v->count);
+        char who[48];
+        snprintf(who, sizeof who, "operand %s", name);
+        BLZ_TRY(device_range(who, "d_ptr", v->d_ptr, v->count * 32, 16, v->count, "elements"));
         out = NttVecArg{(const uint32_t*)v->d_ptr, v->count - 1};
         return BLZ_OK;
     }
@@ -806,6 +817,42 @@ int blz_ntt_vec_gather(blz_ntt* h, size_t buf_dst, const blz_vec_arg* a, const b
         BLZ_TRY(h->ops->vec_gather(h->stream, in_place ? call.ws : dst, va, v->offset, v->stride & va.mask, v->len, call.n));
         if (in_place) BLZ_HIP(hipMemcpyAsync(dst, call.ws, ntt_bytes(h), hipMemcpyDeviceToDevice, h->stream), BLZ_ERR_UNKNOWN);
         return BLZ_OK;
+    });
+}
+
+// The matrix is the caller's device memory and the host never reads it: the three arrays are checked as pointers (device_range),
+// their contents are the kernels' to survive (ntt_spmv.hip.hpp).  `scratch` is the op's workspace, so x may not name buf_dst: the
+// gather's detour is taken.  CSR mode zeroes the destination first - rows without a nonzero are visited by no tile.
+int blz_ntt_vec_spmv(blz_ntt* h, size_t buf_dst, const blz_vec_arg* x, const blz_vec_csr* m) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (buf_dst > 1) return fail(BLZ_ERR_INVALID_PARAM, "buf_dst must be 0 or 1");
+    if (!x || !m) return fail(BLZ_ERR_INVALID_PARAM, "a sparse product takes operand x and a matrix m");
+    NttVecCall call{h};
+    BLZ_TRY(call.begin());
+    const uint64_t max_nnz = std::min<uint64_t>(std::max<uint64_t>(1024, 256 * call.n), 1ull << 31);
+    if (m->rows > call.n)
+        return fail(BLZ_ERR_INVALID_PARAM, "matrix m: rows %llu is above the handle's %llu positions", (unsigned long long)m->rows,
+                    (unsigned long long)call.n);
+    if (m->nnz > max_nnz)
+        return fail(BLZ_ERR_INVALID_PARAM, "matrix m: nnz %llu is above %llu (max(1024, 256 n), at most 2^31)", (unsigned long long)m->nnz,
+                    (unsigned long long)max_nnz);
+    if (!m->d_row_ptr && m->rows != m->nnz)
+        return fail(BLZ_ERR_INVALID_PARAM, "matrix m: without d_row_ptr row p is nonzero p, but rows %llu != nnz %llu",
+                    (unsigned long long)m->rows, (unsigned long long)m->nnz);
+    if (!m->d_col && m->nnz > 0) return fail(BLZ_ERR_INVALID_PARAM, "matrix m: d_col is NULL with nnz %llu", (unsigned long long)m->nnz);
+    NttVecArg vx{};
+    BLZ_TRY(call.resolve({{"x", x, &vx, 1ull << NTT_MAX_LOG}}));
+    const uint32_t* const dst_words = h->buf[buf_dst].as<uint32_t>();
+    if (vx.p < dst_words + call.n * 8 && dst_words < vx.p + (vx.mask + 1) * 8)
+        return fail(BLZ_ERR_INVALID_PARAM, "operand x names or overlaps buffer %zu, the destination: a sparse product cannot run in place", buf_dst);
+    if (m->d_row_ptr) BLZ_TRY(call.device_range("matrix m", "d_row_ptr", m->d_row_ptr, (m->rows + 1) * 4, 4, m->rows + 1, "entries"));
+    if (m->nnz > 0) BLZ_TRY(call.device_range("matrix m", "d_col", m->d_col, m->nnz * 4, 4, m->nnz, "entries"));
+    if (m->d_val && m->nnz > 0) BLZ_TRY(call.device_range("matrix m", "d_val", m->d_val, m->nnz * 32, 16, m->nnz, "elements"));
+    return call.enqueue((int)buf_dst, [&](uint32_t* dst) -> int {
+        const bool csr = m->d_row_ptr != nullptr;
+        if (csr || m->nnz == 0) BLZ_HIP(hipMemsetAsync(dst, 0, ntt_bytes(h), h->stream), BLZ_ERR_UNKNOWN);
+        if (m->nnz == 0 || m->rows == 0) return BLZ_OK;
+        return h->ops->vec_spmv(h->stream, dst, vx, m->d_row_ptr, m->d_col, (const uint32_t*)m->d_val, m->rows, m->nnz, call.n, call.ws);
     });
 }
 

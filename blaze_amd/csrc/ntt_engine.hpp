@@ -120,6 +120,12 @@ struct NttFieldOps {
     // len <= p < n; a may hold more than n words.  offset <= a.mask, stride reduced modulo a.mask + 1, len <= n.  dst must NOT
     // overlap a's words
     int (*vec_gather)(hipStream_t st, uint32_t* dst, NttVecArg a, uint64_t offset, uint64_t stride, uint64_t len, uint64_t n);
+    // Sparse matrix times vector (blz_ntt_vec_spmv; kernels and the workspace's layout: ntt_spmv.hip.hpp): dst[p] = sum over
+    // row_ptr[p] <= k < row_ptr[p + 1] of val[k] x[col[k] & x.mask] for p < rows.  row_ptr == nullptr: row p is nonzero p
+    // (rows == nnz <= n) and every position of dst is written; else dst holds zeros already, rows >= 1 and nnz >= 1.
+    // val == nullptr: coefficients 1.  dst must NOT overlap x's words
+    int (*vec_spmv)(hipStream_t st, uint32_t* dst, NttVecArg x, const uint32_t* row_ptr, const uint32_t* col, const uint32_t* val,
+                    uint64_t rows, uint64_t nnz, uint64_t n, uint32_t* ws);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

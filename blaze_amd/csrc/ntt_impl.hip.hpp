@@ -8,6 +8,7 @@
 #include "ntt_fold.hip.hpp"
 #include "ntt_horner.hip.hpp"
 #include "ntt_gather.hip.hpp"
+#include "ntt_spmv.hip.hpp"
 
 namespace blz {
 
@@ -520,6 +521,7 @@ NttFieldOps make_ntt_ops() {
     o.vec_scan = &ntt_vec_scan_t<Fr>;
     o.vec_horner = &ntt_vec_horner_t<Fr>;
     o.vec_gather = &ntt_vec_gather_t<Fr>;
+    o.vec_spmv = &ntt_vec_spmv_t<Fr>;
     return o;
 }
 

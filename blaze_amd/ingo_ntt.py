@@ -6,7 +6,7 @@ import enum
 from dataclasses import dataclass
 from typing import Optional
 
-from ._lib import BlzVecArg, BlzVecView, DeviceBuffer, buf_ptr, check, lib
+from ._lib import BlzVecArg, BlzVecCsr, BlzVecView, DeviceBuffer, buf_ptr, check, lib
 from .driver_client import DriverClient, DriverPrimitive
 
 NTT_LOG_SIZE = 27  # ntt_data.rs:65: NTT_SIZE = 2^27
@@ -226,6 +226,37 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         zeros above them - n coefficients into a 4n client.  A vec_gather with length = m."""
         self.vec_gather(dst, a, offset=0, stride=1, length=a.nbytes // NTT_WORD_SIZE)
         self._vec_keep = (a,)
+
+    def vec_spmv(self, dst: int, x, col: DeviceBuffer, row_ptr: Optional[DeviceBuffer] = None, val: Optional[DeviceBuffer] = None,
+                 rows: Optional[int] = None, nnz: Optional[int] = None, row0: int = 0) -> None:
+        """Sparse matrix times vector (blz_ntt_vec_spmv): transform buffer `dst`[p] = sum over row_ptr[p] <= k < row_ptr[p + 1] of
+        val[k] x[col[k] mod count] for p < rows, 0 for an empty row and for rows <= p < n.  `x` is the other transform buffer or a
+        DeviceBuffer of count = nbytes / 32 words (a power of two up to 2^27); it may not name `dst`.  `col` (uint32, nnz =
+        nbytes / 4 entries unless `nnz` says less), `row_ptr` (uint32, rows + 1 entries; rows = nbytes / 4 - 1 - row0 unless
+        `rows` says less) and `val` (32-byte words, None: every coefficient is 1) are DeviceBuffers.  row0 = r0 passes the slab
+        of rows from r0 on (row_ptr + r0 with the full col / val arrays).  row_ptr=None is index mode: row p is nonzero p
+        (vec_index).  Every output word is canonical.  Finished by wait_result()."""
+        vx = self._vec_arg(x)
+        if nnz is None:
+            nnz = col.nbytes // 4 if col is not None else 0
+        if row_ptr is None:
+            rows = nnz if rows is None else rows
+            rp = None
+        else:
+            rows = row_ptr.nbytes // 4 - 1 - int(row0) if rows is None else rows
+            if int(row0) < 0 or int(row0) + int(rows) + 1 > row_ptr.nbytes // 4:
+                raise ValueError(f"rows {rows} from row {row0} on need {int(row0) + int(rows) + 1} row pointers, the DeviceBuffer holds {row_ptr.nbytes // 4}")
+            rp = row_ptr.ptr + 4 * int(row0)
+        m = BlzVecCsr(rp, None if col is None else col.ptr, None if val is None else val.ptr, int(rows), int(nnz))
+        check(lib().blz_ntt_vec_spmv(self._h, dst, None if vx is None else C.byref(vx), C.byref(m)))
+        self._vec_keep = (x, col, row_ptr, val)
+
+    def vec_index(self, dst: int, x, col: DeviceBuffer, val: Optional[DeviceBuffer] = None) -> None:
+        """Data-dependent gather: transform buffer `dst`[p] = x[col[p] mod count] (times val[p] with `val`) for p < nbytes / 4
+        entries of the uint32 DeviceBuffer `col`, 0 above - a PLONK wire column w[ia[p]], a looked-up column t[idx[p]], a
+        permutation held as an index table.  A vec_spmv without row_ptr."""
+        self.vec_spmv(dst, x, col, val=val)
+        self._vec_keep = (x, col, val)
 
     def scalar(self, value: int) -> DeviceBuffer:
         """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""

@@ -287,6 +287,16 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
         const blz_vec_arg a = words(d_ptr, count);
         vec_gather(dst, &a, view(0, 1, count));
     }
+    // sparse matrix times vector (blz_ntt_vec_spmv): buffer dst[p] = sum over the nonzeros k of row p of val[k] x[col[k] mod count],
+    // 0 for an empty row and above rows; x may not name dst.  csr(row_ptr, col, val, rows, nnz) builds the struct from device
+    // pointers (val null: coefficients 1).  vec_index: dst[p] = x[col[p] mod count] (times val[p]), the data-dependent gather
+    static blz_vec_csr csr(const uint32_t* d_row_ptr, const uint32_t* d_col, const void* d_val, uint64_t rows, uint64_t nnz) {
+        return blz_vec_csr{d_row_ptr, d_col, d_val, rows, nnz};
+    }
+    void vec_spmv(size_t dst, const blz_vec_arg* x, const blz_vec_csr& m) { check(blz_ntt_vec_spmv(h_, dst, x, &m)); }
+    void vec_index(size_t dst, const blz_vec_arg* x, const uint32_t* d_col, uint64_t count, const void* d_val = nullptr) {
+        vec_spmv(dst, x, csr(nullptr, d_col, d_val, count, count));
+    }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

@@ -431,7 +431,7 @@ typedef struct blz_vec_arg {
     uint32_t buf;        /* 0 | 1, read only when d_ptr == NULL */
     uint32_t reserved;   /* must be 0 */
     uint64_t count;      /* d_ptr != NULL: number of 32-byte elements, a power of two, 1 <= count <= n (the source of
-                            blz_ntt_vec_gather: <= 2^27); position p of the op reads element p & (count - 1).
+                            blz_ntt_vec_gather and blz_ntt_vec_spmv: <= 2^27); position p of the op reads element p & (count - 1).
                             d_ptr == NULL: 0 or n */
 } blz_vec_arg;
 int blz_ntt_vec_op(blz_ntt* h, int op, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c);
@@ -529,6 +529,51 @@ typedef struct blz_vec_view {
     uint64_t len;      /* positions p < len read the source, positions len <= p < n become 0; len <= n */
 } blz_vec_view;
 int blz_ntt_vec_gather(blz_ntt* h, size_t buf_dst, const blz_vec_arg* a, const blz_vec_view* v);
+/* Sparse matrix-vector products on resident buffers: a sparse matrix in CSR form times a resident vector, into a transform
+ * buffer - the first step of a prover, which turns a witness w into vectors on the evaluation domain: A w, B w, C w of an R1CS
+ * (one row per constraint, a few nonzeros per row, a tail of very long rows), the wire columns a[p] = w[ia[p]] of PLONK, the
+ * looked-up column t[idx[p]] of a lookup argument, a permutation held as an index table (a scatter with known indices is a gather
+ * by the inverse table).  Over the handle's field, by buffer POSITION (the BLZ_NTT_BITREV_* flags and the coset shift play no
+ * part), with n = 2^log_size:
+ *   dst[p] = sum over row_ptr[p] <= k < row_ptr[p + 1] of val[k] * x[col[k] mod count]   for p < rows (an empty row gives 0)
+ *   dst[p] = 0                                                                           for rows <= p < n
+ *   Values: every word of x and of val is any 256-bit value and counts as its residue; every output word is canonical,
+ *   little-endian.
+ *   x: a transform buffer (d_ptr == NULL) or `count` device words, checked as for blz_ntt_vec_gather: count is a power of two
+ *   up to 2^27 and may be below or above n.  col[k] is taken modulo count (an AND): no column value reaches outside x.
+ *   x may NOT name buf_dst (nor may its device words overlap that buffer): the handle's scratch is the op's workspace, so the
+ *   gather's detour through it is not available.
+ *   Index mode, d_row_ptr == NULL: rows must equal nnz and row p holds nonzero p alone: dst[p] = val[p] * x[col[p] mod count], the
+ *   data-dependent gather; with d_val == NULL as well a canonicalising copy without a product.
+ *   row_ptr contract: nondecreasing, row_ptr[rows] <= nnz.  Nonzeros below row_ptr[0] or from row_ptr[rows] on belong to no row
+ *   and are ignored, so a slab of rows is d_row_ptr + r0 with the full col / val arrays.  The host never reads the arrays and
+ *   cannot verify the contract: the kernels clamp every nonzero index to nnz, keep every row index below rows and mask every
+ *   column, so whatever bytes row_ptr and col hold, no memory outside the four arrays, the destination buffer and the handle's
+ *   scratch is touched.  For arrays that break the contract dst is UNSPECIFIED.
+ *   Bounds: rows <= n; nnz <= max(1024, 256 n) and nnz <= 2^31 (the workspace is the handle's scratch, n x 32 bytes, 128 bytes per
+ *   tile of 1024 nonzeros; nothing is allocated).  nnz = 0 and rows = 0 are valid and write zeros.
+ *   Pointers: d_row_ptr and d_col are 4-byte aligned device memory of the handle's device with (rows + 1) * 4 and nnz * 4 bytes
+ *   inside one allocation; d_val is 16-byte aligned with nnz * 32 bytes.
+ *   Cost: the work is split by nonzeros, not by rows, so that a long row is spread over lanes and blocks like short ones; the
+ *   sums of rows that cross a block's 1024 nonzeros are added up by one lane per row ("Sparse
+ *   products": derived from the code's shape, no time is claimed).  The random 32-byte reads of x fetch whole cache lines.
+ *   Protocol: that of blz_ntt_vec_gather.  Everything is checked before anything is enqueued; the op runs on the compute stream
+ *   and the call returns without waiting for the device; blz_ntt_wait_result finishes it, blz_ntt_last_kernel_ms then reports
+ *   it, blz_ntt_reset drops it.  While it is in flight buf_dst may not be read, written or exchanged, a buffer that is only read
+ *   may be read, and every transform, blz_ntt_set_coset and op on the buffers is refused (as blz_ntt_vec_spmv is while any of
+ *   those is in flight).  Memory behind the four pointers stays valid and unwritten until blz_ntt_wait_result returns.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing: null handle, null x or m, buf_dst > 1, rows > n, nnz above its bound, null d_col
+ *   with nnz > 0, d_row_ptr == NULL with rows != nnz, a bad pointer (alignment, not device memory of the handle's device, the
+ *   array running past its allocation), x naming buf_dst, and any operand error of blz_ntt_vec_op with the count bound raised
+ *   to 2^27. */
+typedef struct blz_vec_csr {
+    const uint32_t* d_row_ptr; /* rows + 1 entries; NULL: row p holds nonzero p alone (then rows == nnz) */
+    const uint32_t* d_col;     /* nnz entries: nonzero k reads x[col[k] mod count] */
+    const void*     d_val;     /* NULL: every coefficient is 1; else nnz 32-byte words */
+    uint64_t        rows;      /* <= n; positions rows <= p < n become 0 */
+    uint64_t        nnz;
+} blz_vec_csr;                 /* 40 bytes */
+int blz_ntt_vec_spmv(blz_ntt* h, size_t buf_dst, const blz_vec_arg* x, const blz_vec_csr* m);
 /* NTTBanks::preprocess / postprocess (ntt_data.rs:80-156) as device permutations, for byte
  * compatibility with bank files of the FPGA flow; n = 2^log_size elements (log_size >= 10), 16 banks
  * contiguous (n/16 elements each); 2^27 uses the reference's 512 groups x 256 block pairs, smaller sizes

@@ -36,6 +36,17 @@ pub struct BlzVecView {
     pub stride: u64,
     pub len: u64,
 }
+/// `struct blz_vec_csr`: the sparse matrix `blz_ntt_vec_spmv` multiplies by, CSR arrays in device memory.  `d_row_ptr` null: row p
+/// holds nonzero p alone (`rows` == `nnz`); `d_val` null: every coefficient is 1.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct BlzVecCsr {
+    pub d_row_ptr: *const u32,
+    pub d_col: *const u32,
+    pub d_val: *const c_void,
+    pub rows: u64,
+    pub nnz: u64,
+}
 
 pub const BLZ_COMM_ID_BYTES: usize = 128;
 
@@ -124,6 +135,7 @@ extern "C" {
     pub fn blz_ntt_vec_scan(h: *mut BlzNtt, op: c_int, flags: u32, buf_dst: usize, a: *const BlzVecArg, d_total: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_horner(h: *mut BlzNtt, flags: u32, buf_dst: usize, a: *const BlzVecArg, z: *const BlzVecArg, d_total: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_gather(h: *mut BlzNtt, buf_dst: usize, a: *const BlzVecArg, v: *const BlzVecView) -> c_int;
+    pub fn blz_ntt_vec_spmv(h: *mut BlzNtt, buf_dst: usize, x: *const BlzVecArg, m: *const BlzVecCsr) -> c_int;
 
     // ---- Poseidon tree: PoseidonClient (ingo_hash::poseidon_api)
     pub fn blz_poseidon_new(device_id: c_int, field: c_int, out: *mut *mut BlzPoseidon) -> c_int;

@@ -218,6 +218,31 @@ impl NTTClient {
         self.vec_gather(dst, VecOperand::Words { d_ptr, count }, 0, 1, count)
     }
 
+    /// Sparse matrix times vector (blz_ntt_vec_spmv): transform buffer `dst`\[p\] = the sum over the nonzeros k of row p
+    /// (`d_row_ptr`\[p\] <= k < `d_row_ptr`\[p + 1\]) of val\[k\] x\[col\[k\] mod count\] for p < `rows`, 0 for an empty row and
+    /// for `rows` <= p < n.  `x` is the other transform buffer or `count` device words (a power of two up to 2^27); it may not
+    /// name `dst`.  A null `d_row_ptr` is index mode (`rows` == `nnz`, row p is nonzero p), a null `d_val` means coefficients 1.
+    /// Every output word is canonical.
+    ///
+    /// # Safety
+    /// As for `vec_op`; the three arrays are device memory of the client's device that stays valid and unwritten until
+    /// `wait_result` returns.
+    pub unsafe fn vec_spmv(&self, dst: usize, x: VecOperand, d_row_ptr: *const u32, d_col: *const u32,
+                           d_val: *const std::os::raw::c_void, rows: u64, nnz: u64) -> Result<()> {
+        let (rx, m) = (x.raw(), BlzVecCsr { d_row_ptr, d_col, d_val, rows, nnz });
+        check(blz_ntt_vec_spmv(self.h, dst, &rx, &m))
+    }
+
+    /// Data-dependent gather: transform buffer `dst`\[p\] = x\[col\[p\] mod count\] (times val\[p\] unless `d_val` is null) for
+    /// p < `count` entries of `d_col`, 0 above: a PLONK wire column, a looked-up column, a permutation held as an index table.
+    /// A `vec_spmv` without row pointers.
+    ///
+    /// # Safety
+    /// As for `vec_spmv`.
+    pub unsafe fn vec_index(&self, dst: usize, x: VecOperand, d_col: *const u32, count: u64, d_val: *const std::os::raw::c_void) -> Result<()> {
+        self.vec_spmv(dst, x, std::ptr::null(), d_col, d_val, count, count)
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
