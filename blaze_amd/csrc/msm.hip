@@ -44,6 +44,17 @@ size_t mont_point_bytes(int curve) { return curve == BLZ_BN254 ? 64 : 128; }
 // window of max(cmin, what is left of sbits+1) bits (its upper bits are zero for canonical scalars, so
 // its signed digits never go negative; only 2^(real bits) of its buckets are occupied).  k = 0 with a
 // top window of cmin bits is the uniform plan; BLAZE_MSM_PLAN c= forces that one.
+// Unit length: a unit is one lane's sequential chain (L mixed adds of ~15 us each when the SIMD has
+// little else to run), so on small inputs long units ARE the runtime: 2^18 points, c = 13 spent
+// 3.7 of 7.2 ms waiting for the 256-long units of the short top window.  Keep the longest chain
+// below about half of the throughput-bound time of the whole accumulation.
+static uint32_t unit_length(uint32_t npts, int W) {
+    const double chain = (double)npts * W * 5.5e-6;
+    uint32_t L = 16;
+    while (L < 256 && 2.0 * L <= chain) L <<= 1;
+    return L;
+}
+
 static MsmPlan search_plan(uint32_t npts, int sbits, int ebits, int force_c, int split_ns, int max_w) {
     MsmPlan best;
     double best_cost = 1e300;
@@ -74,6 +85,7 @@ static MsmPlan search_plan(uint32_t npts, int sbits, int ebits, int force_c, int
                 for (int w = 0; w < W; ++w) {
                     const int cw = w == lower ? top : (w < k ? cmin + 1 : cmin);
                     const double Bw = (double)(1ull << (cw - 1));
+                    // (plan_tail() keeps its own copy of this occupancy model: there t == 0 counts npts entries, not half, and `active` is not clamped to `entries`)
                     int t = ebits - off;                        // real scalar bits in this window
                     if (t > cw) t = cw;
                     double entries, active;
@@ -113,16 +125,7 @@ static MsmPlan search_plan(uint32_t npts, int sbits, int ebits, int force_c, int
             }
         }
     }
-    // Unit length: a unit is one lane's sequential chain (L mixed adds of ~15 us each when the SIMD has
-    // little else to run), so on small inputs long units ARE the runtime: 2^18 points, c = 13 spent
-    // 3.7 of 7.2 ms waiting for the 256-long units of the short top window.  Keep the longest chain
-    // below about half of the throughput-bound time of the whole accumulation.
-    {
-        double chain = (double)npts * best.W * 5.5e-6;
-        uint32_t L = 16;
-        while (L < 256 && 2.0 * L <= chain) L <<= 1;
-        best.L = L;
-    }
+    best.L = unit_length(npts, best.W);
     return best;
 }
 
@@ -189,10 +192,7 @@ MsmPlan make_table_plan(uint32_t npts, int c, int need_bits) {
     P.boff[W] = (uint32_t)P.G;
     P.Bw = 1u << (c - 1 - 5);   // the one window is walked as 32 virtual windows (k_finish stitches them)
     P.Wv = 32;
-    double chain = (double)npts * W * 5.5e-6;
-    uint32_t L = 16;
-    while (L < 256 && 2.0 * L <= chain) L <<= 1;
-    P.L = L;
+    P.L = unit_length(npts, W);
     return P;
 }
 
@@ -223,6 +223,7 @@ int plan_tail(const MsmPlan& P, TailTraits tr, bool piecewise, TailPlan& T) {
         for (int w = 0; w < P.W; ++w) { offs[w] = off; off += P.width[w]; }
         for (int w = P.W - 1; w >= 0; --w) {
             const int cw = P.width[w];
+            // (search_plan()'s occupancy model, not quite: t == 0 counts npts entries here, half of them there, and only the planner clamps `active` to `entries`)
             int t = P.ebits - offs[w];
             if (t > cw) t = cw;
             const double slots = (double)(1ull << (cw - 1));
@@ -624,23 +625,22 @@ int msm_points_all_canonical(int format_id, const void* d_raw, uint64_t npts, ui
     return ops->points_all_canonical(d_raw, npts, flag, st);
 }
 
-int launch_fill_units(MsmEngine& E, uint32_t U /* upper bound of the unit count */) {
-    const uint64_t G = E.last_plan.G;
-    const uint32_t L = E.last_plan.L;
-    hipStream_t st = E.sort_st;
-    BLZ_TRY(E.sb().unit_bucket.reserve(((size_t)U + 1) * 4));
-    BLZ_TRY(E.sb().unit_order.reserve(((size_t)U + 1) * 4));
-    BLZ_TRY(E.sb().lenhist.reserve(2 * (MAX_L + 1) * 4));
-    uint32_t* hist = E.sb().lenhist.as<uint32_t>();
+int launch_fill_units(const MsmStep& C, uint32_t U /* upper bound of the unit count */) {
+    const uint64_t G = C.P.G;
+    const uint32_t L = C.P.L;
+    hipStream_t st = C.sort_stream;
+    MsmEngine::SortBufs& B = C.B;
+    BLZ_TRY(B.unit_bucket.reserve(((size_t)U + 1) * 4));
+    BLZ_TRY(B.unit_order.reserve(((size_t)U + 1) * 4));
+    BLZ_TRY(B.lenhist.reserve(2 * (MAX_L + 1) * 4));
+    uint32_t* hist = B.lenhist.as<uint32_t>();
     uint32_t* cursor = hist + (MAX_L + 1);
     BLZ_HIP(hipMemsetAsync(hist, 0, 2 * (MAX_L + 1) * 4, st), BLZ_ERR_UNKNOWN);
     uint64_t nchunks = (G + 255) / 256;
     dim3 gg((uint32_t)(nchunks < UNIT_GRID ? nchunks : UNIT_GRID)), b(256);
-    hipLaunchKernelGGL(k_fill_units, gg, b, 0, st, E.sb().off.as<uint32_t>(), E.sb().unit_off.as<uint32_t>(), G, L,
-                       E.sb().unit_bucket.as<uint32_t>(), hist);
+    hipLaunchKernelGGL(k_fill_units, gg, b, 0, st, B.off.as<uint32_t>(), B.unit_off.as<uint32_t>(), G, L, B.unit_bucket.as<uint32_t>(), hist);
     hipLaunchKernelGGL(k_unit_len_scan, dim3(1), b, 0, st, hist, L, cursor);
-    hipLaunchKernelGGL(k_unit_order, gg, b, 0, st, E.sb().off.as<uint32_t>(), E.sb().unit_off.as<uint32_t>(), G, L, cursor,
-                       E.sb().unit_order.as<uint32_t>());
+    hipLaunchKernelGGL(k_unit_order, gg, b, 0, st, B.off.as<uint32_t>(), B.unit_off.as<uint32_t>(), G, L, cursor, B.unit_order.as<uint32_t>());
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     return BLZ_OK;
 }
@@ -668,20 +668,13 @@ int MsmEngine::init(int device_id, int curve_id, int precompute_factor) {
     BLZ_HIP(hipStreamCreateWithPriority(&tail_stream, hipStreamNonBlocking, prio_high), BLZ_ERR_UNKNOWN);
     BLZ_HIP(hipStreamCreateWithPriority(&aux_stream, hipStreamNonBlocking, prio_high), BLZ_ERR_UNKNOWN);
     BLZ_HIP(hipStreamCreateWithPriority(&sort_stream, hipStreamNonBlocking, prio_high), BLZ_ERR_UNKNOWN);
-    sort_st = stream;
     last_sort_done = nullptr;
     for (auto& S : slots) {
-        for (auto& e : S.ev) BLZ_HIP(hipEventCreate(&e), BLZ_ERR_UNKNOWN);
-        for (auto& e : S.slice_ev) BLZ_HIP(hipEventCreate(&e), BLZ_ERR_UNKNOWN);
-        BLZ_HIP(hipEventCreateWithFlags(&S.ev_l0, hipEventDisableTiming), BLZ_ERR_UNKNOWN);
-        BLZ_HIP(hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming), BLZ_ERR_UNKNOWN);
-        BLZ_HIP(hipEventCreateWithFlags(&S.ev_sorted, hipEventDisableTiming), BLZ_ERR_UNKNOWN);
-        for (int i = 0; i < 2; ++i) {
-            BLZ_HIP(hipEventCreateWithFlags(&S.ev_sorted_pp[i], hipEventDisableTiming), BLZ_ERR_UNKNOWN);
-            BLZ_HIP(hipEventCreateWithFlags(&S.ev_acc_pp[i], hipEventDisableTiming), BLZ_ERR_UNKNOWN);
-        }
-        BLZ_HIP(hipEventCreate(&S.ev_s0), BLZ_ERR_UNKNOWN);
-        BLZ_HIP(hipEventCreate(&S.ev_s1), BLZ_ERR_UNKNOWN);
+        BLZ_TRY(for_each_event(S, [](hipEvent_t& e, bool timed) -> int {
+            if (timed) BLZ_HIP(hipEventCreate(&e), BLZ_ERR_UNKNOWN);
+            else BLZ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming), BLZ_ERR_UNKNOWN);
+            return BLZ_OK;
+        }));
         BLZ_HIP(hipHostMalloc((void**)&S.result_h, 256), BLZ_ERR_UNKNOWN);
         BLZ_HIP(hipHostMalloc((void**)&S.stats_h, 64), BLZ_ERR_UNKNOWN);
         memset(S.stats_h, 0, 64);
@@ -702,25 +695,9 @@ bool MsmEngine::destroy() {
         stream = tail_stream = aux_stream = sort_stream = nullptr;
         return false;
     }
-    for (DevBuf* b : {&coarse, &inter, &inter2, &slice_map, &partial, &blocksums, &result, &sort3_tabs, &bucket_sums, &bucket_ident})
-        b->release();
-    for (auto& B : sbuf)
-        for (DevBuf* b : {&B.count, &B.off, &B.unit_off, &B.unit_bucket, &B.unit_order, &B.lenhist, &B.entries, &B.stats, &B.range_scalars}) b->release();
+    for_each_buf([](DevBuf& b) { b.release(); });
     for (auto& S : slots) {
-        for (DevBuf* b : {&S.lvlA[0], &S.lvlA[1], &S.lvlC[0], &S.lvlC[1]}) b->release();
-        for (auto& e : S.ev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& e : S.slice_ev)
-            if (e) (void)hipEventDestroy(e);
-        if (S.ev_l0) (void)hipEventDestroy(S.ev_l0);
-        if (S.ev_done) (void)hipEventDestroy(S.ev_done);
-        if (S.ev_sorted) (void)hipEventDestroy(S.ev_sorted);
-        for (int i = 0; i < 2; ++i) {
-            if (S.ev_sorted_pp[i]) (void)hipEventDestroy(S.ev_sorted_pp[i]);
-            if (S.ev_acc_pp[i]) (void)hipEventDestroy(S.ev_acc_pp[i]);
-        }
-        if (S.ev_s0) (void)hipEventDestroy(S.ev_s0);
-        if (S.ev_s1) (void)hipEventDestroy(S.ev_s1);
+        (void)for_each_event(S, [](hipEvent_t& e, bool) -> int { if (e) (void)hipEventDestroy(e); return BLZ_OK; });
         if (S.result_h) (void)hipHostFree(S.result_h);
         if (S.stats_h) (void)hipHostFree(S.stats_h);
         S = MsmSlot();
@@ -728,10 +705,7 @@ bool MsmEngine::destroy() {
     inputs_event = nullptr;
     if (combine_h) (void)hipHostFree(combine_h);
     combine_h = nullptr;
-    (void)hipStreamDestroy(stream);
-    (void)hipStreamDestroy(tail_stream);
-    (void)hipStreamDestroy(aux_stream);
-    (void)hipStreamDestroy(sort_stream);
+    for (hipStream_t s : {stream, tail_stream, aux_stream, sort_stream}) (void)hipStreamDestroy(s);
     stream = tail_stream = aux_stream = sort_stream = nullptr;
     last_sort_done = nullptr;
     return true;
@@ -852,15 +826,33 @@ int msm_task_pieces(const MsmPlan& P, int want, bool phased, uint32_t* per_out) 
 // and accumulates piece by piece over the same bucket space: the bucket sums live in `bucket_sums`, indexed by bucket;
 // k_accumulate_cont resumes a bucket's sum where the previous piece left it (msm_impl.hip.hpp), runs longer than L go through the
 // unit folds and k_merge_buckets, and the reduce reads bucket_sums through the identity map.
+int MsmEngine::take_slot(int* slot_out) {
+    int slot = (rr_cursor + 1) % MSM_QUEUE_DEPTH;
+    if (slots[slot].busy) slot = (slot + 1) % MSM_QUEUE_DEPTH;
+    if (slots[slot].busy) return fail(BLZ_ERR_INVALID_PARAM, "task queue full (%d tasks in flight)", MSM_QUEUE_DEPTH);
+    *slot_out = slot;
+    return BLZ_OK;
+}
+
+int MsmEngine::step(int slot, int piece, bool curve_kernels, std::optional<MsmStep>& out) {
+    BLZ_TRY(use_device(device));
+    if (slot < 0 || slot >= MSM_QUEUE_DEPTH || !slots[slot].open) return fail(BLZ_ERR_INVALID_PARAM, "slot %d has no task being enqueued", slot);
+    MsmSlot& S = slots[slot];
+    if (curve_kernels && S.repr != repr) return fail(BLZ_ERR_INVALID_PARAM, "the handle's arithmetic changed while task %d was being enqueued", slot);
+    if (S.slices == 1) piece = -1;
+    // a ping-pong task's pieces alternate between the slot's own set and the other slot's; end() reads the slot's own
+    const int set = S.pingpong && piece >= 0 ? (slot + piece) % MSM_QUEUE_DEPTH : slot;
+    out.emplace(MsmStep{slot, S, piece, S.plan, sbuf[set], stream, S.sort_hidden ? sort_stream : stream});
+    return BLZ_OK;
+}
+
 int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int bit_lo, int bit_hi, int nslices, bool phased) {
     BLZ_TRY(use_device(device));
     const MsmCurveOps* ops = msm_ops_for(curve, repr);
     hipStream_t st = stream;
     if (npts == 0) return fail(BLZ_ERR_INVALID_PARAM, "begin: empty task");
-    // slots are handed out round-robin, so results complete in submission order
-    int slot = (cur + 1) % MSM_QUEUE_DEPTH;
-    if (slots[slot].busy) slot = (slot + 1) % MSM_QUEUE_DEPTH;
-    if (slots[slot].busy) return fail(BLZ_ERR_INVALID_PARAM, "task queue full (%d tasks in flight)", MSM_QUEUE_DEPTH);
+    int slot = -1;
+    BLZ_TRY(take_slot(&slot));
     MsmSlot& S = slots[slot];
     MsmPlan P;
     bool ranged = false;
@@ -916,9 +908,9 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
                           sort_fits(false);
     if (pingpong) { s3 = true; hide = true; }
 
-    cur = slot;
+    rr_cursor = slot;
     if (slot_out) *slot_out = slot;
-    last_plan = S.plan = P;
+    S.plan = P;
     S.npts = npts;
     S.sbits = sbits;
     S.ranged = ranged;
@@ -958,23 +950,18 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
 
 // the sort stage of piece `sl`: np points whose scalars start at d_scalars (np x sbits / 8 bytes)
 int MsmEngine::sort_slice(int slot, int sl, const void* d_scalars, uint32_t np) {
-    BLZ_TRY(use_device(device));
-    if (slot < 0 || slot >= MSM_QUEUE_DEPTH || !slots[slot].open) return fail(BLZ_ERR_INVALID_PARAM, "slot %d has no task being enqueued", slot);
-    MsmSlot& S = slots[slot];
+    std::optional<MsmStep> C;
+    BLZ_TRY(step(slot, sl, false, C));
+    MsmSlot& S = C->S;
     if (sl < 0 || sl >= S.slices || np == 0 || np > S.pts_per_slice) return fail(BLZ_ERR_INVALID_PARAM, "piece %d of %d with %u points", sl, S.slices, np);
-    MsmEngine& E = *this;
-    cur = slot;
-    last_plan = S.plan;
-    const MsmPlan& P = S.plan;
+    rr_cursor = slot;
+    const MsmPlan& P = C->P;
     const uint64_t G = P.G;
     const uint32_t nscan = (uint32_t)((G + 1 + SCAN_TILE - 1) / SCAN_TILE);
-    hipStream_t st = stream;
     MsmSlot& O = slots[(slot + 1) % MSM_QUEUE_DEPTH];
-    sb_sel = S.pingpong ? (slot + sl) % MSM_QUEUE_DEPTH : slot;
-    SortBufs& B = sb();
+    SortBufs& B = C->B;
     const bool hide = S.sort_hidden;
-    sort_st = hide ? sort_stream : st;
-    hipStream_t ss = sort_st;
+    hipStream_t ss = C->sort_stream;
     if (last_sort_done) BLZ_HIP(hipStreamWaitEvent(ss, last_sort_done, 0), BLZ_ERR_UNKNOWN);
     if (hide) {
         // whoever read this buffer set last must have let go of it: the accumulation two pieces back (ping-pong), else the
@@ -1001,14 +988,15 @@ int MsmEngine::sort_slice(int slot, int sl, const void* d_scalars, uint32_t np) 
     BLZ_HIP(hipMemsetAsync(B.stats.p, 0, 64, ss), BLZ_ERR_UNKNOWN);
     // a small task's whole sort stage - digits, bucket scan, entries, unit lists - is one block's work (msm_sort_tiny.hip)
     const bool tiny = !S.use_s3 && S.slices == 1 && msm_sort_tiny_ok(P, np, S.sbits);
+    LdsSortPass lds_pass;
     if (S.use_s3) {
-        BLZ_TRY(msm_sort3(E, sc_s, np, S.sbits));   // count[] and entries[] in one go
+        BLZ_TRY(msm_sort3(*this, *C, sc_s, np, S.sbits));   // count[] and entries[] in one go
     } else if (tiny) {
-        BLZ_TRY(msm_sort_tiny(E, sc_s, np, S.sbits, (uint32_t)S.max_units));
+        BLZ_TRY(msm_sort_tiny(*this, *C, sc_s, np, S.sbits, (uint32_t)S.max_units));
     } else {
         const size_t n16 = ((G + 1) * 4 + 15) / 16;   // the reserve of begin() rounds the allocation up
         hipLaunchKernelGGL(k_zero, dim3(2048), dim3(256), 0, ss, (uint4*)B.count.p, n16);
-        BLZ_TRY(msm_sort_lds(E, sc_s, np, S.sbits));
+        BLZ_TRY(msm_sort_lds(*this, *C, sc_s, np, S.sbits, lds_pass));
     }
     if (!tiny) {
         hipLaunchKernelGGL(k_scan_reduce, dim3(nscan), b256, 0, ss, B.count.as<uint32_t>(), G, P.L, blocksums.as<uint64_t>(),
@@ -1016,14 +1004,14 @@ int MsmEngine::sort_slice(int slot, int sl, const void* d_scalars, uint32_t np) 
         hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_SUMS_THREADS), 0, ss, blocksums.as<uint64_t>(), nscan, B.stats.as<uint32_t>());
         hipLaunchKernelGGL(k_scan_final, dim3(nscan), b256, 0, ss, B.count.as<uint32_t>(), G, P.L, blocksums.as<uint64_t>(),
                            B.off.as<uint32_t>(), B.unit_off.as<uint32_t>());
-        if (!S.use_s3) BLZ_TRY(msm_sort_lds_scatter(E));
+        if (!S.use_s3) BLZ_TRY(msm_sort_lds_scatter(*this, *C, lds_pass));
     }
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     // No host round trip: the unit count stays on the device.  Buffers and grids are sized by the bound
     // (every bucket at most one short unit, plus entries / L full ones) and the kernels read the real count
     // from `stats`; the host copy below is for the log line, the sanity check of finish() and the hot-bucket guard.
     BLZ_TRY(copy_words_to_pinned(S.stats_h, B.stats.p, 4, ss));
-    if (!tiny) BLZ_TRY(launch_fill_units(E, (uint32_t)S.max_units));
+    if (!tiny) BLZ_TRY(launch_fill_units(*C, (uint32_t)S.max_units));
     hipEvent_t sorted = S.pingpong ? S.ev_sorted_pp[sl & 1] : S.ev_sorted;
     BLZ_HIP(hipEventRecord(sorted, ss), BLZ_ERR_UNKNOWN);
     last_sort_done = sorted;
@@ -1043,18 +1031,14 @@ int MsmEngine::sort_slice(int slot, int sl, const void* d_scalars, uint32_t np) 
 
 // the accumulation of piece `sl` (its sort stage has been enqueued): d_pts = Montgomery points of the piece's first point
 int MsmEngine::accumulate_slice(int slot, int sl, const void* d_pts) {
-    BLZ_TRY(use_device(device));
-    if (slot < 0 || slot >= MSM_QUEUE_DEPTH || !slots[slot].open) return fail(BLZ_ERR_INVALID_PARAM, "slot %d has no task being enqueued", slot);
-    MsmSlot& S = slots[slot];
-    if (S.repr != repr) return fail(BLZ_ERR_INVALID_PARAM, "the handle's arithmetic changed while task %d was being enqueued", slot);
+    std::optional<MsmStep> C;
+    BLZ_TRY(step(slot, sl, true, C));
+    MsmSlot& S = C->S;
     const MsmCurveOps* ops = msm_ops_for(curve, repr);
-    cur = slot;
-    last_plan = S.plan;
-    sort_st = S.sort_hidden ? sort_stream : stream;
-    sb_sel = S.pingpong ? (slot + sl) % MSM_QUEUE_DEPTH : slot;
+    rr_cursor = slot;
     if (S.sort_hidden) BLZ_HIP(hipStreamWaitEvent(stream, S.pingpong ? S.ev_sorted_pp[sl & 1] : S.ev_sorted, 0), BLZ_ERR_UNKNOWN);
-    BLZ_TRY(ops->run_accumulate(*this, S, d_pts, (uint32_t)S.max_units, S.slices > 1 ? sl : -1));
-    if (S.slices > 1) BLZ_TRY(ops->merge_buckets(*this));
+    BLZ_TRY(ops->run_accumulate(*this, *C, d_pts, (uint32_t)S.max_units));
+    if (S.slices > 1) BLZ_TRY(ops->merge_buckets(*this, *C));
     if (S.pingpong) {
         BLZ_HIP(hipEventRecord(S.ev_acc_pp[sl & 1], stream), BLZ_ERR_UNKNOWN);
         S.acc_pp_recorded[sl & 1] = true;
@@ -1064,25 +1048,22 @@ int MsmEngine::accumulate_slice(int slot, int sl, const void* d_pts) {
 
 // every piece is enqueued: bucket reduce + tail
 int MsmEngine::end(int slot) {
-    BLZ_TRY(use_device(device));
-    if (slot < 0 || slot >= MSM_QUEUE_DEPTH || !slots[slot].open) return fail(BLZ_ERR_INVALID_PARAM, "slot %d has no task being enqueued", slot);
-    MsmSlot& S = slots[slot];
-    if (S.repr != repr) return fail(BLZ_ERR_INVALID_PARAM, "the handle's arithmetic changed while task %d was being enqueued", slot);
+    std::optional<MsmStep> C;
+    BLZ_TRY(step(slot, -1, true, C));
+    MsmSlot& S = C->S;
     const MsmCurveOps* ops = msm_ops_for(curve, repr);
-    cur = slot;
-    last_plan = S.plan;
+    rr_cursor = slot;
     if (S.task_inputs_event) {
         // phased task: every reader of the staged inputs - the pieces' sorts and the caller's to-Montgomery passes - is on
         // the main stream or has been waited for by it
         BLZ_HIP(hipEventRecord(S.task_inputs_event, stream), BLZ_ERR_UNKNOWN);
         S.task_inputs_event = nullptr;
     }
-    sb_sel = slot;
     if (S.slices > 1) {
         hipLaunchKernelGGL(k_iota, dim3(1024), dim3(256), 0, stream, bucket_ident.as<uint32_t>(), S.plan.G + 2);
-        BLZ_TRY(ops->run_reduce(*this, S, bucket_sums.p, bucket_ident.p));
+        BLZ_TRY(ops->run_reduce(*this, *C, bucket_sums.p, bucket_ident.p));
     } else {
-        BLZ_TRY(ops->run_reduce(*this, S, partial.p, sb().unit_off.p));
+        BLZ_TRY(ops->run_reduce(*this, *C, partial.p, C->B.unit_off.p));
     }
     S.l0_recorded = true;
     S.open = false;
@@ -1104,20 +1085,18 @@ int MsmEngine::run(const void* d_pts, const void* d_scalars, uint32_t npts, int 
                    int bit_hi) {
     BLZ_TRY(use_device(device));
     if (npts == 0) {
-        const MsmCurveOps* ops = msm_ops_for(curve, repr);
         hipStream_t st = stream;
-        int slot = (cur + 1) % MSM_QUEUE_DEPTH;
-        if (slots[slot].busy) slot = (slot + 1) % MSM_QUEUE_DEPTH;
-        if (slots[slot].busy) return fail(BLZ_ERR_INVALID_PARAM, "task queue full (%d tasks in flight)", MSM_QUEUE_DEPTH);
-        cur = slot;
+        int slot = -1;
+        BLZ_TRY(take_slot(&slot));
+        rr_cursor = slot;
         MsmSlot& S = slots[slot];
         if (slot_out) *slot_out = slot;
         BLZ_HIP(hipEventRecord(S.ev[0], st), BLZ_ERR_UNKNOWN);
-        BLZ_TRY(ops->emit_infinity(*this));
+        BLZ_TRY(msm_ops_for(curve, repr)->emit_infinity(*this, slot));
         for (int i = 1; i <= 4; ++i) BLZ_HIP(hipEventRecord(S.ev[i], st), BLZ_ERR_UNKNOWN);
         BLZ_TRY(copy_words_to_pinned(S.result_h, slot_result(slot), (uint32_t)(3 * fq_bytes(curve) / 4), st));
         BLZ_HIP(hipEventRecord(S.ev_done, st), BLZ_ERR_UNKNOWN);
-        last_plan = S.plan = MsmPlan();
+        S.plan = MsmPlan();
         S.accum_timed = false;
         S.open = false;
         S.busy = true;

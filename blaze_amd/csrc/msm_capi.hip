@@ -362,12 +362,7 @@ int blz_msm_memory_info(blz_msm* h, uint64_t out[6]) {
     if (!h || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
     MsmEngine& E = h->eng;
     uint64_t ws = 0;
-    for (const DevBuf* b : {&E.coarse, &E.inter, &E.inter2, &E.slice_map, &E.partial, &E.blocksums, &E.result, &E.sort3_tabs, &E.bucket_sums, &E.bucket_ident})
-        ws += b->cap;
-    for (const auto& B : E.sbuf)
-        for (const DevBuf* b : {&B.count, &B.off, &B.unit_off, &B.unit_bucket, &B.unit_order, &B.lenhist, &B.entries, &B.stats, &B.range_scalars}) ws += b->cap;
-    for (const auto& S : E.slots)
-        for (const DevBuf* b : {&S.lvlA[0], &S.lvlA[1], &S.lvlC[0], &S.lvlC[1]}) ws += b->cap;
+    E.for_each_buf([&](DevBuf& b) { ws += b.cap; });
     uint64_t staging = h->points_mont.cap + h->comm_buf.cap + h->ring.raw.cap + h->ring.mont.cap;
     for (int i = 0; i < 2; ++i) staging += h->scalars_buf[i].cap + h->points_raw[i].cap;
     uint64_t raw = 0, mont = 0, tables = 0;

@@ -1,6 +1,7 @@
 // Host-side interface of the MSM device pipeline (implemented in msm.hip).
 #pragma once
 #include "common.hpp"
+#include <optional>
 
 namespace blz {
 
@@ -135,6 +136,7 @@ struct MsmSlot {
     bool acc_pp_recorded[2] = {false, false};
 };
 
+struct MsmStep;
 struct MsmEngine {
     int device = 0;
     int curve = 0;
@@ -148,7 +150,7 @@ struct MsmEngine {
     int format_id() const { return curve | (repr << 8); }
     hipStream_t stream = nullptr, tail_stream = nullptr, aux_stream = nullptr;  // aux: combine_partials
     MsmSlot slots[MSM_QUEUE_DEPTH];
-    int cur = 0;                   // slot of the task being enqueued
+    int rr_cursor = 0;             // round-robin cursor of take_slot(): the slot a step was last enqueued for
     // What the digit sort of a task hands to its accumulation / reduce: one set per task slot, so that the sort of task
     // k + 1 can run (on sort_stream, underneath task k's accumulation: msm_sort3.hip) while task k still reads its own.
     struct SortBufs {
@@ -156,10 +158,7 @@ struct MsmEngine {
         DevBuf range_scalars;   // scalar-range tasks: words [bit_lo / 32, bit_hi / 32) of every scalar, zero-extended to 32 bytes
     };
     SortBufs sbuf[MSM_QUEUE_DEPTH];
-    int sb_sel = 0;                // the set the piece being enqueued uses: its slot's, or (ping-pong pieces) the other slot's
-    SortBufs& sb() { return sbuf[sb_sel]; }
     hipStream_t sort_stream = nullptr;   // hidden sorts
-    hipStream_t sort_st = nullptr;       // the stream the CURRENT task's sort stage is being enqueued on (stream or sort_stream)
     hipEvent_t last_sort_done = nullptr; // sorts share their scratch (coarse, inter, inter2, ...): each waits for the one before
     DevBuf coarse, inter, inter2, slice_map, partial, blocksums, result, sort3_tabs;
     DevBuf bucket_sums, bucket_ident;   // piecewise tasks: the bucket sums carried across pieces; identity unit_off for the reduce
@@ -172,16 +171,34 @@ struct MsmEngine {
     int accumulate_slice(int slot, int piece, const void* d_points_mont);
     int end(int slot);
     void abandon(int slot);   // give up a task between begin() and end() (a copy failed)
+    int take_slot(int* slot);   // the next task's slot: round-robin, so results complete in submission order; fails when both are busy
+    // The context of one step of the task in `slot` (MsmStep below; piece: -1 for end()), checked and computed HERE only: the device is made current,
+    // the slot must hold a task being enqueued and - curve_kernels - the handle's arithmetic must still be the one begin() sized the task for
+    int step(int slot, int piece, bool curve_kernels, std::optional<MsmStep>& out);
     hipEvent_t inputs_event = nullptr;   // set by the caller of run() / begin(): recorded once the task has read
                                          // its scalars / raw points
     uint8_t* combine_h = nullptr;  // pinned bytes of combine_partials
-    MsmPlan last_plan;
     float last_ms[8] = {};
     bool last_sort_hidden = false;   // of the last task collected by finish(): its sort stage ran on sort_stream
     bool recent_hot[2] = {false, false};   // the last two collected tasks piled entries into a few buckets (begin()'s guard)
-    uint32_t sort_slices = 1, sort_nc = 0;  // geometry of the last LDS sort (msm_sort.hip)
-    int sort_cl = 0;
-    void* sort_inter_fine = nullptr;  // u16 fine digits of the sort intermediate (second half of `inter`)
+    // every workspace buffer of the engine, once: f(DevBuf&) (destroy(), blz_msm_memory_info)
+    template <class Fn>
+    void for_each_buf(Fn&& f) {
+        for (DevBuf* b : {&coarse, &inter, &inter2, &slice_map, &partial, &blocksums, &result, &sort3_tabs, &bucket_sums, &bucket_ident}) f(*b);
+        for (auto& B : sbuf)
+            for (DevBuf* b : {&B.count, &B.off, &B.unit_off, &B.unit_bucket, &B.unit_order, &B.lenhist, &B.entries, &B.stats, &B.range_scalars}) f(*b);
+        for (auto& S : slots)
+            for (DevBuf* b : {&S.lvlA[0], &S.lvlA[1], &S.lvlC[0], &S.lvlC[1]}) f(*b);
+    }
+    // every event of a slot, once: f(hipEvent_t&, timed) -> BLZ_OK to go on.  timed: finish() reads elapsed times between them; the others only order streams
+    template <class Fn>
+    static int for_each_event(MsmSlot& S, Fn&& f) {
+        for (auto& e : S.ev) BLZ_TRY(f(e, true));
+        for (auto& e : S.slice_ev) BLZ_TRY(f(e, true));
+        for (hipEvent_t* e : {&S.ev_l0, &S.ev_done, &S.ev_sorted, &S.ev_sorted_pp[0], &S.ev_acc_pp[0], &S.ev_sorted_pp[1], &S.ev_acc_pp[1]}) BLZ_TRY(f(*e, false));
+        for (hipEvent_t* e : {&S.ev_s0, &S.ev_s1}) BLZ_TRY(f(*e, true));
+        return BLZ_OK;
+    }
 
     int init(int device_id, int curve_id, int precompute_factor);
     bool destroy();   // false: the streams never drained (wedged device work): everything was leaked instead of freed
@@ -212,6 +229,16 @@ struct MsmEngine {
     int sync_all();
 };
 
+// One step of a task - a piece's sort stage, its accumulation, or end() - as its launches see it: built by MsmEngine::step(), read by every launcher
+struct MsmStep {
+    int slot;                  // index of S: the task's result is slot_result(slot)
+    MsmSlot& S;
+    int piece;                 // piece of a piecewise task; -1: a one-piece task, or end()
+    const MsmPlan& P;          // S.plan
+    MsmEngine::SortBufs& B;    // the sort outputs the step writes / reads: the slot's own set; a ping-pong task's pieces alternate with the other slot's
+    hipStream_t stream, sort_stream;   // the main stream; where the sort stage goes: the engine's sort_stream if the sort is hidden, else `stream`
+};
+
 // arena diet: conversions keyed by the FORMAT of a Montgomery copy (MsmEngine::format_id(): curve | repr << 8), for callers
 // without an engine of that format at hand (arena.hip)
 int msm_points_from_mont(int format_id, const void* d_mont, void* d_raw, uint64_t npts, hipStream_t st);
@@ -224,35 +251,41 @@ int msm_points_all_canonical(int format_id, const void* d_raw, uint64_t npts, ui
 int copy_words_to_pinned(void* host_pinned, const void* d_src, uint32_t dwords, hipStream_t st);
 size_t fq_bytes(int curve);
 size_t mont_point_bytes(int curve);  // stride of the Montgomery point array the pipeline reads (msm_impl.hip.hpp MONT_STRIDE)
-// two-level LDS-privatised digit sort (msm_sort.hip): fills count[], then (after the scan) entries[]
-int msm_sort_lds(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits);
-// three-level, small-footprint digit sort built to run underneath another task's k_accumulate (msm_sort3.hip): fills
-// count[] and entries[] of the current slot's SortBufs on E.sort_st.  One family of kernels for plain plans and for
-// window-table plans (P.table: shared bucket set, entries = point * W + window).  msm_sort3_ok: does the plan qualify
+// The sort stages enqueue on C.sort_stream and fill C.B for the plan C.P; the scratch they share is the engine's.  Two-level LDS-privatised digit
+// sort (msm_sort.hip): msm_sort_lds fills count[]; after the caller's scan msm_sort_lds_scatter fills entries[] from the intermediate described by `pass`
+struct LdsSortPass {
+    uint32_t slices = 0, nc = 0;           // fine-pass work items (upper bound), coarse bins
+    int cl = 0;                            // log2 of the buckets per coarse bin
+    const uint16_t* inter_fine = nullptr;  // u16 fine digits of the sort intermediate (second half of `inter`)
+};
+int msm_sort_lds(MsmEngine& E, const MsmStep& C, const void* d_scalars, uint32_t npts, int sbits, LdsSortPass& pass);
+int msm_sort_lds_scatter(MsmEngine& E, const MsmStep& C, const LdsSortPass& pass);
+// three-level, small-footprint digit sort built to run underneath another task's k_accumulate (msm_sort3.hip): fills count[] and
+// entries[].  One family of kernels for plain plans and for window-table plans (P.table: shared bucket set, entries = point * W +
+// window).  msm_sort3_ok: does the plan qualify
 bool msm_sort3_ok(const MsmPlan& P, int sbits);
 int msm_sort3_max_vgprs(bool table);   // the largest register count among the kernels of that kind of plan (0 if unknown)
 int msm_sort3_max_lds(bool table);     // ... and the largest LDS allocation of one block, in bytes (0 if unknown)
 // do the hidden sort's blocks (sv VGPRs per lane, sl bytes of LDS per block) fit on a CU beside the accumulation's (av VGPRs,
 // al bytes of LDS per block of 128 lanes)?  msm.hip; a count that is not known (<= 0) is taken to fit.
 bool msm_sort_fits_beside(int av, int sv, int al, int sl);
-int msm_sort3(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits);
-int msm_sort_lds_scatter(MsmEngine& E);
+int msm_sort3(MsmEngine& E, const MsmStep& C, const void* d_scalars, uint32_t npts, int sbits);
 // the whole sort stage of a small task (digits, bucket scan, entries, unit lists, stats) in one block (msm_sort_tiny.hip)
 bool msm_sort_tiny_ok(const MsmPlan& P, uint32_t npts, int sbits);
-int msm_sort_tiny(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits, uint32_t max_units);
-int launch_fill_units(MsmEngine& E, uint32_t units);  // unit->bucket map + length-ordered unit list
+int msm_sort_tiny(MsmEngine& E, const MsmStep& C, const void* d_scalars, uint32_t npts, int sbits, uint32_t max_units);
+int launch_fill_units(const MsmStep& C, uint32_t units);  // unit->bucket map + length-ordered unit list (at most `units` units)
 
 // per-curve entry points (one translation unit per curve: msm_<curve>.hip)
 struct MsmCurveOps {
     int (*points_to_mont)(MsmEngine&, const void* d_raw, void* d_mont, uint32_t npts);
-    int (*emit_infinity)(MsmEngine&);
+    int (*emit_infinity)(MsmEngine&, int slot);   // the result of an empty task, into slot_result(slot)
     // phase 1 after a digit sort: unit lists, k_accumulate, k_combine_units (at most max_units units; the real count is on
-    // the device).  slice >= 0: piece of a piecewise task - k_accumulate_cont, bracketed by the piece's events.
-    int (*run_accumulate)(MsmEngine&, MsmSlot&, const void* d_pts, uint32_t max_units, int slice);
+    // the device).  C.piece >= 0: piece of a piecewise task - k_accumulate_cont, bracketed by the piece's events.
+    int (*run_accumulate)(MsmEngine&, const MsmStep& C, const void* d_pts, uint32_t max_units);
     // piecewise tasks: bucket_sums[g] += the piece's sum of bucket g where its run needed several units
-    int (*merge_buckets)(MsmEngine&);
+    int (*merge_buckets)(MsmEngine&, const MsmStep& C);
     // phases 2 - 3 over bucket sums found at sums[unit_off[g]] (unit_off[g + 1] > unit_off[g], else the bucket is empty)
-    int (*run_reduce)(MsmEngine&, MsmSlot&, const void* sums, const void* unit_off);
+    int (*run_reduce)(MsmEngine&, const MsmStep& C, const void* sums, const void* unit_off);
     TailTraits tail;
     // VGPRs of k_accumulate as compiled (hipFuncGetAttributes): what the hidden sort has to fit beside
     int (*accumulate_vgprs)();

@@ -1256,8 +1256,8 @@ int points_to_mont_t(MsmEngine& E, const void* d_raw, void* d_mont, uint32_t npt
 }
 
 template <class F>
-int emit_infinity_t(MsmEngine& E) {
-    hipLaunchKernelGGL(k_emit_infinity<F>, dim3(1), dim3(64), 0, E.stream, E.slot_result(E.cur));
+int emit_infinity_t(MsmEngine& E, int slot) {
+    hipLaunchKernelGGL(k_emit_infinity<F>, dim3(1), dim3(64), 0, E.stream, E.slot_result(slot));
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     return BLZ_OK;
 }
@@ -1447,37 +1447,38 @@ template <class F>
 constexpr bool HAS_ROW = has_row_law<F>();  // the wave-wide row law (ec_row.hip.hpp)
 inline int no_tail_kernel(const char* name) { return fail(BLZ_ERR_UNKNOWN, "the tail plan names %s, which this field does not have", name); }
 
-// phase 1 after a digit sort: at most U units (the real count is in E.sb().stats on the device)
+// phase 1 after a digit sort: at most U units (the real count is in the step's stats on the device)
 template <class F>
-int run_accumulate_t(MsmEngine& E, MsmSlot& S, const void* d_pts, uint32_t U, int slice) {
-    hipStream_t st = E.stream;
-    const MsmPlan& P = S.plan;
+int run_accumulate_t(MsmEngine& E, const MsmStep& C, const void* d_pts, uint32_t U) {
+    hipStream_t st = C.stream;
+    MsmSlot& S = C.S;
+    const MsmPlan& P = C.P;
     const TailPlan& T = S.tail;
+    MsmEngine::SortBufs& B = C.B;
     BLZ_TRY(E.partial.reserve(((size_t)U + 1) * 4 * partial_dwords<F>()));
-    if (slice <= 0) BLZ_HIP(hipEventRecord(S.ev[1], st), BLZ_ERR_UNKNOWN);   // (piecewise task: the FIRST piece's sort stage is done)
+    if (C.piece <= 0) BLZ_HIP(hipEventRecord(S.ev[1], st), BLZ_ERR_UNKNOWN);   // (piecewise task: the FIRST piece's sort stage is done)
     S.accum_timed = true;
-    // ev5..ev6 (or the slice's pair) bracket the dominant kernel alone
-    BLZ_HIP(hipEventRecord(slice < 0 ? S.ev[5] : S.slice_ev[2 * slice], st), BLZ_ERR_UNKNOWN);
-    if (slice < 0)
+    // ev5..ev6 (or the piece's pair) bracket the dominant kernel alone
+    BLZ_HIP(hipEventRecord(C.piece < 0 ? S.ev[5] : S.slice_ev[2 * C.piece], st), BLZ_ERR_UNKNOWN);
+    if (C.piece < 0)
         hipLaunchKernelGGL(k_accumulate<F>, dim3((U + 127) / 128), dim3(128), 0, st, (const uint32_t*)d_pts,
-                           E.sb().entries.as<uint32_t>(), E.sb().off.as<uint32_t>(), E.sb().unit_off.as<uint32_t>(),
-                           E.sb().unit_bucket.as<uint32_t>(), E.sb().unit_order.as<uint32_t>(), E.sb().stats.as<uint32_t>(), P.L,
+                           B.entries.as<uint32_t>(), B.off.as<uint32_t>(), B.unit_off.as<uint32_t>(), B.unit_bucket.as<uint32_t>(),
+                           B.unit_order.as<uint32_t>(), B.stats.as<uint32_t>(), P.L,
                            E.partial.as<uint32_t>());
     else   // piecewise task: single-unit buckets carry their sums in bucket_sums from piece to piece
         hipLaunchKernelGGL(k_accumulate_cont<F>, dim3((U + 127) / 128), dim3(128), 0, st, (const uint32_t*)d_pts,
-                           E.sb().entries.as<uint32_t>(), E.sb().off.as<uint32_t>(), E.sb().unit_off.as<uint32_t>(),
-                           E.sb().unit_bucket.as<uint32_t>(), E.sb().unit_order.as<uint32_t>(), E.sb().stats.as<uint32_t>(), P.L,
-                           E.partial.as<uint32_t>(), E.bucket_sums.as<uint32_t>(), slice == 0 ? 1u : 0u);
-    BLZ_HIP(hipEventRecord(slice < 0 ? S.ev[6] : S.slice_ev[2 * slice + 1], st), BLZ_ERR_UNKNOWN);
+                           B.entries.as<uint32_t>(), B.off.as<uint32_t>(), B.unit_off.as<uint32_t>(), B.unit_bucket.as<uint32_t>(),
+                           B.unit_order.as<uint32_t>(), B.stats.as<uint32_t>(), P.L,
+                           E.partial.as<uint32_t>(), E.bucket_sums.as<uint32_t>(), C.piece == 0 ? 1u : 0u);
+    BLZ_HIP(hipEventRecord(C.piece < 0 ? S.ev[6] : S.slice_ev[2 * C.piece + 1], st), BLZ_ERR_UNKNOWN);
     uint64_t full_bound = (uint64_t)P.npts * P.W / P.L + 1;  // units of length L: at most entries / L
     if (full_bound > U) full_bound = U;
-    const uint32_t* unit_off = E.sb().unit_off.as<uint32_t>();
+    const uint32_t* unit_off = B.unit_off.as<uint32_t>();
     uint32_t* partial = E.partial.as<uint32_t>();
     uint64_t stride = 1;
     for (int pass = 0; pass < T.unit_passes; ++pass, stride *= 16)
-        hipLaunchKernelGGL(k_combine_units<F>, dim3((uint32_t)((full_bound / 16 + 1) * 4 / 128 + 1)), dim3(128), 0, st, unit_off,
-                           E.sb().unit_bucket.as<uint32_t>(), E.sb().unit_order.as<uint32_t>(), E.sb().lenhist.as<uint32_t>() + P.L,
-                           E.sb().stats.as<uint32_t>(), P.L, (uint32_t)stride, T.thr, T.hot_start, partial);
+        hipLaunchKernelGGL(k_combine_units<F>, dim3((uint32_t)((full_bound / 16 + 1) * 4 / 128 + 1)), dim3(128), 0, st, unit_off, B.unit_bucket.as<uint32_t>(),
+                           B.unit_order.as<uint32_t>(), B.lenhist.as<uint32_t>() + P.L, B.stats.as<uint32_t>(), P.L, (uint32_t)stride, T.thr, T.hot_start, partial);
     const dim3 hot_grid((uint32_t)(P.G - T.hot_start)), fold_grid(T.hot_start);   // a block per bucket
     switch (T.hot) {
         case TailPlan::HOT_NONE: break;
@@ -1513,22 +1514,23 @@ int run_accumulate_t(MsmEngine& E, MsmSlot& S, const void* d_pts, uint32_t U, in
 }
 
 template <class F>
-int merge_buckets_t(MsmEngine& E) {
-    const uint64_t G = E.last_plan.G;
-    hipLaunchKernelGGL(k_merge_buckets<F>, dim3((uint32_t)((G + 127) / 128)), dim3(128), 0, E.stream, E.partial.as<uint32_t>(),
-                       E.sb().unit_off.as<uint32_t>(), G, E.bucket_sums.as<uint32_t>());
+int merge_buckets_t(MsmEngine& E, const MsmStep& C) {
+    const uint64_t G = C.P.G;
+    hipLaunchKernelGGL(k_merge_buckets<F>, dim3((uint32_t)((G + 127) / 128)), dim3(128), 0, C.stream, E.partial.as<uint32_t>(),
+                       C.B.unit_off.as<uint32_t>(), G, E.bucket_sums.as<uint32_t>());
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     return BLZ_OK;
 }
 
 // phases 2 - 3: bucket reduce over the sums at sums[unit_off[g]], then the window combine
 template <class F>
-int run_reduce_t(MsmEngine& E, MsmSlot& S, const void* sums, const void* unit_off_v) {
-    hipStream_t st = E.stream;
-    const MsmPlan& P = S.plan;
+int run_reduce_t(MsmEngine& E, const MsmStep& C, const void* sums, const void* unit_off_v) {
+    hipStream_t st = C.stream;
+    MsmSlot& S = C.S;
+    const MsmPlan& P = C.P;
     const TailPlan& T = S.tail;
     const uint32_t* unit_off = (const uint32_t*)unit_off_v;
-    uint32_t* const result = E.slot_result((int)(&S - E.slots));
+    uint32_t* const result = E.slot_result(C.slot);
     BLZ_HIP(hipEventRecord(S.ev[2], st), BLZ_ERR_UNKNOWN);
 
     // ---- phase 2

@@ -501,9 +501,9 @@ static SortGeom make_geom(const MsmPlan& P) {
     return g;
 }
 
-int msm_sort_lds(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits) {
-    const MsmPlan& P = E.last_plan;
-    hipStream_t st = E.sort_st;
+int msm_sort_lds(MsmEngine& E, const MsmStep& C, const void* d_scalars, uint32_t npts, int sbits, LdsSortPass& pass) {
+    const MsmPlan& P = C.P;
+    hipStream_t st = C.sort_stream;
     SortGeom g = make_geom(P);
     if (g.cl > 12 || g.NC > 24576u) return fail(BLZ_ERR_UNKNOWN, "sort geometry out of range (c=%d W=%d)", P.c, P.W);
     // points per block: enough entries per block to amortise the NC-sized LDS sweeps, enough blocks to fill the chip
@@ -519,7 +519,6 @@ int msm_sort_lds(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits) 
     BLZ_TRY(E.inter.reserve(max_entries * 6 + 64));
     uint32_t* inter_idx = E.inter.as<uint32_t>();
     uint16_t* inter_fine = reinterpret_cast<uint16_t*>(inter_idx + max_entries);
-    E.sort_inter_fine = inter_fine;
     uint32_t* coarse_count = E.coarse.as<uint32_t>();
     uint32_t* coarse_off = coarse_count + g.NC;
     BLZ_HIP(hipMemsetAsync(coarse_count, 0, (size_t)g.NC * 4, st), BLZ_ERR_UNKNOWN);
@@ -552,28 +551,25 @@ int msm_sort_lds(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits) 
     uint2* slice_map = E.slice_map.as<uint2>() + 1;             // element 0 holds the slice count
     uint32_t* nslices = E.slice_map.as<uint32_t>();
     hipLaunchKernelGGL(k_slice_map, dim3(1), dim3(SLICEMAP_THREADS), 0, st, coarse_off, g.NC, slice_map, nslices);
-    E.sort_slices = max_slices;
-    E.sort_cl = g.cl;
-    E.sort_nc = g.NC;
+    pass = LdsSortPass{max_slices, g.NC, g.cl, inter_fine};
     hipLaunchKernelGGL(k_fine_count, dim3(max_slices), dim3(FINE_THREADS), (size_t)4 << g.cl, st, inter_fine, coarse_off,
-                       slice_map, nslices, g.cl, E.sb().count.as<uint32_t>());
+                       slice_map, nslices, g.cl, C.B.count.as<uint32_t>());
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     return BLZ_OK;
 }
 
-int msm_sort_lds_scatter(MsmEngine& E) {
-    hipStream_t st = E.sort_st;
-    uint32_t* coarse_off = E.coarse.as<uint32_t>() + E.sort_nc;
+int msm_sort_lds_scatter(MsmEngine& E, const MsmStep& C, const LdsSortPass& pass) {
+    hipStream_t st = C.sort_stream;
+    uint32_t* coarse_off = E.coarse.as<uint32_t>() + pass.nc;
     BLZ_TRY(ensure_dynamic_lds((const void*)k_fine_scatter, 158 * 1024));
     // staging entries per round (6 bytes each): what is left of the LDS after the two per-bucket arrays
-    size_t budget = (size_t)exp_knob("BLAZE_SORT_FS_KB", 157) * 1024 - ((size_t)2 << E.sort_cl) * 4;
+    size_t budget = (size_t)exp_knob("BLAZE_SORT_FS_KB", 157) * 1024 - ((size_t)2 << pass.cl) * 4;
     uint32_t round_cap = (uint32_t)(budget / 6);
     if (round_cap > (uint32_t)FS_ROUND) round_cap = FS_ROUND;
     round_cap &= ~1023u;
-    const size_t lds = ((size_t)2 << E.sort_cl) * 4 + (size_t)round_cap * 6;
-    hipLaunchKernelGGL(k_fine_scatter, dim3(E.sort_slices), dim3(FS_THREADS), lds, st, E.inter.as<uint32_t>(), (const uint16_t*)E.sort_inter_fine, coarse_off,
-                       E.slice_map.as<uint2>() + 1, E.slice_map.as<uint32_t>(), E.sort_cl, round_cap, E.sb().count.as<uint32_t>(),
-                       E.sb().entries.as<uint32_t>());
+    const size_t lds = ((size_t)2 << pass.cl) * 4 + (size_t)round_cap * 6;
+    hipLaunchKernelGGL(k_fine_scatter, dim3(pass.slices), dim3(FS_THREADS), lds, st, E.inter.as<uint32_t>(), pass.inter_fine, coarse_off,
+                       E.slice_map.as<uint2>() + 1, E.slice_map.as<uint32_t>(), pass.cl, round_cap, C.B.count.as<uint32_t>(), C.B.entries.as<uint32_t>());
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     return BLZ_OK;
 }

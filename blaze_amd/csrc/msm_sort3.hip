@@ -780,12 +780,12 @@ static int s3_level1(hipStream_t st, const uint32_t* sc, uint32_t npts, const Ge
 
 // geometry -> tables -> launches, for either kind of plan
 template <class Geom>
-static int s3_enqueue(MsmEngine& E, const Geom& g, const void* d_scalars, uint32_t npts, int sbits) {
+static int s3_enqueue(MsmEngine& E, const MsmStep& C, const Geom& g, const void* d_scalars, uint32_t npts, int sbits) {
     using L2 = typename Geom::L2;
     using Lo = typename L2::Lo;
-    const MsmPlan& P = E.last_plan;
-    hipStream_t st = E.sort_st;
-    MsmEngine::SortBufs& B = E.sb();
+    const MsmPlan& P = C.P;
+    hipStream_t st = C.sort_stream;
+    MsmEngine::SortBufs& B = C.B;
     const uint32_t NB1 = g.NB1, NB2 = (uint32_t)(P.G >> g.bits3());
     const uint64_t max_entries = (uint64_t)npts * P.W;
     const uint32_t max_items = (uint32_t)(max_entries / S3_SLICE2) + NB1 + 1;
@@ -843,9 +843,9 @@ static int s3_enqueue(MsmEngine& E, const Geom& g, const void* d_scalars, uint32
     return BLZ_OK;
 }
 
-int msm_sort3(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits) {
-    const MsmPlan& P = E.last_plan;
-    return P.table ? s3_enqueue(E, s3t_geometry(P, P.npts), d_scalars, npts, sbits) : s3_enqueue(E, s3_geometry(P), d_scalars, npts, sbits);
+int msm_sort3(MsmEngine& E, const MsmStep& C, const void* d_scalars, uint32_t npts, int sbits) {
+    const MsmPlan& P = C.P;
+    return P.table ? s3_enqueue(E, C, s3t_geometry(P, P.npts), d_scalars, npts, sbits) : s3_enqueue(E, C, s3_geometry(P), d_scalars, npts, sbits);
 }
 
 }  // namespace blz

@@ -271,10 +271,10 @@ bool msm_sort_tiny_ok(const MsmPlan& P, uint32_t npts, int sbits) {
     return true;
 }
 
-int msm_sort_tiny(MsmEngine& E, const void* d_scalars, uint32_t npts, int sbits, uint32_t max_units) {
-    const MsmPlan& P = E.last_plan;
-    hipStream_t st = E.sort_st;
-    MsmEngine::SortBufs& B = E.sb();
+int msm_sort_tiny(MsmEngine& E, const MsmStep& C, const void* d_scalars, uint32_t npts, int sbits, uint32_t max_units) {
+    const MsmPlan& P = C.P;
+    hipStream_t st = C.sort_stream;
+    MsmEngine::SortBufs& B = C.B;
     TinyGeom g;
     g.W = P.W;
     g.G = (uint32_t)P.G;

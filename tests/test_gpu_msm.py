@@ -1300,6 +1300,46 @@ def test_dma_pieces_host_buffers(gpu, orc, curve, pf, n, monkeypatch):
     cl.close()
 
 
+def test_lone_piecewise_task_sorts_under_its_own_accumulation(gpu, orc, monkeypatch):
+    """A piecewise task on an otherwise idle handle sorts piece k + 1 on the sort stream underneath the accumulation of piece
+    k, its pieces alternating between its own slot's sort buffers and the other slot's (msm.hip begin(): ping-pong; which
+    buffer set and which stream a piece gets is MsmEngine::step()'s decision).  That path needs a plan the three-level sort
+    accepts - every window of 15 bits or more - which default plans reach only from about 2^19 points up, so the small
+    piecewise tests never take it.  Forced here at an oracle-checkable size: c=15 gives 5000 points 18 uniform windows and
+    18 x 2^14 = 295 K bucket slots.  (a) a lone task: right bytes, and its sorts were hidden; (b) two in flight with different
+    scalars: the first is a ping-pong task again - its first hidden sort waits for the level-0 event of the other slot, whose
+    last task (a) borrowed this slot's buffers - and the second begins while it holds both buffer sets; (c) a lone task after
+    both were collected, back on the slot of (b)'s first."""
+    curve, n = "BLS381", 5000
+    monkeypatch.setenv("BLAZE_MSM_PLAN", "c=15")
+    monkeypatch.setenv("BLAZE_MSM_PIECES", "3")
+    pts, _, _ = orc.input_generator(curve, n, 1, 5150)
+    rng = np.random.default_rng(5150)
+    scs, exps, bufs = [], [], []
+    for _ in range(2):
+        sc = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+        sc[:, 31] &= 0x0F                     # < 2^252: canonical in all three scalar fields
+        scs.append(sc.tobytes())
+        exps.append(orc.msm_pippenger(curve, pts, scs[-1], n, 1, threads=8))
+    for data in (pts, scs[0], scs[1]):
+        b_ = DeviceBuffer(0, len(data))
+        b_.upload(data)
+        bufs.append(b_)
+    dp, ds, ds2 = bufs
+    p = MSMParams(n, None)
+    cl = msm_client(curve, 1)
+    assert run_msm(cl, dp, ds, n) == exps[0]                                   # (a)
+    assert cl.get_api()["sort_hidden"] == 1
+    cl.initialize(p); cl.start_process(); cl.set_data(MSMInput(dp, ds, p))     # (b)
+    cl.initialize(p); cl.start_process(); cl.set_data(MSMInput(dp, ds2, p))
+    cl.wait_result(); assert cl.result().result == exps[0]
+    cl.wait_result(); assert cl.result().result == exps[1]
+    assert run_msm(cl, dp, ds2, n) == exps[1]                                  # (c)
+    cl.close()
+    for b_ in bufs:
+        b_.free()
+
+
 @pytest.mark.parametrize("curve,logn,pf", [("BLS381", 19, 1), ("BLS381", 20, 1), ("BLS377", 22, 1), ("BN254", 21, 1),
                                             ("BN254", 18, 8), ("BN254", 20, 8), ("BLS381", 19, 8)])
 def test_hidden_three_level_sort(gpu, orc, curve, logn, pf, monkeypatch):

@@ -1,5 +1,5 @@
-"""Which kernels the MSM tail launches, shape by shape: runs the shapes of tests/test_gpu_msm.py::test_every_tail_schedule_is_served
-once each (one task at a time, an empty task - k_emit_infinity - in front of every shape as a separator) so that a kernel trace of
+"""Which kernels an MSM task launches, shape by shape: runs the shapes of tests/test_gpu_msm.py::test_every_tail_schedule_is_served
+and a few more (STEP_SHAPES) once each (one task at a time, an empty task - k_emit_infinity - in front of every shape as a separator) so that a kernel trace of
 the run can be cut into per-shape launch sequences and two builds of the library (BLAZE_HIP_LIB) compared:
 
     rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 tools/msm_tail_trace.py          (a run of its own, no counters)
@@ -31,6 +31,14 @@ SHAPES = [
     ("BN254", 1, 1 << 14, "c=18", None),
     ("BN254", 8, 1 << 9, None, None),
 ]
+# ... and beside that mirror, the shapes whose launches depend on which sort buffers and which stream a step is given (MsmEngine::step()):
+# a lone piecewise task that sorts each piece underneath the accumulation of the one before (ping-pong over both slots' buffers,
+# tests/test_gpu_msm.py::test_lone_piecewise_task_sorts_under_its_own_accumulation), and the one-block sort stage of a tiny task
+STEP_SHAPES = [
+    ("BLS381", 1, 5000, "c=15", "3"),
+    ("BLS381", 1, 16, None, None),
+]
+ALL_SHAPES = SHAPES + STEP_SHAPES
 MARKER = "k_emit_infinity"
 
 
@@ -52,7 +60,7 @@ def run_shapes():
         cl.wait_result()
         return cl.result().result
 
-    for curve, pf, n, plan, pieces in SHAPES:
+    for curve, pf, n, plan, pieces in ALL_SHAPES:
         for key, val in (("BLAZE_MSM_PLAN", plan), ("BLAZE_MSM_PIECES", pieces)):
             os.environ.pop(key, None)
             if val:
@@ -84,10 +92,10 @@ def listing(out_dir):
         name = r["Kernel_Name"]
         if MARKER in name:
             shape += 1
-            print("== shape %d: %s pf=%d n=%d plan=%s pieces=%s" % ((shape,) + SHAPES[shape]))
+            print("== shape %d: %s pf=%d n=%d plan=%s pieces=%s" % ((shape,) + ALL_SHAPES[shape]))
         elif shape >= 0:
             print(f"{name.split('(')[0]}  grid {dims(r, 'Grid_Size')}  block {dims(r, 'Workgroup_Size')}")
-    assert shape + 1 == len(SHAPES), f"{shape + 1} separators for {len(SHAPES)} shapes"
+    assert shape + 1 == len(ALL_SHAPES), f"{shape + 1} separators for {len(ALL_SHAPES)} shapes"
 
 
 if __name__ == "__main__":
