@@ -5,6 +5,7 @@
 // a different product of the formula in the same instruction stream; results are exchanged with
 // quad_perm broadcasts (one v_mov_dpp per limb).  Doubling = 3 rounds, addition = 4 rounds.
 // All 4 lanes of a quad must be active and hold identical inputs; outputs are identical on all 4.
+// The tail's algorithms reach both halves of this file through QuadLaw32 / QuadLawRR (ec_law.hip.hpp).
 #pragma once
 #include "ec.hip.hpp"
 #include "ec_rr.hip.hpp"
@@ -124,7 +125,7 @@ __device__ __noinline__ void quad_add(XYZZ<F>& acc, const XYZZ<F>& q, uint32_t l
 // The same quad-cooperative group law on the reduced-radix field (ec_rr.hip.hpp) for the curves that have one.  The tail is
 // a chain of sequential point operations on ONE wave, and a single wave issues a vector instruction every four cycles at
 // best: what counts is the instruction count of a field product - 576 (multiply-add / add-carry pairs) on 32-bit limbs,
-// about 480 on 28-bit limbs.  k_finish is 250 doublings in sequence and dominates the latency of a small MSM (2^13
+// about 480 on 28-bit limbs.  k_finish (horner_walk) is 250 doublings in sequence and dominates the latency of a small MSM (2^13
 // elements: 1.93 of 4.4 ms; 1.56 of 3.9 with this).  Measured and dropped: a product with one accumulator per column
 // (27 independent chains for the scheduler) is no faster - the wave is issue-bound, not latency-bound; splitting a
 // product over the four lanes of a quad saves a quarter of the instructions at best (operand rotation, digit

@@ -1,4 +1,4 @@
-// Row-cooperative XYZZ group law for the one strictly sequential chain of an MSM: k_finish's Horner walk over the windows -
+// Row-cooperative XYZZ group law (RowLaw, ec_law.hip.hpp) for the one strictly sequential chain of an MSM: the Horner walk over the windows (horner_walk, k_finish_row) -
 // ~255 dependent doublings, with a single point in flight.  The quad-cooperative law (ec_quad.hip.hpp) gives that chain one
 // lane per PRODUCT of a formula round; every lane still runs a whole 14 x 14-limb Montgomery product on its own, ~470
 // dependent instructions, and a doubling took ~5 us whatever the chip had free.  Here the 16 lanes of a DPP row hold ONE field

@@ -59,7 +59,7 @@ struct TailTraits {
     bool row = false;         // ... on the loose 28-bit budget: the row law (ec_row.hip.hpp)
     int partial_dwords = 0;   // dwords of one unit / bucket sum in `partial`
 };
-// window table of k_finish: window w owns virtual windows v0 .. v0 + m - 1 and starts at scalar bit `off`
+// window table of k_finish / k_finish_row (horner_walk, msm_impl.hip.hpp): window w owns virtual windows v0 .. v0 + m - 1 and starts at scalar bit `off`
 struct FinishPlan {
     int W, logV;
     uint16_t v0[MSM_MAX_W], off[MSM_MAX_W];   // make_plan keeps m <= 128 and sum m < 2^16 (checked when filled)
@@ -73,7 +73,7 @@ struct TailPlan {
     int unit_passes = 0;
     enum Hot { HOT_NONE, HOT_WAVES8, HOT_ROW } hot = HOT_NONE;   // k_fold_hot / k_fold_hot_row
     // k_combine_buckets (a lane per bucket) / _wave / _row; FOLD_ROW_WEAK leaves the sums in the row law's weakly
-    // normalised form, which k_reduce_level_row alone reads: only in front of a ROW level 0
+    // normalised form, which k_reduce_level_row (reduce_segment on the row law) alone reads: only in front of a ROW level 0
     enum Fold { FOLD_NONE, FOLD_LANE, FOLD_WAVE, FOLD_ROW_STRICT, FOLD_ROW_WEAK } fold = FOLD_NONE;
     // bucket reduce: level l folds M sums per virtual window into T segments of SEG; level 0 stays on the main stream
     struct Level {

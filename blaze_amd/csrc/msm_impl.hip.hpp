@@ -3,11 +3,7 @@
 // instantiations compile in parallel.  See msm.hip for the pipeline overview.
 #pragma once
 #include "msm_engine.hpp"
-#include "ec.hip.hpp"
-#include "ec_rr.hip.hpp"
-#include "ec_quad.hip.hpp"
-#include "ec_row.hip.hpp"
-#include <type_traits>
+#include "ec_law.hip.hpp"
 
 namespace blz {
 
@@ -401,23 +397,6 @@ BLZ_DEV void load_affine(Affine<F>& a, const uint32_t* pts, uint32_t idx) {
     fp_load(a.x, q);
     fp_load(a.y, q + F::N);
 }
-template <class F>
-BLZ_DEV void load_xyzz(XYZZ<F>& a, const uint32_t* base, size_t idx) {
-    const uint32_t* q = base + idx * 4 * F::N;
-    fp_load(a.x, q);
-    fp_load(a.y, q + F::N);
-    fp_load(a.zz, q + 2 * F::N);
-    fp_load(a.zzz, q + 3 * F::N);
-}
-template <class F>
-BLZ_DEV void store_xyzz(uint32_t* base, size_t idx, const XYZZ<F>& a) {
-    uint32_t* q = base + idx * 4 * F::N;
-    fp_store(q, a.x);
-    fp_store(q + F::N, a.y);
-    fp_store(q + 2 * F::N, a.zz);
-    fp_store(q + 3 * F::N, a.zzz);
-}
-
 // The accumulation's gather of unpacked 128-byte points (the BLS base fields), as whole lines through LDS.  load_affine_rr
 // is seven global_load_dwordx4 per lane, each touching 64 lines and 64 pages per wave: 448 line and page look-ups for a
 // wave's 64 points.  Here eight consecutive lanes fetch one point's line, 16 bytes each, straight into LDS
@@ -783,24 +762,15 @@ __global__ __launch_bounds__(128, 3) void k_combine_buckets(const uint32_t* __re
     if (g >= G) return;   // (the host passes G = hot_start when k_fold_hot takes the buckets above)
     const uint32_t u0 = unit_off[g], u1 = unit_off[g + 1];
     if (u1 - u0 < 2 || u1 - u0 > thr) return;
-    if constexpr (USE_RR<F>) {
-        using Q = typename F::RR;
-        XYZZRR<Q> acc, t;
-        ptrr_load(acc, partial, u0);
-        for (uint32_t u = u0 + 1; u < u1; ++u) {
-            ptrr_load(t, partial, u);
-            ptrr_add<Q, 5>(acc, t);
-        }
-        ptrr_store(partial, u0, acc);
-    } else {
-        XYZZ<F> acc, t;
-        load_xyzz(acc, partial, u0);
-        for (uint32_t u = u0 + 1; u < u1; ++u) {
-            load_xyzz(t, partial, u);
-            pt_add_inl<F, 3>(acc, t);
-        }
-        store_xyzz(partial, u0, acc);
+    using Law = LaneLaw<F, 3, 5>;
+    const Law law(0);
+    typename Law::Pt acc, t;
+    law.load(acc, partial, u0);
+    for (uint32_t u = u0 + 1; u < u1; ++u) {
+        law.load(t, partial, u);
+        law.add(acc, t);
     }
+    law.store(partial, u0, acc);
 }
 
 #ifndef BLZ_TAIL_PRIO
@@ -811,63 +781,98 @@ __global__ __launch_bounds__(128, 3) void k_combine_buckets(const uint32_t* __re
 //   F = Sum_t s_t + SEG * Sum_t t * r_t,  r_t = Sum_j A_(t SEG + j),  s_t = Sum_j (j + woff) A_(t SEG + j)
 // outA[t] = r_t (weights t at the next level, woff = 0), outC[t] = Sum C_in + 2^shift * s_t.
 // ------------------------------------------------------------------------------------------------
+// One body for every law (ec_law.hip.hpp): a group of Law::LANES lanes per segment, blocks of 64 lanes.  LEVEL0: the bucket
+// sums sit at inA[unit_off[bucket]] (an empty bucket has none and adds nothing), the weights are i + 1, there is no incoming C
+// and no doubling (inC, shift unused).  Upper levels: weights i, the carried C sums, `shift` doublings.
+template <class Law, bool LEVEL0>
+BLZ_DEV void reduce_segment(const uint32_t* inA, const uint32_t* inC, const uint32_t* unit_off, uint32_t M, uint32_t SEG, uint32_t T, int W,
+                            int shift, uint32_t* outA, uint32_t* outC) {
+    using Pt = typename Law::Pt;
+    const uint32_t gtid = blockIdx.x * 64u + threadIdx.x;
+    const uint32_t tid = Law::LANES == 64 ? blockIdx.x : gtid / Law::LANES;   // (a wave per segment: one wave per block)
+    if (tid >= T * (uint32_t)W) return;
+    const uint32_t w = tid / T, t = tid - w * T;
+    const uint32_t lo = t * SEG;
+    uint32_t hi = lo + SEG;
+    if (hi > M) hi = M;
+    const Law law(gtid % Law::LANES);
+    Pt run, s, cs;
+    law.inf(run);
+    law.inf(s);
+    if constexpr (!LEVEL0) law.inf(cs);
+    for (uint32_t i = hi; i-- > lo;) {
+        const size_t idx = (size_t)w * M + i;
+        if constexpr (LEVEL0) {
+            const uint32_t u0 = unit_off[idx], u1 = unit_off[idx + 1];
+            if (u1 > u0) {   // (uniform over the group)
+                Pt a;
+                law.load(a, inA, u0);
+                law.add(run, a);
+            }
+            law.add(s, run);  // weights i + 1 at the first level
+        } else {
+            Pt a, cc;
+            law.load(a, inA, idx);
+            law.load(cc, inC, idx);
+            law.add(cs, cc);
+            law.add(run, a);
+            if (i != lo) law.add(s, run);  // weights i afterwards
+        }
+    }
+    if constexpr (!LEVEL0) {
+        for (int d = 0; d < shift; ++d) law.dbl(s);
+        law.add(cs, s);
+    }
+    if (!law.owner()) return;
+    law.store(outA, (size_t)w * T + t, run);
+    law.store(outC, (size_t)w * T + t, LEVEL0 ? s : cs);
+}
+
+// The kernels below are reduce_segment on one law each; which of them a level runs is the TailPlan's choice (plan_tail()).
+// 32-bit limbs: level 0 (FIRST) one lane per segment, throughput-bound.  Upper levels: one DPP quad per
+// segment (ec_quad.hip.hpp), because there the sequential chain, not the work, is the cost.
+// The upper levels (and k_finish) are a few waves of sequential work on the tail stream, underneath the next task's
+// accumulation: raised wave priority, or they crawl (k_finish 1.8 ms alone, 3.0 ms underneath) - and the host, which
+// hands out the next-but-one task when this one's result arrives, enqueues that task's hidden sort too late for it
+// to finish before the main stream wants its buckets (2^22: 0.8 ms of idle main stream per MSM).
 template <class F, bool FIRST>
 __global__ __launch_bounds__(64, FIRST ? 2 : 3) void k_reduce_level(const uint32_t* __restrict__ inA, const uint32_t* __restrict__ inC,
                                                      const uint32_t* __restrict__ unit_off, uint32_t M, uint32_t SEG,
                                                      uint32_t T, int W, int shift, uint32_t* __restrict__ outA,
                                                      uint32_t* __restrict__ outC) {
-    // level 0 (FIRST): one lane per segment, throughput-bound.  Upper levels: one DPP quad per
-    // segment (ec_quad.hip.hpp), because there the sequential chain, not the work, is the cost.
-    // The upper levels (and k_finish) are a few waves of sequential work on the tail stream, underneath the next task's
-    // accumulation: raised wave priority, or they crawl (k_finish 1.8 ms alone, 3.0 ms underneath) - and the host, which
-    // hands out the next-but-one task when this one's result arrives, enqueues that task's hidden sort too late for it
-    // to finish before the main stream wants its buckets (2^22: 0.8 ms of idle main stream per MSM).
-    if constexpr (!FIRST) __builtin_amdgcn_s_setprio(BLZ_TAIL_PRIO);
-    const uint32_t gtid = blockIdx.x * 64u + threadIdx.x;
-    const uint32_t tid = FIRST ? gtid : gtid >> 2;
-    const uint32_t ql = gtid & 3u;
-    if (tid >= T * (uint32_t)W) return;
-    uint32_t w = tid / T, t = tid - w * T;
-    uint32_t lo = t * SEG;
-    uint32_t hi = lo + SEG;
-    if (hi > M) hi = M;
-    XYZZ<F> run, s, cs;
-    pt_set_inf(run);
-    pt_set_inf(s);
-    pt_set_inf(cs);
-    for (uint32_t i = hi; i-- > lo;) {
-        XYZZ<F> a;
-        size_t idx = (size_t)w * M + i;
-        if constexpr (FIRST) {
-            uint32_t u0 = unit_off[idx], u1 = unit_off[idx + 1];
+    if constexpr (!FIRST) {
+        __builtin_amdgcn_s_setprio(BLZ_TAIL_PRIO);
+        reduce_segment<QuadLaw32<F>, false>(inA, inC, unit_off, M, SEG, T, W, shift, outA, outC);
+    } else {
+        // (written out: on reduce_segment<LaneLaw32<F, 1>, true> this kernel took two more VGPRs and other spill code.  An empty
+        // bucket adds an infinity here where reduce_segment skips the addition: the same sums.  No call into the shared
+        // out-of-line group law: this kernel has its own register budget, see pt_dbl_val's TAG)
+        const uint32_t tid = blockIdx.x * 64u + threadIdx.x;
+        if (tid >= T * (uint32_t)W) return;
+        const uint32_t w = tid / T, t = tid - w * T;
+        const uint32_t lo = t * SEG;
+        uint32_t hi = lo + SEG;
+        if (hi > M) hi = M;
+        XYZZ<F> run, s;
+        pt_set_inf(run);
+        pt_set_inf(s);
+        for (uint32_t i = hi; i-- > lo;) {
+            XYZZ<F> a;
+            const size_t idx = (size_t)w * M + i;
+            const uint32_t u0 = unit_off[idx], u1 = unit_off[idx + 1];
             if (u1 > u0) load_xyzz(a, inA, u0);
             else pt_set_inf(a);
             pt_add_inl<F, 1>(run, a);
             pt_add_inl<F, 1>(s, run);  // weights i + 1 at the first level
-        } else {
-            load_xyzz(a, inA, idx);
-            XYZZ<F> cc;
-            load_xyzz(cc, inC, idx);
-            quad_add(cs, cc, ql);
-            quad_add(run, a, ql);
-            if (i != lo) quad_add(s, run, ql);  // weights i afterwards
         }
+        store_xyzz(outA, (size_t)w * T + t, run);
+        store_xyzz(outC, (size_t)w * T + t, s);
     }
-    if constexpr (FIRST) {
-        cs = s;  // level 0: shift = 0 and no incoming C (and no call into the shared out-of-line group law:
-                 // this kernel has its own register budget, see pt_dbl_val's TAG)
-    } else {
-        for (int d = 0; d < shift; ++d) quad_dbl(s, ql);
-        quad_add(cs, s, ql);
-        if (ql != 0) return;
-    }
-    store_xyzz(outA, (size_t)w * T + t, run);
-    store_xyzz(outC, (size_t)w * T + t, cs);
 }
 
 // level 0 on the reduced-radix field (ec_rr.hip.hpp): the bucket sums arrive in it straight from k_accumulate, the two
-// running sums stay in it, and only the segment's two results are converted to the 32-bit form the upper levels
-// (DPP quads) work in.  20 % fewer multiply-adds than the 32-bit full add, and no conversion per bucket.
+// running sums stay in it, and so do the segment's two results: the upper levels and k_finish work in the reduced radix too
+// (ec_quad.hip.hpp).  20 % fewer multiply-adds than the 32-bit full add, and no conversion per bucket.
 #ifndef BLZ_REDUCE_RR_WAVES
 #define BLZ_REDUCE_RR_WAVES 2
 #endif
@@ -876,28 +881,7 @@ __global__ __launch_bounds__(64, BLZ_REDUCE_RR_WAVES) void k_reduce_level0_rr(co
                                                                             const uint32_t* __restrict__ unit_off, uint32_t M,
                                                                             uint32_t SEG, uint32_t T, int W,
                                                                             uint32_t* __restrict__ outA, uint32_t* __restrict__ outC) {
-    using Q = typename F::RR;
-    const uint32_t tid = blockIdx.x * 64u + threadIdx.x;
-    if (tid >= T * (uint32_t)W) return;
-    const uint32_t w = tid / T, t = tid - w * T;
-    const uint32_t lo = t * SEG;
-    uint32_t hi = lo + SEG;
-    if (hi > M) hi = M;
-    XYZZRR<Q> run, s;
-    ptrr_set_inf(run);
-    ptrr_set_inf(s);
-    for (uint32_t i = hi; i-- > lo;) {
-        const size_t idx = (size_t)w * M + i;
-        const uint32_t u0 = unit_off[idx], u1 = unit_off[idx + 1];
-        if (u1 > u0) {
-            XYZZRR<Q> a;
-            ptrr_load(a, inA, u0);
-            ptrr_add<Q, 3>(run, a);
-        }
-        ptrr_add<Q, 3>(s, run);  // weights i + 1 at the first level
-    }
-    ptrr_store(outA, (size_t)w * T + t, run);   // the upper levels and k_finish work in the reduced radix too (ec_quad.hip.hpp)
-    ptrr_store(outC, (size_t)w * T + t, s);
+    reduce_segment<LaneLawRR<typename F::RR, 3>, true>(inA, nullptr, unit_off, M, SEG, T, W, 0, outA, outC);
 }
 
 // level 0 with one DPP QUAD per segment (ec_quad.hip.hpp) for the sizes in between: too many segments for a wave each
@@ -907,30 +891,7 @@ template <class F>
 __global__ __launch_bounds__(64, 2) void k_reduce_level0_quad(const uint32_t* __restrict__ inA, const uint32_t* __restrict__ unit_off, uint32_t M,
                                                              uint32_t SEG, uint32_t T, int W, uint32_t* __restrict__ outA,
                                                              uint32_t* __restrict__ outC) {
-    using Q = typename F::RR;
-    const uint32_t gtid = blockIdx.x * 64u + threadIdx.x;
-    const uint32_t tid = gtid >> 2, ql = gtid & 3u;
-    if (tid >= T * (uint32_t)W) return;
-    const uint32_t w = tid / T, t = tid - w * T;
-    const uint32_t lo = t * SEG;
-    uint32_t hi = lo + SEG;
-    if (hi > M) hi = M;
-    XYZZRR<Q> run, s;
-    ptrr_set_inf(run);
-    ptrr_set_inf(s);
-    for (uint32_t i = hi; i-- > lo;) {
-        const size_t idx = (size_t)w * M + i;
-        const uint32_t u0 = unit_off[idx], u1 = unit_off[idx + 1];
-        if (u1 > u0) {   // (uniform over the quad)
-            XYZZRR<Q> a;
-            ptrr_load(a, inA, u0);
-            quadrr_add(run, a, ql);
-        }
-        quadrr_add(s, run, ql);  // weights i + 1 at the first level
-    }
-    if (ql != 0) return;
-    ptrr_store(outA, (size_t)w * T + t, run);
-    ptrr_store(outC, (size_t)w * T + t, s);
+    reduce_segment<QuadLawRR<typename F::RR>, true>(inA, nullptr, unit_off, M, SEG, T, W, 0, outA, outC);
 }
 
 // upper levels on the reduced-radix field: one DPP quad per segment, as k_reduce_level<F, false>, with the quad group law
@@ -939,83 +900,21 @@ template <class F>
 __global__ __launch_bounds__(64, 2) void k_reduce_level_rr(const uint32_t* __restrict__ inA, const uint32_t* __restrict__ inC, uint32_t M,
                                                           uint32_t SEG, uint32_t T, int W, int shift, uint32_t* __restrict__ outA,
                                                           uint32_t* __restrict__ outC) {
-    using Q = typename F::RR;
     __builtin_amdgcn_s_setprio(BLZ_TAIL_PRIO);
-    const uint32_t gtid = blockIdx.x * 64u + threadIdx.x;
-    const uint32_t tid = gtid >> 2, ql = gtid & 3u;
-    if (tid >= T * (uint32_t)W) return;
-    const uint32_t w = tid / T, t = tid - w * T;
-    const uint32_t lo = t * SEG;
-    uint32_t hi = lo + SEG;
-    if (hi > M) hi = M;
-    XYZZRR<Q> run, s, cs;
-    ptrr_set_inf(run);
-    ptrr_set_inf(s);
-    ptrr_set_inf(cs);
-    for (uint32_t i = hi; i-- > lo;) {
-        const size_t idx = (size_t)w * M + i;
-        XYZZRR<Q> a, cc;
-        ptrr_load(a, inA, idx);
-        ptrr_load(cc, inC, idx);
-        quadrr_add(cs, cc, ql);
-        quadrr_add(run, a, ql);
-        if (i != lo) quadrr_add(s, run, ql);  // weights i at the upper levels
-    }
-    for (int d = 0; d < shift; ++d) quadrr_dbl(s, ql);
-    quadrr_add(cs, s, ql);
-    if (ql != 0) return;
-    ptrr_store(outA, (size_t)w * T + t, run);
-    ptrr_store(outC, (size_t)w * T + t, cs);
+    reduce_segment<QuadLawRR<typename F::RR>, false>(inA, inC, nullptr, M, SEG, T, W, shift, outA, outC);
 }
 
 // A level whose segments are FEW (a small task's every level; a large task's last ones): the chain of a segment is what the
 // level costs, and the row law of ec_row.hip.hpp - one point spread over the wave, an addition in ~3 us against the quad law's
-// ~6 and a lone lane's ~12 - runs it two to four times faster: one segment per wave.  Same sums as k_reduce_level0_rr (LEVEL0:
-// bucket sums through unit_off, weights i + 1) and k_reduce_level_rr (weights i, the carried C sums, `shift` doublings).  The
-// results stay in the row law's weakly normalised form, so from the first level that takes this kernel every later level and
-// the Horner walk (k_finish_row) take the row law too (run_reduce_t).
+// ~6 and a lone lane's ~12 - runs it two to four times faster: one segment per wave.  The results stay in the row law's weakly
+// normalised form, so from the first level that takes this kernel every later level and the Horner walk (k_finish_row) take
+// the row law too (run_reduce_t).
 template <class F, bool LEVEL0>
 __global__ __launch_bounds__(64, 4) void k_reduce_level_row(const uint32_t* __restrict__ inA, const uint32_t* __restrict__ inC,
                                                            const uint32_t* __restrict__ unit_off, uint32_t M, uint32_t SEG, uint32_t T, int W,
                                                            int shift, uint32_t* __restrict__ outA, uint32_t* __restrict__ outC) {
-    using Q = typename F::RR;
     __builtin_amdgcn_s_setprio(BLZ_TAIL_PRIO);
-    const uint32_t tid = blockIdx.x;   // (one wave per block)
-    if (tid >= T * (uint32_t)W) return;
-    const uint32_t w = tid / T, t = tid - w * T;
-    const uint32_t lo = t * SEG;
-    uint32_t hi = lo + SEG;
-    if (hi > M) hi = M;
-    const RowCtx<Q> c = row_ctx<Q>();
-    RowPt run, s, cs;
-    rowpt_set_inf(run);
-    rowpt_set_inf(s);
-    rowpt_set_inf(cs);
-    for (uint32_t i = hi; i-- > lo;) {
-        const size_t idx = (size_t)w * M + i;
-        RowPt a;
-        if constexpr (LEVEL0) {
-            const uint32_t u0 = unit_off[idx], u1 = unit_off[idx + 1];
-            if (u1 > u0) {
-                rowpt_load<Q>(c, a, inA, u0);
-                rowpt_add<Q>(c, run, a);
-            }
-            rowpt_add<Q>(c, s, run);
-        } else {
-            RowPt cc;
-            rowpt_load<Q>(c, a, inA, idx);
-            rowpt_load<Q>(c, cc, inC, idx);
-            rowpt_add<Q>(c, cs, cc);
-            rowpt_add<Q>(c, run, a);
-            if (i != lo) rowpt_add<Q>(c, s, run);
-        }
-    }
-    if constexpr (!LEVEL0) {
-        for (int d = 0; d < shift; ++d) rowpt_dbl<Q>(c, s);
-        rowpt_add<Q>(c, cs, s);
-    }
-    rowpt_store<Q>(c, outA, (size_t)w * T + t, run);
-    rowpt_store<Q>(c, outC, (size_t)w * T + t, LEVEL0 ? s : cs);
+    reduce_segment<RowLaw<typename F::RR>, LEVEL0>(inA, inC, unit_off, M, SEG, T, W, shift, outA, outC);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1048,80 +947,63 @@ __device__ void emit_result(uint32_t* out, const XYZZ<F>& p) {
 //   S_w = sum_j C_(v0+j) + V * sum_j j * A_(v0+j),
 // so the result is a Horner evaluation over the terms (off_w + log2 V, sum_j j A_j) and (off_w, sum_j C_j)
 // in descending bit offset (off_(w+1) >= off_w + log2 V + 1, so the order is strict).
-// (the body is written once over "a point type with quad operations": the reduced-radix accumulator for the curves that
-// have one, the 32-bit XYZZ otherwise)
-template <class F>
-struct FinishOps32 {
-    using Pt = XYZZ<F>;
-    static BLZ_DEV void inf(Pt& p) { pt_set_inf(p); }
-    static BLZ_DEV void load(Pt& p, const uint32_t* base, size_t idx) { load_xyzz(p, base, idx); }
-    static BLZ_DEV void add(Pt& a, const Pt& b, uint32_t ql) { quad_add(a, b, ql); }
-    static BLZ_DEV void dbl(Pt& a, uint32_t ql) { quad_dbl(a, ql); }
-    static BLZ_DEV void to32(XYZZ<F>& o, const Pt& p) { o = p; }
-};
-template <class F>
-struct FinishOpsRR {
-    using Q = typename F::RR;
-    using Pt = XYZZRR<Q>;
-    static BLZ_DEV void inf(Pt& p) { ptrr_set_inf(p); }
-    static BLZ_DEV void load(Pt& p, const uint32_t* base, size_t idx) { ptrr_load(p, base, idx); }
-    static BLZ_DEV void add(Pt& a, const Pt& b, uint32_t ql) { quadrr_add(a, b, ql); }
-    static BLZ_DEV void dbl(Pt& a, uint32_t ql) { quadrr_dbl(a, ql); }
-    static BLZ_DEV void to32(XYZZ<F>& o, const Pt& p) { ptrr_to_xyzz32<F>(o, p); }
-};
-template <class F>
-using FinishOps = std::conditional_t<USE_RR<F>, FinishOpsRR<F>, FinishOps32<F>>;
-
-template <class F>
-__global__ __launch_bounds__(64, USE_RR<F> ? 2 : 3) void k_finish(const uint32_t* __restrict__ vsumA, const uint32_t* __restrict__ vsumC,
-                                                  FinishPlan fp, uint32_t* __restrict__ out) {
-    // one wave; every DPP quad runs the same chain cooperatively (ec_quad.hip.hpp), lane 0 emits
-    if (blockIdx.x != 0) return;
-    __builtin_amdgcn_s_setprio(BLZ_TAIL_PRIO);   // (see k_reduce_level)
-    using Ops = FinishOps<F>;
-    using Pt = typename Ops::Pt;
-    const uint32_t ql = threadIdx.x & 3u;
+// (the body is written once over a cooperative law, ec_law.hip.hpp: every group of the wave runs the same chain, lane 0 emits)
+template <class F, class Law>
+BLZ_DEV void horner_walk(const uint32_t* vsumA, const uint32_t* vsumC, const FinishPlan& fp, uint32_t* out) {
+    using Pt = typename Law::Pt;
+    const Law law(threadIdx.x % Law::LANES);
     Pt acc;
-    Ops::inf(acc);
+    law.inf(acc);
     int pos = 0;
     bool started = false;
     for (int w = fp.W - 1; w >= 0; --w) {
         const int v0 = fp.v0[w], m = fp.m[w], off = fp.off[w];
         if (m > 1) {
             Pt t, u;
-            Ops::inf(t);
-            Ops::inf(u);
+            law.inf(t);
+            law.inf(u);
             for (int j = m - 1; j >= 1; --j) {
                 Pt a;
-                Ops::load(a, vsumA, (size_t)(v0 + j));
-                Ops::add(t, a, ql);
-                Ops::add(u, t, ql);
+                law.load(a, vsumA, (size_t)(v0 + j));
+                law.add(t, a);
+                law.add(u, t);
             }
             const int o2 = off + fp.logV;
-            if (started) for (int d = 0; d < pos - o2; ++d) Ops::dbl(acc, ql);
-            Ops::add(acc, u, ql);
+            if (started) for (int d = 0; d < pos - o2; ++d) law.dbl(acc);
+            law.add(acc, u);
             pos = o2;
             started = true;
         }
         Pt cs;
-        Ops::load(cs, vsumC, (size_t)v0);
+        law.load(cs, vsumC, (size_t)v0);
         for (int j = 1; j < m; ++j) {
             Pt a;
-            Ops::load(a, vsumC, (size_t)(v0 + j));
-            Ops::add(cs, a, ql);
+            law.load(a, vsumC, (size_t)(v0 + j));
+            law.add(cs, a);
         }
-        if (started) for (int d = 0; d < pos - off; ++d) Ops::dbl(acc, ql);
-        Ops::add(acc, cs, ql);
+        if (started) for (int d = 0; d < pos - off; ++d) law.dbl(acc);
+        law.add(acc, cs);
         pos = off;
         started = true;
     }
     // scalar-range tasks: the lowest window starts at bit_lo of the scalar, the partial result carries that weight
-    for (int d = 0; d < pos; ++d) Ops::dbl(acc, ql);
+    for (int d = 0; d < pos; ++d) law.dbl(acc);
+    const auto r = law.to_lane(acc);   // (every lane takes part: the row law's limbs meet in LDS)
     if (threadIdx.x == 0) {
         XYZZ<F> o;
-        Ops::to32(o, acc);
+        to_xyzz32<F>(o, r);
         emit_result(out, o);
     }
+}
+
+// one wave; every DPP quad runs the same chain cooperatively (ec_quad.hip.hpp): the reduced-radix accumulator for the curves
+// that have one, the 32-bit XYZZ otherwise
+template <class F>
+__global__ __launch_bounds__(64, USE_RR<F> ? 2 : 3) void k_finish(const uint32_t* __restrict__ vsumA, const uint32_t* __restrict__ vsumC,
+                                                  FinishPlan fp, uint32_t* __restrict__ out) {
+    if (blockIdx.x != 0) return;
+    __builtin_amdgcn_s_setprio(BLZ_TAIL_PRIO);   // (see k_reduce_level)
+    horner_walk<F, QuadLaw<F>>(vsumA, vsumC, fp, out);
 }
 
 // The same walk with ONE point spread over the wave (ec_row.hip.hpp: a limb per lane, the four products of a formula round on
@@ -1130,53 +1012,9 @@ __global__ __launch_bounds__(64, USE_RR<F> ? 2 : 3) void k_finish(const uint32_t
 template <class F>
 __global__ __launch_bounds__(64, 2) void k_finish_row(const uint32_t* __restrict__ vsumA, const uint32_t* __restrict__ vsumC, FinishPlan fp,
                                                       uint32_t* __restrict__ out) {
-    using Q = typename F::RR;
     if (blockIdx.x != 0) return;
     __builtin_amdgcn_s_setprio(BLZ_TAIL_PRIO);
-    __shared__ uint32_t sh[4][16];
-    const RowCtx<Q> c = row_ctx<Q>();
-    RowPt acc;
-    rowpt_set_inf(acc);
-    int pos = 0;
-    bool started = false;
-    for (int w = fp.W - 1; w >= 0; --w) {
-        const int v0 = fp.v0[w], m = fp.m[w], off = fp.off[w];
-        if (m > 1) {
-            RowPt t, u;
-            rowpt_set_inf(t);
-            rowpt_set_inf(u);
-            for (int j = m - 1; j >= 1; --j) {
-                RowPt a;
-                rowpt_load<Q>(c, a, vsumA, (size_t)(v0 + j));
-                rowpt_add<Q>(c, t, a);
-                rowpt_add<Q>(c, u, t);
-            }
-            const int o2 = off + fp.logV;
-            if (started) for (int d = 0; d < pos - o2; ++d) rowpt_dbl<Q>(c, acc);
-            rowpt_add<Q>(c, acc, u);
-            pos = o2;
-            started = true;
-        }
-        RowPt cs;
-        rowpt_load<Q>(c, cs, vsumC, (size_t)v0);
-        for (int j = 1; j < m; ++j) {
-            RowPt a;
-            rowpt_load<Q>(c, a, vsumC, (size_t)(v0 + j));
-            rowpt_add<Q>(c, cs, a);
-        }
-        if (started) for (int d = 0; d < pos - off; ++d) rowpt_dbl<Q>(c, acc);
-        rowpt_add<Q>(c, acc, cs);
-        pos = off;
-        started = true;
-    }
-    for (int d = 0; d < pos; ++d) rowpt_dbl<Q>(c, acc);
-    XYZZRR<Q> r;
-    rowpt_export<Q>(c, acc, sh, r);
-    if (threadIdx.x == 0) {
-        XYZZ<F> o;
-        ptrr_to_xyzz32<F>(o, r);
-        emit_result(out, o);
-    }
+    horner_walk<F, RowLaw<typename F::RR>>(vsumA, vsumC, fp, out);
 }
 
 template <class F>
@@ -1279,17 +1117,7 @@ __global__ __launch_bounds__(64, 2) void k_combine_buckets_wave(const uint32_t* 
     XYZZRR<Q> acc;
     if (lane < U) ptrr_load(acc, partial, u0 + lane);
     else ptrr_set_inf(acc);
-    for (uint32_t r = 1; r < U && r < 64; r <<= 1) {
-        XYZZRR<Q> o;
-#pragma unroll
-        for (int i = 0; i < Q::NL; ++i) {
-            o.x.v[i] = __shfl_down(acc.x.v[i], r, 64);
-            o.y.v[i] = __shfl_down(acc.y.v[i], r, 64);
-            o.zz.v[i] = __shfl_down(acc.zz.v[i], r, 64);
-            o.zzz.v[i] = __shfl_down(acc.zzz.v[i], r, 64);
-        }
-        if ((lane & (2u * r - 1u)) == 0 && lane + r < U) ptrr_add<Q, 6>(acc, o);
-    }
+    for (uint32_t r = 1; r < U && r < 64; r <<= 1) ptrr_shuffle_round<Q, 6>(acc, lane, r, U);
     if (lane == 0) ptrr_store(partial, u0, acc);
 }
 
@@ -1376,17 +1204,7 @@ __global__ __launch_bounds__(512, 1) void k_fold_hot(const uint32_t* __restrict_
         XYZZRR<Q> acc;
         if (lane < cnt) ptrr_load(acc, partial, u0 + base + lane);
         else ptrr_set_inf(acc);
-        for (uint32_t r = 1; r < cnt; r <<= 1) {
-            XYZZRR<Q> o;
-#pragma unroll
-            for (int i = 0; i < Q::NL; ++i) {
-                o.x.v[i] = __shfl_down(acc.x.v[i], r, 64);
-                o.y.v[i] = __shfl_down(acc.y.v[i], r, 64);
-                o.zz.v[i] = __shfl_down(acc.zz.v[i], r, 64);
-                o.zzz.v[i] = __shfl_down(acc.zzz.v[i], r, 64);
-            }
-            if ((lane & (2u * r - 1u)) == 0 && lane + r < cnt) ptrr_add<Q, 7>(acc, o);
-        }
+        for (uint32_t r = 1; r < cnt; r <<= 1) ptrr_shuffle_round<Q, 7>(acc, lane, r, cnt);
         if (lane == 0) ptrr_add<Q, 7>(tot, acc);
     }
     if (lane == 0) ptrr_store(sh, wave, tot);
@@ -1395,17 +1213,7 @@ __global__ __launch_bounds__(512, 1) void k_fold_hot(const uint32_t* __restrict_
     XYZZRR<Q> acc;
     if (lane < 8) ptrr_load(acc, sh, lane);
     else ptrr_set_inf(acc);
-    for (uint32_t r = 1; r < 8; r <<= 1) {
-        XYZZRR<Q> o;
-#pragma unroll
-        for (int i = 0; i < Q::NL; ++i) {
-            o.x.v[i] = __shfl_down(acc.x.v[i], r, 64);
-            o.y.v[i] = __shfl_down(acc.y.v[i], r, 64);
-            o.zz.v[i] = __shfl_down(acc.zz.v[i], r, 64);
-            o.zzz.v[i] = __shfl_down(acc.zzz.v[i], r, 64);
-        }
-        if ((lane & (2u * r - 1u)) == 0 && lane + r < 8) ptrr_add<Q, 7>(acc, o);
-    }
+    for (uint32_t r = 1; r < 8; r <<= 1) ptrr_shuffle_round<Q, 7>(acc, lane, r, 8u);
     if (lane == 0) ptrr_store(partial, u0, acc);
 }
 
@@ -1419,20 +1227,13 @@ __global__ __launch_bounds__(128, 2) void k_merge_buckets(const uint32_t* __rest
     if (g >= G) return;
     const uint32_t u0 = unit_off[g], u1 = unit_off[g + 1];
     if (u1 - u0 < 2 || u1 < u0) return;
-    if constexpr (USE_RR<F>) {
-        using Q = typename F::RR;
-        XYZZRR<Q> a, b;
-        ptrr_load(a, sums, g);
-        ptrr_load(b, partial, u0);
-        ptrr_add<Q, 4>(a, b);
-        ptrr_store(sums, g, a);
-    } else {
-        XYZZ<F> a, b;
-        load_xyzz(a, sums, g);
-        load_xyzz(b, partial, u0);
-        pt_add_inl<F, 2>(a, b);
-        store_xyzz(sums, g, a);
-    }
+    using Law = LaneLaw<F, 2, 4>;
+    const Law law(0);
+    typename Law::Pt a, b;
+    law.load(a, sums, g);
+    law.load(b, partial, u0);
+    law.add(a, b);
+    law.store(sums, g, a);
 }
 
 // The launchers below only launch what the task's TailPlan names (plan_tail(), msm.hip); a kernel the field does not have is an error.
