@@ -639,8 +639,8 @@ int blz_ntt_reset(blz_ntt* h) {
     return BLZ_OK;
 }
 
-// Ops on the transform buffers (include/blaze_hip.h: blz_ntt_vec_op, _reduce, _scan, _horner, _gather, _spmv; kernels and their workspace:
-// ntt_vec.hip.hpp, ntt_fold.hip.hpp, ntt_horner.hip.hpp, ntt_gather.hip.hpp, ntt_spmv.hip.hpp).  An op runs like a transform: compute stream, ev0 .. ev1, finished by
+// Ops on the transform buffers (include/blaze_hip.h: blz_ntt_vec_op, _reduce, _scan, _horner, _gather, _spmv, _mle_*; kernels and their workspace:
+// ntt_vec.hip.hpp, ntt_fold.hip.hpp, ntt_horner.hip.hpp, ntt_gather.hip.hpp, ntt_spmv.hip.hpp, ntt_mle.hip.hpp).  An op runs like a transform: compute stream, ev0 .. ev1, finished by
 // blz_ntt_wait_result.  Everything is checked before anything is enqueued and nothing waits for the device.  The workspace is
 // `scratch`, n x 32 bytes that only a transform or an op of this handle uses - and none can be in flight.  An entry point
 // checks its own arguments, then walks this protocol: begin, resolve, enqueue.
@@ -703,21 +703,46 @@ struct NttVecCall {
         return BLZ_OK;
     }
 
-    // The operands in order, then the one-word output (d_out / d_total; nullptr: none): 32 bytes checked like an operand's
-    // d_ptr, and kept off the words of every d_ptr operand.
-    int resolve(std::initializer_list<Operand> ops, const char* out_name = nullptr, void* d_out = nullptr) {
+    // The operands in order, then the output words (d_out / d_total; nullptr: none): out_words x 32 bytes checked like an
+    // operand's d_ptr, and kept off the words of every d_ptr operand.
+    int resolve(std::initializer_list<Operand> ops, const char* out_name = nullptr, void* d_out = nullptr, uint64_t out_words = 1) {
         for (const Operand& o : ops)
             if (o.v) BLZ_TRY(operand(o.name, o.v, *o.out, o.max_count ? o.max_count : n));
         if (!d_out) return BLZ_OK;
-        const blz_vec_arg as_arg{d_out, 0u, 0u, 1u};
-        NttVecArg unused{};
-        BLZ_TRY(operand(out_name, &as_arg, unused, n));
+        char who[48];
+        snprintf(who, sizeof who, "operand %s", out_name);
+        BLZ_TRY(device_range(who, "d_ptr", d_out, out_words * 32, 16, out_words, "elements"));
         for (const Operand& o : ops) {
             if (!o.v || !o.v->d_ptr) continue;
             const char *lo = (const char*)o.v->d_ptr, *hi = lo + o.v->count * 32, *q = (const char*)d_out;
-            if (q < hi && q + 32 > lo) return fail(BLZ_ERR_INVALID_PARAM, "%s overlaps the words of a d_ptr operand", out_name);
+            if (q < hi && q + out_words * 32 > lo) return fail(BLZ_ERR_INVALID_PARAM, "%s overlaps the words of a d_ptr operand", out_name);
         }
         return BLZ_OK;
+    }
+
+    // A destination that may be the caller's device words (the multilinear ops): an operand's checks - a transform buffer, or
+    // `count` device words, a power of two up to n - and room for the out_len words the op writes from its start.  buf: the
+    // transform buffer it names, -1 for device words
+    int destination(const blz_vec_arg* v, uint64_t out_len, uint32_t*& words, int& buf) {
+        NttVecArg d{};
+        BLZ_TRY(operand("dst", v, d, n));
+        if (d.mask + 1 < out_len)
+            return fail(BLZ_ERR_INVALID_PARAM, "operand dst: count %llu is below the %llu words the op writes", (unsigned long long)(d.mask + 1),
+                        (unsigned long long)out_len);
+        words = const_cast<uint32_t*>(d.p);
+        buf = v->d_ptr ? -1 : (int)v->buf;
+        return BLZ_OK;
+    }
+    // the live length of a multilinear op: 2^m words, at least one pair, at most the handle's n
+    int live_length(uint64_t len) const {
+        if (len < 2 || (len & (len - 1)) != 0 || len > n)
+            return fail(BLZ_ERR_INVALID_PARAM, "len %llu: the live length is 2^m with 2 <= len <= %llu", (unsigned long long)len, (unsigned long long)n);
+        return BLZ_OK;
+    }
+    // [p, p + words x 32 bytes) meets [q, q + qwords x 32 bytes)
+    static bool words_meet(const void* p, uint64_t words, const void* q, uint64_t qwords) {
+        const char *a = (const char*)p, *b = (const char*)q;
+        return a < b + qwords * 32 && b < a + words * 32;
     }
 
     // buf_dst: the transform buffer the op writes (dispatch is handed its words), -1: none
@@ -854,6 +879,76 @@ int blz_ntt_vec_spmv(blz_ntt* h, size_t buf_dst, const blz_vec_arg* x, const blz
         if (m->nnz == 0 || m->rows == 0) return BLZ_OK;
         return h->ops->vec_spmv(h->stream, dst, vx, m->d_row_ptr, m->d_col, (const uint32_t*)m->d_val, m->rows, m->nnz, call.n, call.ws);
     });
+}
+
+// Multilinear tables (ntt_mle.hip.hpp).  The first ops whose destination may be the caller's device words, and the first that
+// write less than a buffer: out_len words from the start of the destination and not a byte more.  In place (the destination
+// starts where the source starts) the default pairing needs nothing; BLZ_MLE_LOW takes the gather's detour through `scratch`,
+// len / 2 words each way.
+int blz_ntt_vec_mle_fold(blz_ntt* h, uint32_t flags, const blz_vec_arg* dst, const blz_vec_arg* a, const blz_vec_arg* r, uint64_t len) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (flags & ~BLZ_MLE_LOW) return fail(BLZ_ERR_INVALID_PARAM, "unknown multilinear flags 0x%x", flags);
+    if (!dst || !a || !r) return fail(BLZ_ERR_INVALID_PARAM, "a multilinear fold takes dst, a and r");
+    if (!r->d_ptr || r->count != 1)
+        return fail(BLZ_ERR_INVALID_PARAM, "a multilinear fold takes the challenge as one device word: r.d_ptr != NULL, r.count == 1");
+    NttVecCall call{h};
+    BLZ_TRY(call.live_length(len));
+    BLZ_TRY(call.begin());
+    NttVecArg va{}, vr{};
+    BLZ_TRY(call.resolve({{"a", a, &va}, {"r", r, &vr}}));
+    const uint64_t half = len >> 1, count = va.mask + 1;
+    uint32_t* d = nullptr;
+    int buf = -1;
+    BLZ_TRY(call.destination(dst, half, d, buf));
+    const bool in_place = d == va.p;
+    if (!in_place && NttVecCall::words_meet(d, half, va.p, std::min(count, len)))
+        return fail(BLZ_ERR_INVALID_PARAM, "dst overlaps the words of a without starting where they start");
+    if (in_place && count < len)
+        return fail(BLZ_ERR_INVALID_PARAM, "dst names a's %llu words, read periodically over len %llu: a periodic source cannot be folded in place",
+                    (unsigned long long)count, (unsigned long long)len);
+    if (NttVecCall::words_meet(vr.p, 1, d, half)) return fail(BLZ_ERR_INVALID_PARAM, "r lies in the words dst receives");
+    return call.enqueue(buf, [&](uint32_t*) -> int {
+        const bool detour = in_place && (flags & BLZ_MLE_LOW);
+        BLZ_TRY(h->ops->vec_mle_fold(h->stream, flags, detour ? call.ws : d, va, vr.p, len));
+        if (detour) BLZ_HIP(hipMemcpyAsync(d, call.ws, half * 32, hipMemcpyDeviceToDevice, h->stream), BLZ_ERR_UNKNOWN);
+        return BLZ_OK;
+    });
+}
+
+int blz_ntt_vec_mle_round(blz_ntt* h, uint32_t flags, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c, uint32_t points,
+                          uint64_t len, void* d_out) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (flags & ~BLZ_MLE_LOW) return fail(BLZ_ERR_INVALID_PARAM, "unknown multilinear flags 0x%x", flags);
+    if (!a || (c && !b)) return fail(BLZ_ERR_INVALID_PARAM, "a round polynomial takes operands a, then b, then c: %s", !a ? "a is NULL" : "b is NULL while c is set");
+    if (points < 1 || points > 4) return fail(BLZ_ERR_INVALID_PARAM, "points %u is not in [1, 4]", points);
+    if (!d_out) return fail(BLZ_ERR_INVALID_PARAM, "null d_out");
+    NttVecCall call{h};
+    BLZ_TRY(call.live_length(len));
+    BLZ_TRY(call.begin());
+    NttVecArg va{}, vb{}, vc{};
+    BLZ_TRY(call.resolve({{"a", a, &va}, {"b", b, &vb}, {"c", c, &vc}}, "d_out", d_out, points));
+    const int k = c ? 3 : b ? 2 : 1;
+    return call.enqueue(-1, [&](uint32_t*) {
+        return h->ops->vec_mle_round(h->stream, flags, (uint32_t*)d_out, k, va, b ? vb : va, c ? vc : va, points, len, call.ws);
+    });
+}
+
+int blz_ntt_vec_mle_eq(blz_ntt* h, const blz_vec_arg* dst, const void* d_point, uint32_t m) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (!dst) return fail(BLZ_ERR_INVALID_PARAM, "an equality table takes dst");
+    if (m > (uint32_t)h->logn) return fail(BLZ_ERR_INVALID_PARAM, "m %u is above the handle's log_size %d", m, h->logn);
+    if (!d_point && m > 0) return fail(BLZ_ERR_INVALID_PARAM, "null d_point with m %u", m);
+    NttVecCall call{h};
+    BLZ_TRY(call.begin());
+    const uint64_t out_len = 1ull << m;
+    uint32_t* d = nullptr;
+    int buf = -1;
+    BLZ_TRY(call.destination(dst, out_len, d, buf));
+    if (m > 0) {
+        BLZ_TRY(call.device_range("the point", "d_point", d_point, (uint64_t)m * 32, 16, m, "elements"));
+        if (NttVecCall::words_meet(d_point, m, d, out_len)) return fail(BLZ_ERR_INVALID_PARAM, "d_point lies in the words dst receives");
+    }
+    return call.enqueue(buf, [&](uint32_t*) { return h->ops->vec_mle_eq(h->stream, d, (const uint32_t*)d_point, m, call.ws); });
 }
 
 int blz_ntt_stream(blz_ntt* h, void** hip_stream, int* device_id) {

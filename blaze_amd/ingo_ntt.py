@@ -45,6 +45,7 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
     SCAN_SUM, SCAN_PROD = range(2)                  # enum blz_scan_op
     SCAN_EXCLUSIVE = 1                              # BLZ_SCAN_EXCLUSIVE
     HORNER_EXCLUSIVE, HORNER_REVERSE = 1, 2         # BLZ_HORNER_*
+    MLE_LOW = 1                                     # BLZ_MLE_LOW
 
     def __init__(self, _ptype: NTT, dclient: DriverClient, log_size: int = NTT_LOG_SIZE, inverse: bool = False,
                  field: str = "BLS381", flags: int = 0, root: Optional[int] = None):
@@ -257,6 +258,51 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         permutation held as an index table.  A vec_spmv without row_ptr."""
         self.vec_spmv(dst, x, col, val=val)
         self._vec_keep = (x, col, val)
+
+    def _mle_len(self, length, *tables) -> int:
+        """The live length of a multilinear op: `length`, or the shortest table named (a transform buffer holds n words)."""
+        if length is not None:
+            return int(length)
+        n = 1 << self.log_size
+        return min(x.nbytes // NTT_WORD_SIZE if isinstance(x, DeviceBuffer) else n for x in tables)
+
+    def vec_mle_fold(self, dst, a, r: DeviceBuffer, length: Optional[int] = None, low: bool = False) -> None:
+        """Bind one variable of a multilinear table (blz_ntt_vec_mle_fold): dst[p] = lo + r (hi - lo) for p < length / 2, with
+        (lo, hi) = (a[p], a[p + length / 2]) - the top variable - or, low=True, (a[2p], a[2p + 1]) - variable 0.  `dst` is an int
+        (a transform buffer) or a DeviceBuffer (device words); exactly length / 2 words of it are written, every other byte keeps
+        its value.  `dst` may be `a` itself (in place).  `r` is a one-word DeviceBuffer (scalar()) the host never reads;
+        length=None means all of `a`.  Finished by wait_result()."""
+        vd, va, vr = self._vec_arg(dst), self._vec_arg(a), self._vec_arg(r)
+        check(lib().blz_ntt_vec_mle_fold(self._h, self.MLE_LOW if low else 0, *[None if v is None else C.byref(v) for v in (vd, va, vr)],
+                                         self._mle_len(length, a)))
+        self._vec_keep = (dst, a, r)
+
+    def vec_mle_round(self, a, b=None, c=None, points: Optional[int] = None, length: Optional[int] = None, low: bool = False,
+                      out: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """One round polynomial of a sumcheck (blz_ntt_vec_mle_round): out[t] = sum over p < length / 2 of the product over the k
+        tables given (a, then b, then c) of lo + t (hi - lo), for t = 0 .. points - 1, pairing as in vec_mle_fold.  points (1 .. 4)
+        defaults to k + 1, the number of values that determines the polynomial.  Returns the DeviceBuffer of points x 32 bytes the
+        canonical values land in (`out`, or a fresh one) once wait_result() has finished the op; nothing else is written."""
+        k = 1 + (b is not None) + (c is not None)
+        points = k + 1 if points is None else int(points)
+        if out is None:
+            out = DeviceBuffer(self.driver_client.id, NTT_WORD_SIZE * max(points, 1))
+        args = [self._vec_arg(x) for x in (a, b, c)]
+        check(lib().blz_ntt_vec_mle_round(self._h, self.MLE_LOW if low else 0, *[None if v is None else C.byref(v) for v in args], points,
+                                          self._mle_len(length, *[x for x in (a, b, c) if x is not None]), out.ptr))
+        self._vec_keep = (a, b, c, out)
+        return out
+
+    def vec_mle_eq(self, dst, point: Optional[DeviceBuffer], m: Optional[int] = None) -> None:
+        """The equality table (blz_ntt_vec_mle_eq): dst[p] = prod over i < m of (x_i tau_i + (1 - x_i)(1 - tau_i)) for p < 2^m, x_i
+        bit i of p and tau_i word i of the DeviceBuffer `point` (m = nbytes / 32 unless `m` says less; m = 0, for which point may
+        be None, writes the single word 1).  `dst` is an int (a transform buffer) or a DeviceBuffer; exactly 2^m words of it are
+        written.  The host never reads the point.  Finished by wait_result()."""
+        vd = self._vec_arg(dst)
+        if m is None:
+            m = 0 if point is None else point.nbytes // NTT_WORD_SIZE
+        check(lib().blz_ntt_vec_mle_eq(self._h, None if vd is None else C.byref(vd), None if point is None else point.ptr, int(m)))
+        self._vec_keep = (dst, point)
 
     def scalar(self, value: int) -> DeviceBuffer:
         """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""

@@ -297,6 +297,19 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
     void vec_index(size_t dst, const blz_vec_arg* x, const uint32_t* d_col, uint64_t count, const void* d_val = nullptr) {
         vec_spmv(dst, x, csr(nullptr, d_col, d_val, count, count));
     }
+    // multilinear tables (blz_ntt_vec_mle_fold / _round / _eq): the steps of a sumcheck round on tables of live length len = 2^m.
+    // vec_mle_fold: dst[p] = lo + r (hi - lo), p < len / 2, pairs (a[p], a[p + len / 2]) or with BLZ_MLE_LOW (a[2p], a[2p + 1]); dst
+    // is buffer(i) or words(p, count) and may be a (in place); r one device word.  vec_mle_round: d_out[t] = sum over the pairs of
+    // the product over the operands given (a, b, c; nullptr: not taken) of lo + t (hi - lo), t < points (default: operands + 1).
+    // vec_mle_eq: dst[p] = eq(point, p), p < 2^m, the point m device words.  Exactly the words named are written
+    void vec_mle_fold(const blz_vec_arg* dst, const blz_vec_arg* a, const blz_vec_arg* r, uint64_t len, uint32_t flags = 0) {
+        check(blz_ntt_vec_mle_fold(h_, flags, dst, a, r, len));
+    }
+    void vec_mle_round(const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c, uint64_t len, void* d_out, uint32_t points = 0,
+                       uint32_t flags = 0) {
+        check(blz_ntt_vec_mle_round(h_, flags, a, b, c, points ? points : 2u + (b ? 1u : 0u) + (c ? 1u : 0u), len, d_out));
+    }
+    void vec_mle_eq(const blz_vec_arg* dst, const void* d_point, uint32_t m) { check(blz_ntt_vec_mle_eq(h_, dst, d_point, m)); }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

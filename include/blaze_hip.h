@@ -574,6 +574,54 @@ typedef struct blz_vec_csr {
     uint64_t        nnz;
 } blz_vec_csr;                 /* 40 bytes */
 int blz_ntt_vec_spmv(blz_ntt* h, size_t buf_dst, const blz_vec_arg* x, const blz_vec_csr* m);
+/* Multilinear tables on resident buffers: the three steps a sumcheck prover (Spartan, HyperPlonk, GKR) repeats log n times on
+ * the vectors blz_ntt_vec_spmv produces - bind a variable, take the round polynomial, build eq(tau, .).  A multilinear polynomial
+ * in m variables is its 2^m values on the hypercube, by buffer POSITION p = sum x_i 2^i (the BLZ_NTT_BITREV_* flags and the coset
+ * shift play no part); len = 2^m is the live length of a call, 2 <= len <= n, and may shrink from call to call.
+ *   blz_ntt_vec_mle_fold   dst[p] = lo + r (hi - lo) for p < len / 2, with (lo, hi) = (a[p], a[p + len / 2]): the TOP variable is
+ *                          bound to r; with BLZ_MLE_LOW (lo, hi) = (a[2p], a[2p + 1]): variable 0 is bound.  out_len = len / 2.
+ *   blz_ntt_vec_mle_round  out[t] = sum_{p < len / 2} prod_{j < k} (lo_j + t (hi_j - lo_j)) for t = 0 .. points - 1: the round
+ *                          polynomial of the product of k tables at the points 0, 1, 2, 3; pairing as in the fold.  k = 1 .. 3 is
+ *                          the number of operands, given as a, then b, then c, the ones not taken NULL (b NULL with c set is
+ *                          refused); the same table may be named twice.  points = 1 .. 4 is independent of k: a gate that is a
+ *                          sum of products of different degrees is one call per product at the same `points`, and the outputs add.
+ *                          out[0] + out[1] is the sum (k = 1) or the dot product (k = 2) of the live prefix.
+ *   blz_ntt_vec_mle_eq     dst[p] = prod_{i < m} (x_i tau_i + (1 - x_i)(1 - tau_i)) for p < 2^m, tau_i = word i of d_point, x_i =
+ *                          bit i of p.  0 <= m <= log_size; m = 0 writes the single word 1.  out_len = 2^m.
+ *   Values: every input word (tables, r, the point) is any 256-bit value and counts as its residue; every output word is canonical,
+ *   little-endian.
+ *   Table operands: those of blz_ntt_vec_op, checked by the same code - a transform buffer, or `count` device words (a power of
+ *   two <= n) read at p & (count - 1).
+ *   Destination (fold, eq): a blz_vec_arg too.  d_ptr == NULL names transform buffer `buf`; otherwise it names `count` device
+ *   words, count a power of two with out_len <= count <= n.  The op writes EXACTLY out_len words from the start of the destination;
+ *   every other byte of it keeps its value - no zero fill: a sumcheck's tables shrink geometrically, and so does its traffic.
+ *   In place (fold): the destination must start at the same word as the source or not overlap the words the op reads (the first
+ *   min(count, len) of a).  In place with the default pairing costs nothing extra; with BLZ_MLE_LOW it goes through the handle's
+ *   scratch and a device-to-device copy of len / 2 words on the compute stream.  A periodic source (count < len) cannot be folded in
+ *   place.
+ *   r: one device word, BLZ_FOLD_EVAL's rule (d_ptr != NULL, count == 1); the host never reads it, so a challenge derived on the
+ *   device chains rounds without a round trip.  It may not lie in the words written.
+ *   d_out (round): points x 32 bytes of device memory, checked as blz_ntt_vec_reduce's d_out is and off the words of every d_ptr
+ *   operand; exactly `points` words are written.  The round writes no transform buffer.
+ *   d_point (eq): m x 32 bytes of device memory on the handle's device, 16-byte aligned, inside one allocation, off the words
+ *   written; not looked at when m == 0.  The host never reads it.
+ *   Cost ("Multilinear tables"; derived from the code): the fold takes one Montgomery product per output
+ *   word, the round points x (k - 1) per pair (none at k = 1), the equality table about two per word.
+ *   Protocol: that of blz_ntt_vec_op.  Everything is checked before anything is enqueued; the op runs on the compute stream and the
+ *   call returns without waiting for the device; blz_ntt_wait_result finishes it, blz_ntt_last_kernel_ms then reports it,
+ *   blz_ntt_reset drops it.  One op is in flight at a time.  While it is, a destination BUFFER may not be read, written or
+ *   exchanged, a buffer that is only read may be read, and every transform, blz_ntt_set_coset and op on the buffers is refused.
+ *   Memory behind every pointer stays valid (inputs: unwritten) until blz_ntt_wait_result returns.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing: null handle, unknown flag bits, a null a, r, dst, d_out or (m > 0) d_point, an op in
+ *   flight, any operand error of blz_ntt_vec_op (dst included); fold: len not a power of two in [2, n], r naming a buffer or with
+ *   count != 1, a destination count below out_len, a destination overlapping the source without starting where it starts, in
+ *   place with a periodic source, r inside the words written; round: points outside 1 .. 4, b NULL while c is set, a bad d_out or
+ *   one that overlaps a d_ptr operand, len as for the fold; eq: m above log_size, a bad d_point or one inside the words written. */
+#define BLZ_MLE_LOW 1u
+int blz_ntt_vec_mle_fold(blz_ntt* h, uint32_t flags, const blz_vec_arg* dst, const blz_vec_arg* a, const blz_vec_arg* r, uint64_t len);
+int blz_ntt_vec_mle_round(blz_ntt* h, uint32_t flags, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c, uint32_t points,
+                          uint64_t len, void* d_out);
+int blz_ntt_vec_mle_eq(blz_ntt* h, const blz_vec_arg* dst, const void* d_point, uint32_t m);
 /* NTTBanks::preprocess / postprocess (ntt_data.rs:80-156) as device permutations, for byte
  * compatibility with bank files of the FPGA flow; n = 2^log_size elements (log_size >= 10), 16 banks
  * contiguous (n/16 elements each); 2^27 uses the reference's 512 groups x 256 block pairs, smaller sizes

@@ -47,6 +47,8 @@ pub struct BlzVecCsr {
     pub rows: u64,
     pub nnz: u64,
 }
+/// `BLZ_MLE_LOW`: `blz_ntt_vec_mle_fold` / `_round` pair (a\[2p\], a\[2p + 1\]) - variable 0 - instead of (a\[p\], a\[p + len / 2\]).
+pub const BLZ_MLE_LOW: u32 = 1;
 
 pub const BLZ_COMM_ID_BYTES: usize = 128;
 
@@ -136,6 +138,10 @@ extern "C" {
     pub fn blz_ntt_vec_horner(h: *mut BlzNtt, flags: u32, buf_dst: usize, a: *const BlzVecArg, z: *const BlzVecArg, d_total: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_gather(h: *mut BlzNtt, buf_dst: usize, a: *const BlzVecArg, v: *const BlzVecView) -> c_int;
     pub fn blz_ntt_vec_spmv(h: *mut BlzNtt, buf_dst: usize, x: *const BlzVecArg, m: *const BlzVecCsr) -> c_int;
+    pub fn blz_ntt_vec_mle_fold(h: *mut BlzNtt, flags: u32, dst: *const BlzVecArg, a: *const BlzVecArg, r: *const BlzVecArg, len: u64) -> c_int;
+    pub fn blz_ntt_vec_mle_round(h: *mut BlzNtt, flags: u32, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg, points: u32,
+                                 len: u64, d_out: *mut c_void) -> c_int;
+    pub fn blz_ntt_vec_mle_eq(h: *mut BlzNtt, dst: *const BlzVecArg, d_point: *const c_void, m: u32) -> c_int;
 
     // ---- Poseidon tree: PoseidonClient (ingo_hash::poseidon_api)
     pub fn blz_poseidon_new(device_id: c_int, field: c_int, out: *mut *mut BlzPoseidon) -> c_int;

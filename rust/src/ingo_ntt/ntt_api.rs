@@ -243,6 +243,43 @@ impl NTTClient {
         self.vec_spmv(dst, x, std::ptr::null(), d_col, d_val, count, count)
     }
 
+    /// Bind one variable of a multilinear table (blz_ntt_vec_mle_fold): dst\[p\] = lo + r (hi - lo) for p < `len` / 2, with
+    /// (lo, hi) = (a\[p\], a\[p + len / 2\]) - the top variable - or, with `low`, (a\[2p\], a\[2p + 1\]) - variable 0.  `dst` is a
+    /// transform buffer or device words (count a power of two, len / 2 <= count <= n) and may be `a` itself; exactly len / 2
+    /// words are written and every other byte of the destination keeps its value.  `r` is one device word
+    /// (`VecOperand::Words { count: 1, .. }`) the host never reads.
+    ///
+    /// # Safety
+    /// As for `vec_op`; device words named by `dst` are WRITTEN until `wait_result` returns.
+    pub unsafe fn vec_mle_fold(&self, dst: VecOperand, a: VecOperand, r: VecOperand, len: u64, low: bool) -> Result<()> {
+        let (rd, ra, rr) = (dst.raw(), a.raw(), r.raw());
+        check(blz_ntt_vec_mle_fold(self.h, if low { BLZ_MLE_LOW } else { 0 }, &rd, &ra, &rr, len))
+    }
+
+    /// One round polynomial of a sumcheck (blz_ntt_vec_mle_round): `d_out`\[t\] = the sum over p < `len` / 2 of the product over
+    /// the k tables given (a, then b, then c) of lo + t (hi - lo), for t = 0 .. `points` - 1 (1 ..= 4; k + 1 values determine the
+    /// polynomial), pairing as in `vec_mle_fold`.  `d_out` is `points` x 32 bytes of device memory; nothing else is written.
+    ///
+    /// # Safety
+    /// As for `vec_reduce`.
+    pub unsafe fn vec_mle_round(&self, a: VecOperand, b: Option<VecOperand>, c: Option<VecOperand>, points: u32, len: u64, low: bool,
+                                d_out: *mut std::os::raw::c_void) -> Result<()> {
+        let (ra, rb, rc) = (a.raw(), b.map(|v| v.raw()), c.map(|v| v.raw()));
+        let p = |v: &Option<BlzVecArg>| v.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg);
+        check(blz_ntt_vec_mle_round(self.h, if low { BLZ_MLE_LOW } else { 0 }, &ra, p(&rb), p(&rc), points, len, d_out))
+    }
+
+    /// The equality table (blz_ntt_vec_mle_eq): dst\[p\] = prod over i < `m` of (x_i tau_i + (1 - x_i)(1 - tau_i)) for p < 2^m,
+    /// x_i bit i of p, tau_i word i of `d_point` (m x 32 bytes of device memory the host never reads; null with m = 0, which
+    /// writes the single word 1).  `dst` as for `vec_mle_fold`; exactly 2^m words are written.
+    ///
+    /// # Safety
+    /// As for `vec_mle_fold`; `d_point` stays valid and unwritten until `wait_result` returns.
+    pub unsafe fn vec_mle_eq(&self, dst: VecOperand, d_point: *const std::os::raw::c_void, m: u32) -> Result<()> {
+        let rd = dst.raw();
+        check(blz_ntt_vec_mle_eq(self.h, &rd, d_point, m))
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
