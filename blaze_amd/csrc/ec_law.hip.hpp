@@ -6,6 +6,8 @@
 // Every law has: Pt; LANES, the lanes that share a point; a constructor from the lane's index inside that group; inf, load,
 // add, dbl, store; owner(), the lanes that store (every lane of the row law stores: its own limb).  All lanes of a group run
 // every call with the same arguments.  The cooperative laws also have to_lane: the point as ONE lane holds it, for emit_result.
+// settle: called behind the last of a run of doublings, before the point is used - a law may put a test off until then (the row
+// law's for a point of order two, ec_row.hip.hpp rowpt_dbl); a lone dbl is followed by it too.
 // TAG (lane laws): a kernel's own out-of-line copy of the doubling, so that its register budget stays its own (see the NOTE
 // above k_accumulate).
 #pragma once
@@ -57,6 +59,7 @@ struct LaneLaw32 : PointIo32<F> {
     BLZ_DEV explicit LaneLaw32(uint32_t) {}
     BLZ_DEV void add(Pt& a, const Pt& b) const { pt_add_inl<F, TAG>(a, b); }
     BLZ_DEV void dbl(Pt& a) const { a = pt_dbl_val<F, TAG>(a); }
+    BLZ_DEV void settle(Pt&) const {}
     BLZ_DEV bool owner() const { return true; }
 };
 template <class Q, int TAG>
@@ -66,6 +69,7 @@ struct LaneLawRR : PointIoRR<Q> {
     BLZ_DEV explicit LaneLawRR(uint32_t) {}
     BLZ_DEV void add(Pt& a, const Pt& b) const { ptrr_add<Q, TAG>(a, b); }
     BLZ_DEV void dbl(Pt& a) const { a = ptrr_dbl_val<Q, TAG>(a); }
+    BLZ_DEV void settle(Pt&) const {}
     BLZ_DEV bool owner() const { return true; }
 };
 // the field's lane law: the reduced radix where it has one (and the tag of the kernel's copy on either)
@@ -82,6 +86,7 @@ struct QuadLaw32 : PointIo32<F> {
     BLZ_DEV explicit QuadLaw32(uint32_t lane) : ql(lane) {}
     BLZ_DEV void add(Pt& a, const Pt& b) const { quad_add(a, b, ql & 3u); }
     BLZ_DEV void dbl(Pt& a) const { quad_dbl(a, ql & 3u); }
+    BLZ_DEV void settle(Pt&) const {}
     BLZ_DEV bool owner() const { return ql == 0; }
     BLZ_DEV Pt to_lane(const Pt& p) const { return p; }
 };
@@ -93,6 +98,7 @@ struct QuadLawRR : PointIoRR<Q> {
     BLZ_DEV explicit QuadLawRR(uint32_t lane) : ql(lane) {}
     BLZ_DEV void add(Pt& a, const Pt& b) const { quadrr_add(a, b, ql & 3u); }
     BLZ_DEV void dbl(Pt& a) const { quadrr_dbl(a, ql & 3u); }
+    BLZ_DEV void settle(Pt&) const {}
     BLZ_DEV bool owner() const { return ql == 0; }
     BLZ_DEV Pt to_lane(const Pt& p) const { return p; }
 };
@@ -110,7 +116,10 @@ struct RowLaw {
     BLZ_DEV void inf(Pt& p) const { rowpt_set_inf(p); }
     BLZ_DEV void load(Pt& p, const uint32_t* base, size_t idx) const { rowpt_load<Q>(c, p, base, idx); }
     BLZ_DEV void add(Pt& a, const Pt& b) const { rowpt_add<Q>(c, a, b); }
-    BLZ_DEV void dbl(Pt& a) const { rowpt_dbl<Q>(c, a); }
+    BLZ_DEV void dbl(Pt& a) const { rowpt_dbl<Q, false>(c, a); }   // (a link of a run that settle() ends: ec_row.hip.hpp)
+    BLZ_DEV void settle(Pt& a) const {
+        if constexpr (RR_EVEN_ORDER<Q>) rowpt_settle<Q>(c, a);
+    }
     BLZ_DEV void store(uint32_t* base, size_t idx, const Pt& p) const { rowpt_store<Q>(c, base, idx, p); }
     BLZ_DEV void store_strict(uint32_t* base, size_t idx, const Pt& p) const { rowpt_store_strict<Q>(c, base, idx, p); }
     BLZ_DEV bool owner() const { return true; }

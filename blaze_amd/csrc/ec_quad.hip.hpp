@@ -159,6 +159,7 @@ BLZ_DEV Frr<Q, 1, 2> rrq_diff(const Frr<Q, 1, 2>& t, const Frr<Q, 1, 2>& u) { re
 template <class Q>
 BLZ_DEV void quadrr_dbl(XYZZRR<Q>& p, uint32_t l) {
     if (ptrr_is_inf(p)) return;
+    if (rr_y_of_order_two(p.y)) { ptrr_set_inf(p); return; }   // (ec_rr.hip.hpp RR_EVEN_ORDER; the same on the 4 lanes)
     Frr<Q, 1, 2> r, V, A, W, S, ZZ3, MM, t, WY, ZZZ3;
     const auto U = rr_tn(rr_add(p.y, p.y));
     // round 1: V = U^2 | A = X^2

@@ -70,6 +70,28 @@ BLZ_DEV void ptrr_set_inf(XYZZRR<Q>& p) {
 template <class Q>
 BLZ_DEV bool ptrr_is_inf(const XYZZRR<Q>& p) { return rr_all_zero(p.zz); }
 
+// A curve group of EVEN order has a point with Y = 0, and the doublings below have no branch for it: they answer ZZ3 = 0 (mod m).
+// Infinity is recognised by LITERAL zero limbs, and a product without a conditional subtraction turns a non-zero multiple of m into
+// m, never into 0: only a T that comes straight from memory (Y literally 0) doubles to an infinity the next addition knows.  A
+// computed T - a bucket holding A and T - A - has Y = m, and T + T (the bucket reduce's s += run) gave ZZ = m: every later sum was
+// garbage.  So the doublings of such a curve test Y = 0 (mod m) and answer the literal infinity.  BLS12-377's y^2 = x^3 + 1 has
+// T = (-1, 0); BLS12-381's and BN254's groups have odd order, and their doublings compile to what they were.
+template <class Q>
+struct RrEvenOrder { static constexpr bool value = false; };
+template <>
+struct RrEvenOrder<Fq_BLS377_RR> { static constexpr bool value = true; };
+template <class Q>
+constexpr bool RR_EVEN_ORDER = RrEvenOrder<Q>::value;
+// y = 0 (mod m)?  The low-limb filter first (rr_maybe_equal): y = k m with 0 <= k < V, and k = y_0 m^-1 mod 2^B
+template <class Q, int F, int V>
+BLZ_DEV bool rr_y_of_order_two(const Frr<Q, F, V>& y) {
+    if constexpr (RR_EVEN_ORDER<Q>) {
+        const uint32_t k = (y.v[0] * Q::MINV) & Q::MASK;
+        if (__builtin_expect(k < (uint32_t)V, 0)) return rr_is_zero(y);
+    }
+    return false;
+}
+
 // Bounds in the comments: (limb factor, value factor), loose budget first, tight budget after the bar.
 
 // 2 (x, y) for an affine point whose y may be the lazy negation 4m - y.  By value and out of line: the rare
@@ -215,7 +237,7 @@ BLZ_DEV void ptrr_jdbl(JacRR<Q>& p) {
 template <class Q, int TAG = 0>
 __device__ __noinline__ XYZZRR<Q> ptrr_dbl_val(XYZZRR<Q> p) {
     XYZZRR<Q> r;
-    if (ptrr_is_inf(p)) { ptrr_set_inf(r); return r; }
+    if (ptrr_is_inf(p) || rr_y_of_order_two(p.y)) { ptrr_set_inf(r); return r; }
     const auto U = rr_tn(rr_add(p.y, p.y));            // (2, 8) | (1, 4)
     Frr<Q, 1, 2> V, W, S, t, Msq, y3;
     rr_sqr(V, U);

@@ -821,6 +821,7 @@ BLZ_DEV void reduce_segment(const uint32_t* inA, const uint32_t* inC, const uint
     }
     if constexpr (!LEVEL0) {
         for (int d = 0; d < shift; ++d) law.dbl(s);
+        law.settle(s);
         law.add(cs, s);
     }
     if (!law.owner()) return;
@@ -970,6 +971,7 @@ BLZ_DEV void horner_walk(const uint32_t* vsumA, const uint32_t* vsumC, const Fin
             }
             const int o2 = off + fp.logV;
             if (started) for (int d = 0; d < pos - o2; ++d) law.dbl(acc);
+            law.settle(acc);
             law.add(acc, u);
             pos = o2;
             started = true;
@@ -982,12 +984,14 @@ BLZ_DEV void horner_walk(const uint32_t* vsumA, const uint32_t* vsumC, const Fin
             law.add(cs, a);
         }
         if (started) for (int d = 0; d < pos - off; ++d) law.dbl(acc);
+        law.settle(acc);
         law.add(acc, cs);
         pos = off;
         started = true;
     }
     // scalar-range tasks: the lowest window starts at bit_lo of the scalar, the partial result carries that weight
     for (int d = 0; d < pos; ++d) law.dbl(acc);
+    law.settle(acc);
     const auto r = law.to_lane(acc);   // (every lane takes part: the row law's limbs meet in LDS)
     if (threadIdx.x == 0) {
         XYZZ<F> o;

@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "ec_rr.hip.hpp"
 #include "ec_row.hip.hpp"
+#include "ec_law.hip.hpp"
 #include "poseidon_engine.hpp"
 #include "msm_engine.hpp"
 
@@ -519,6 +520,213 @@ int test_pos_tree_check_t(const uint8_t* words, size_t len, int tree_mode, uint3
     return BLZ_OK;
 }
 
+// ---- the group laws of the MSM tail (ec_law.hip.hpp), one program per case on raw point images (include/blaze_hip_aux.h
+// blz_test_law_op).  The programs reach a law through its policy interface only, so one body serves every law; the additions and
+// doublings go through one out-of-line copy each (a lane law's addition is 14 field products: inlined at every step of every
+// program the kernel would be a dozen times the size of the product's largest).
+template <class L>
+struct LaneRROf { static constexpr bool value = false; };
+template <class Q, int TAG>
+struct LaneRROf<LaneLawRR<Q, TAG>> {
+    static constexpr bool value = true;
+    using RR = Q;
+    static constexpr int tag = TAG;
+};
+template <class Law>
+__device__ __noinline__ void law_add(const Law& law, typename Law::Pt& a, const typename Law::Pt& b) { law.add(a, b); }
+template <class Law>
+__device__ __noinline__ void law_dbl(const Law& law, typename Law::Pt& a) { law.dbl(a); }
+template <class F>
+BLZ_DEV void lane_store(uint32_t* base, size_t idx, const XYZZ<F>& p) { store_xyzz(base, idx, p); }
+template <class Q>
+BLZ_DEV void lane_store(uint32_t* base, size_t idx, const XYZZRR<Q>& p) { ptrr_store(base, idx, p); }
+
+enum { LAW_IDENT = 0, LAW_ADD, LAW_DBL, LAW_RUNSUM, LAW_HORNER, LAW_REUSE, LAW_TREE, LAW_PROGRAMS };
+constexpr int LAW_TEST_TAG = 9;   // the lane laws' out-of-line doubling: a copy of this kernel's own (ec_law.hip.hpp TAG)
+
+// A group of Law::LANES lanes per case (TREE: the wave), one wave per block (RowLaw::to_lane holds a block barrier).  Every lane
+// of a group runs every step: a surplus group repeats case n - 1 and stores nothing.  The host has checked that the program reads
+// points 0 .. k - 1 of its case only and that arg bounds every loop.
+template <class Law>
+__global__ __launch_bounds__(64) void k_test_law(int program, int exit, uint32_t k, uint32_t arg, const uint32_t* in, uint32_t* out, uint32_t n) {
+    using Pt = typename Law::Pt;
+    const uint32_t lane = threadIdx.x & 63u, sub = lane % Law::LANES;
+    const bool tree = program == LAW_TREE;
+    const uint32_t e = tree ? blockIdx.x : blockIdx.x * (64u / Law::LANES) + lane / Law::LANES;
+    const size_t p0 = (size_t)(e < n ? e : n - 1u) * k;
+    const Law law(sub);
+    Pt acc, t;
+    law.inf(acc);
+    switch (program) {
+        case LAW_IDENT:
+            law.load(acc, in, p0);
+            break;
+        case LAW_ADD:
+            law.load(acc, in, p0);
+            law.load(t, in, p0 + 1);
+            law_add(law, acc, t);
+            break;
+        case LAW_DBL:
+            law.load(acc, in, p0);
+            law_dbl(law, acc);
+            law.settle(acc);
+            break;
+        case LAW_RUNSUM: {   // reduce_segment's inner loop (acc is its s)
+            Pt run;
+            law.inf(run);
+            for (uint32_t j = 0; j < 4; ++j) {
+                law.load(t, in, p0 + j);
+                law_add(law, run, t);
+                law_add(law, acc, run);
+            }
+        } break;
+        case LAW_HORNER:     // horner_walk's shape
+            law.load(acc, in, p0);
+            for (uint32_t j = 1; j < 3; ++j) {
+                for (uint32_t d = 0; d < arg; ++d) law_dbl(law, acc);
+                law.settle(acc);
+                law.load(t, in, p0 + j);
+                law_add(law, acc, t);
+            }
+            break;
+        case LAW_REUSE:      // a computed sum added to its own copy, then to two more points
+            law.load(acc, in, p0);
+            law.load(t, in, p0 + 1);
+            law_add(law, acc, t);
+            t = acc;
+            law_add(law, acc, t);
+            for (uint32_t j = 2; j < 4; ++j) {
+                law.load(t, in, p0 + j);
+                law_add(law, acc, t);
+            }
+            break;
+        case LAW_TREE:       // k_combine_buckets_wave's tree: lane i holds point i, infinity from lane arg on
+            if constexpr (LaneRROf<Law>::value) {
+                if (lane < arg) law.load(acc, in, p0 + lane);
+                for (uint32_t r = 1; r < arg; r <<= 1) ptrr_shuffle_round<typename LaneRROf<Law>::RR, LaneRROf<Law>::tag>(acc, lane, r, arg);
+            }
+            break;
+    }
+    const bool mine = e < n && (!tree || lane == 0u);
+    if (exit == 0) {
+        if (mine && law.owner()) law.store(out, e, acc);
+    }
+    if constexpr (Law::LANES > 1) {
+        if (exit == 1) {
+            const auto r = law.to_lane(acc);
+            if (mine && sub == 0u) lane_store(out, e, r);
+        }
+    }
+    if constexpr (Law::LANES == 64) {
+        if (exit == 2 && mine) law.store_strict(out, e, acc);
+    }
+}
+
+// what a law's point type declares about its memory image: include/blaze_hip_aux.h blz_test_law_layout
+struct LawBound { uint32_t vx, vy, vzz, vzzz, limb_max; };
+struct LawLayout {
+    uint32_t B = 0, NL = 0, stride = 0, e = 0, lanes = 0, closed = 0;
+    LawBound in{}, store{}, strict{}, to_lane{};
+    bool tree = false;
+};
+template <class F, uint32_t LANES>
+LawLayout layout_32() {
+    LawLayout L;
+    L.B = 32; L.NL = F::N; L.stride = F::N; L.e = 32 * F::N; L.lanes = LANES;
+    // field.hip.hpp: the lazy fields keep values in [0, 2m], a closed range; the others in [0, m)
+    L.closed = F::LAZY ? 1 : 0;
+    const uint32_t v = F::LAZY ? 2 : 1;
+    L.in = L.store = LawBound{v, v, v, v, 0xffffffffu};
+    if (LANES > 1) L.to_lane = L.store;
+    return L;
+}
+template <class Q, uint32_t LANES>
+LawLayout layout_rr() {
+    LawLayout L;
+    L.B = Q::B; L.NL = Q::NL; L.stride = rr_stride<Q>(); L.e = Q::B * Q::NL; L.lanes = LANES;
+    // XYZZRR<Q>: x Frr<Q, 1, VX>, y Frr<Q, 1, VY>, zz and zzz Frr<Q, 1, 2>; F = 1 is limbs < 2^B
+    L.in = L.store = LawBound{(uint32_t)XYZZRR<Q>::VX, (uint32_t)XYZZRR<Q>::VY, 2, 2, Q::MASK};
+    if (LANES > 1) L.to_lane = L.store;
+    L.tree = LANES == 1;
+    return L;
+}
+// RowLaw has no bound types; from the comments of ec_row.hip.hpp:
+//   in      rowpt_load takes the limbs as they are.  The law reads level 0's bucket sums (XYZZRR: x < VX m, y < VY m) and its own
+//           sums: "X3 ... (1, 14)" rowpt_add, "(1, 10)" rowpt_dbl; "Y3 = t - W Y + 4m stays the lazy < 6m it is"; products "< 2m with
+//           WEAKLY normalised limbs (<= 2^28 ...)".  The wider of the two per coordinate.
+//   store   "limbs as they are (weakly normalised)": the same bounds, a loaded point may leave as it came.
+//   strict  rowpt_store_strict / rowpt_export: "exact limbs, Y below 2m by a product with R mod m: XYZZRR's bounds".
+template <class Q>
+LawLayout layout_row() {
+    LawLayout L = layout_rr<Q, 64>();
+    const uint32_t vx = XYZZRR<Q>::VX > 14 ? XYZZRR<Q>::VX : 14, vy = XYZZRR<Q>::VY > 6 ? XYZZRR<Q>::VY : 6;
+    L.in = L.store = LawBound{vx, vy, 2, 2, 1u << Q::B};
+    L.strict = L.to_lane = LawBound{(uint32_t)XYZZRR<Q>::VX, 2, 2, 2, Q::MASK};
+    return L;
+}
+
+struct LawOp {
+    int program, exit;
+    uint32_t k, arg;
+    const uint32_t* in;
+    uint32_t* out;
+    size_t n;
+};
+template <class Law>
+int test_law_run(const LawLayout& L, const LawOp& op) {
+    const bool tree = op.program == LAW_TREE;
+    const size_t pd = 4 * (size_t)L.stride * 4, in_bytes = op.n * op.k * pd, out_bytes = op.n * pd;
+    Tmp tmp;
+    void *din, *dout;
+    BLZ_TRY(tmp.alloc(&din, in_bytes)); BLZ_TRY(tmp.alloc(&dout, out_bytes));
+    BLZ_HIP(hipMemcpy(din, op.in, in_bytes, hipMemcpyHostToDevice), BLZ_ERR_WRITE);
+    BLZ_HIP(hipMemset(dout, 0, out_bytes), BLZ_ERR_UNKNOWN);
+    const size_t per_block = tree ? 1 : 64 / Law::LANES;
+    hipLaunchKernelGGL(k_test_law<Law>, dim3((unsigned)((op.n + per_block - 1) / per_block)), dim3(64), 0, 0, op.program, op.exit, op.k, op.arg,
+                       (const uint32_t*)din, (uint32_t*)dout, (uint32_t)op.n);
+    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
+    BLZ_TRY(sync_stream_bounded(nullptr, "group law test kernel"));
+    BLZ_HIP(hipMemcpy(op.out, dout, out_bytes, hipMemcpyDeviceToHost), BLZ_ERR_READ);
+    return BLZ_OK;
+}
+// op == nullptr: the layout only
+template <class Law>
+int test_law_do(const LawLayout& L, LawLayout* layout, const LawOp* op) {
+    if (layout) *layout = L;
+    return op ? test_law_run<Law>(L, *op) : BLZ_OK;
+}
+// the laws the product instantiates for a field (msm_impl.hip.hpp HAS_RR / HAS_ROW; tests/msm_tail_ref.py LAWS)
+template <class F>
+int test_law_field(int law, LawLayout* layout, const LawOp* op) {
+    if constexpr (USE_RR<F>) {
+        using Q = typename F::RR;
+        if (law == 0) return test_law_do<LaneLawRR<Q, LAW_TEST_TAG>>(layout_rr<Q, 1>(), layout, op);
+        if (law == 1) return test_law_do<QuadLawRR<Q>>(layout_rr<Q, 4>(), layout, op);
+        if constexpr (!RR_TIGHT<Q>) {
+            if (law == 2) return test_law_do<RowLaw<Q>>(layout_row<Q>(), layout, op);
+        }
+    } else {
+        if (law == 0) return test_law_do<LaneLaw32<F, LAW_TEST_TAG>>(layout_32<F, 1>(), layout, op);
+        if (law == 1) return test_law_do<QuadLaw32<F>>(layout_32<F, 4>(), layout, op);
+    }
+    return fail(BLZ_ERR_INVALID_PARAM, "the field has no law %d", law);
+}
+struct Fq_BN254_W32 : Fq_BN254 {   // BN254 on 32-bit limbs (msm_bn254w.hip): repr 1
+    using RR = void;
+};
+static int test_law_dispatch(int curve, int repr, int law, LawLayout* layout, const LawOp* op) {
+    if (repr == 0) {
+        switch (curve) {
+            case BLZ_BLS377: return test_law_field<Fq_BLS377>(law, layout, op);
+            case BLZ_BLS381: return test_law_field<Fq_BLS381>(law, layout, op);
+            case BLZ_BN254: return test_law_field<Fq_BN254>(law, layout, op);
+        }
+    } else if (repr == 1 && curve == BLZ_BN254) {
+        return test_law_field<Fq_BN254_W32>(law, layout, op);
+    }
+    return fail(BLZ_ERR_INVALID_PARAM, "no group laws for curve %d with arithmetic %d", curve, repr);
+}
+
 }  // namespace blz
 
 using namespace blz;
@@ -635,6 +843,42 @@ int blz_test_msm_tail_plan(int curve, int repr, uint32_t npts, int sbits, int pi
     if (line.size() >= cap) return fail(BLZ_ERR_INVALID_PARAM, "text buffer of %zu bytes for a line of %zu", cap, line.size());
     memcpy(text, line.c_str(), line.size() + 1);
     return BLZ_OK;
+}
+
+int blz_test_law_layout(int curve, int repr, int law, uint32_t out[32]) {
+    if (!out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    LawLayout L;
+    BLZ_TRY(test_law_dispatch(curve, repr, law, &L, nullptr));
+    memset(out, 0, 32 * sizeof(uint32_t));
+    const uint32_t head[6] = {L.B, L.NL, L.stride, L.e, L.lanes, L.closed};
+    memcpy(out, head, sizeof(head));
+    const LawBound* b[4] = {&L.in, &L.store, &L.strict, &L.to_lane};
+    for (int i = 0; i < 4; ++i) memcpy(out + 6 + 5 * i, b[i], sizeof(LawBound));
+    out[26] = L.tree ? 1u : 0u;
+    return BLZ_OK;
+}
+
+int blz_test_law_op(int device_id, int curve, int repr, int law, int program, int exit, uint32_t k, uint32_t arg, const uint32_t* in, uint32_t* out,
+                    size_t n) {
+    if (!in || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    LawLayout L;
+    BLZ_TRY(test_law_dispatch(curve, repr, law, &L, nullptr));
+    // every index and loop bound of the kernel is decided here
+    if (program < 0 || program >= LAW_PROGRAMS) return fail(BLZ_ERR_INVALID_PARAM, "unknown program %d", program);
+    if (program == LAW_TREE) {
+        if (!L.tree) return fail(BLZ_ERR_INVALID_PARAM, "the shuffle tree runs on the reduced-radix lane law only");
+        if (k < 1 || k > 64 || arg < 1 || arg > k) return fail(BLZ_ERR_INVALID_PARAM, "tree of %u lanes over %u points", arg, k);
+    } else {
+        if (k != 4) return fail(BLZ_ERR_INVALID_PARAM, "program %d takes 4 points per case, not %u", program, k);
+        if (arg > 64) return fail(BLZ_ERR_INVALID_PARAM, "%u doublings per step (at most 64)", arg);
+    }
+    const LawBound& ex = exit == 0 ? L.store : exit == 1 ? L.to_lane : L.strict;
+    if (exit < 0 || exit > 2 || ex.limb_max == 0) return fail(BLZ_ERR_INVALID_PARAM, "law %d has no exit %d", law, exit);
+    if (n == 0) return BLZ_OK;
+    if (n > (1u << 20)) return fail(BLZ_ERR_INVALID_PARAM, "%zu cases (at most 2^20)", n);
+    BLZ_TRY(use_device(device_id));
+    const LawOp op = {program, exit, k, arg, in, out, n};
+    return test_law_dispatch(curve, repr, law, nullptr, &op);
 }
 
 int blz_test_sort_fits_beside(int acc_vgprs, int sort_vgprs, int acc_lds, int sort_lds) {

@@ -62,6 +62,26 @@ int blz_test_ec_op(int device_id, int curve, int op, const uint8_t* p, const uin
 int blz_test_msm_tail_plan(int curve, int repr, uint32_t npts, int sbits, int pieces, int table_c, int bit_lo, int bit_hi, uint32_t plan_out[8],
                            uint8_t* widths, char* text, size_t cap);
 
+/* The group laws of the MSM tail (ec_law.hip.hpp), element by element on RAW point images: what a law loads and stores, limb for limb.
+ * law: 0 lane, 1 quad (a DPP quad per point), 2 row (a wave per point); repr as above.  A (curve, repr, law) the product does not
+ * instantiate is BLZ_ERR_INVALID_PARAM (the set: tests/msm_tail_ref.py LAWS).
+ * blz_test_law_layout (host only): what the point type and the law declare about an image -
+ *   out[0] limb bits B, [1] limbs NL, [2] dwords per coordinate (an image is x | y | zz | zzz, 4 out[2] dwords), [3] the Montgomery
+ *   exponent e (R = 2^e), [4] LANES, [5] 1 when the value bounds are closed (value <= V m: the 32-bit lazy range [0, 2m]), 0 when open
+ *   (value < V m), then four bounds of five words each - the value factors V of x, y, zz, zzz and the largest limb admitted - at
+ *   [6] what the law reads, [11] what store writes, [16] store_strict, [21] to_lane (all zero: the law has no such exit);
+ *   [26] 1 when the law has the shuffle tree (program 6).  Limbs are B bits apart whatever their size: a coordinate is
+ *   sum limb_i 2^(B i); infinity is zz with every limb zero.
+ * blz_test_law_op: n cases of k images each (host pointers, the law's own layout), one result image per case.  Programs (k = 4
+ *   except TREE): 0 IDENT P0; 1 ADD P0 + P1; 2 DBL 2 P0; 3 RUNSUM run = s = inf, for j: run += Pj, s += run (the bucket reduce's
+ *   inner loop: 4 P0 + 3 P1 + 2 P2 + P3); 4 HORNER acc = P0, arg doublings, += P1, arg doublings, += P2 (arg <= 64);
+ *   5 REUSE a = P0 + P1, a += copy of a, a += P2, a += P3; 6 TREE (reduced-radix lane law only, 1 <= arg <= k <= 64): lane i < arg of a
+ *   wave holds Pi, the others infinity, then the pairwise shuffle rounds 1, 2, 4 .. < arg; lane 0's sum.
+ *   exit: 0 the law's store; 1 to_lane, written by the owner lane in the lane law's layout (cooperative laws); 2 store_strict (row). */
+int blz_test_law_layout(int curve, int repr, int law, uint32_t out[32]);
+int blz_test_law_op(int device_id, int curve, int repr, int law, int program, int exit, uint32_t k, uint32_t arg, const uint32_t* in,
+                    uint32_t* out, size_t n);
+
 /* MsmEngine::begin()'s test for hiding a task's digit sort under another task's accumulation: 1 when a block of the sort (sort_vgprs
  * registers per lane, sort_lds bytes of LDS) fits on a CU beside the accumulation's blocks of 128 lanes (acc_vgprs, acc_lds), else 0.
  * Host only.  A count <= 0 is "not known" and is taken to fit. */

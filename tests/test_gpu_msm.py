@@ -775,6 +775,31 @@ def test_randomised_small_cases(gpu, orc):
         c.close()
 
 
+@pytest.mark.parametrize("with_b", [True, False])
+def test_bucket_sum_of_order_two(gpu, with_b):
+    """BLS12-377's curve has T = (q - 1, 0) of order two.  A bucket holding A and T - A sums to T in a COMPUTED form - y a non-zero
+    multiple of q - and the bucket reduce's running sums then add that T to itself: 2 A + 2 (T - A) + B = B, and without B infinity."""
+    import random
+
+    curve = "BLS377"
+    c = pyref.CURVES[curve]
+    rng = random.Random(2)
+    G = pyref.generator(curve)
+    A, B = (pyref.mul(curve, G, rng.randrange(1, c["r"])) for _ in range(2))
+    T = (c["q"] - 1, 0)
+    pts = [A, pyref.add(curve, T, pyref.neg(curve, A))] + ([B] if with_b else [])
+    sc = [2, 2] + ([1] if with_b else [])
+    n = len(pts)
+    points = b"".join(pyref.enc_point(curve, P) for P in pts)
+    scalars = b"".join(pyref.enc_scalar(s) for s in sc)
+    want = pyref.msm_naive(curve, points, scalars, n)
+    assert want == (B if with_b else None)
+    cl = msm_client(curve, 1)
+    got = run_msm(cl, points, scalars, n)
+    cl.close()
+    assert got == pyref.enc_result(curve, want)
+
+
 @pytest.mark.parametrize("curve", CURVES)
 @pytest.mark.parametrize("pf", [1, 8])
 def test_mixed_window_widths_small(gpu, orc, curve, pf, monkeypatch):
