@@ -132,6 +132,8 @@ _SIGS = {
     "blz_ntt_vec_mle_eq": (C.c_int, [C.c_void_p, C.POINTER(BlzVecArg), C.c_void_p, C.c_uint32]),
     "blz_ntt_banks_preprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
     "blz_ntt_banks_postprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
+    "blz_ntt_sumcheck_step": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg),
+                                        C.POINTER(BlzVecArg), C.c_uint32, C.c_uint64, C.c_void_p]),
     "blz_poseidon_new": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "blz_poseidon_free": (None, [C.c_void_p]),
     "blz_poseidon_loaded_binary_parameters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),

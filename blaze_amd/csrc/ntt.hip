@@ -93,6 +93,7 @@ struct blz_ntt {
     bool in_flight = false;
     int in_flight_buf = -1;   // buffer under transform (or written by an element-wise op) while in_flight
     uint32_t in_flight_reads = 0;   // blz_ntt_vec_op in flight: bit b = transform buffer b is an operand it reads
+    int in_flight_buf2 = -1;  // blz_ntt_sumcheck_step in flight: the second buffer it writes (both buffers may be tables), else -1
     float last_ms = 0.f;
     bool wedged = false;      // a wait ran into BLAZE_WAIT_TIMEOUT_MS: only reset / free are accepted (common.hpp)
 };
@@ -116,6 +117,8 @@ struct blz_ntt {
 namespace {
 
 size_t ntt_bytes(const blz_ntt* h) { return (size_t)32 << h->logn; }
+// what is in flight writes transform buffer `buf`
+bool ntt_buf_in_flight(const blz_ntt* h, size_t buf) { return h->in_flight && (h->in_flight_buf == (int)buf || h->in_flight_buf2 == (int)buf); }
 
 const NttFieldOps* ntt_ops_for(int field) {
     switch (field) {
@@ -300,7 +303,7 @@ static int ntt_set_data_common(blz_ntt* h, size_t buf_host, const void* data, si
     if (buf_host > 1) return fail(BLZ_ERR_INVALID_PARAM, "buf_host must be 0 or 1");
     if (len != ntt_bytes(h)) return fail(BLZ_ERR_INVALID_PARAM, "data length %zu != %zu", len, ntt_bytes(h));
     BLZ_NTT_LIVE(h);
-    if (h->in_flight && h->in_flight_buf == (int)buf_host)
+    if (ntt_buf_in_flight(h, buf_host))
         return fail(BLZ_ERR_INVALID_PARAM, "buffer %zu is being transformed; call wait_result first", buf_host);
     if (h->in_flight && ((h->in_flight_reads >> buf_host) & 1u))
         return fail(BLZ_ERR_INVALID_PARAM, "buffer %zu is read by the element-wise op in flight; call wait_result first", buf_host);
@@ -342,6 +345,7 @@ int blz_ntt_start_process(blz_ntt* h, size_t buf_kernel) {
     BLZ_HIP(hipEventRecord(h->ev1, h->stream), BLZ_ERR_UNKNOWN);
     h->in_flight = true;
     h->in_flight_buf = (int)buf_kernel;
+    h->in_flight_buf2 = -1;
     return BLZ_OK;
 }
 
@@ -360,7 +364,7 @@ int blz_ntt_wait_result(blz_ntt* h) {
 static int ntt_result_common(blz_ntt* h, size_t buf, void* out, size_t out_cap, bool on_device) {
     if (!h || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
     if (buf > 1) return fail(BLZ_ERR_INVALID_PARAM, "buffer index must be 0 or 1");
-    if (h->in_flight && h->in_flight_buf == (int)buf)
+    if (ntt_buf_in_flight(h, buf))
         return fail(BLZ_ERR_INVALID_PARAM, "buffer %zu is being transformed; call wait_result first", buf);
     if (out_cap < ntt_bytes(h)) return fail(BLZ_ERR_INVALID_PARAM, "output buffer too small");
     BLZ_NTT_LIVE(h);
@@ -400,7 +404,7 @@ int blz_ntt_exchange(blz_ntt* h, size_t buf, const uint8_t* next_in, size_t in_l
     if (in_len != total) return fail(BLZ_ERR_INVALID_PARAM, "data length %zu != %zu", in_len, total);
     if (out_cap < total) return fail(BLZ_ERR_INVALID_PARAM, "output buffer too small");
     BLZ_NTT_LIVE(h);
-    if (h->in_flight && h->in_flight_buf == (int)buf)
+    if (ntt_buf_in_flight(h, buf))
         return fail(BLZ_ERR_INVALID_PARAM, "buffer %zu is being transformed; call wait_result first", buf);
     if (h->in_flight && ((h->in_flight_reads >> buf) & 1u))
         return fail(BLZ_ERR_INVALID_PARAM, "buffer %zu is read by the element-wise op in flight; call wait_result first", buf);
@@ -635,6 +639,7 @@ int blz_ntt_reset(blz_ntt* h) {
     BLZ_TRY(sync_stream_bounded(h->copy_stream2, "reset: NTT copy stream"));
     h->in_flight = false;
     h->in_flight_reads = 0;
+    h->in_flight_buf2 = -1;
     h->wedged = false;
     return BLZ_OK;
 }
@@ -745,16 +750,19 @@ struct NttVecCall {
         return a < b + qwords * 32 && b < a + words * 32;
     }
 
-    // buf_dst: the transform buffer the op writes (dispatch is handed its words), -1: none
+    // buf_dst: the transform buffer the op writes (dispatch is handed its words), -1: none; buf_dst2: a second one (a sumcheck
+    // step whose tables are both buffers)
     template <class Dispatch>
-    int enqueue(int buf_dst, Dispatch&& dispatch) {
+    int enqueue(int buf_dst, Dispatch&& dispatch, int buf_dst2 = -1) {
         BLZ_HIP(hipEventRecord(h->ev0, h->stream), BLZ_ERR_UNKNOWN);
         BLZ_TRY(dispatch(buf_dst < 0 ? nullptr : h->buf[buf_dst].as<uint32_t>()));
         BLZ_HIP(hipEventRecord(h->ev1, h->stream), BLZ_ERR_UNKNOWN);
         h->in_flight = true;
         h->in_flight_buf = buf_dst;
+        h->in_flight_buf2 = buf_dst2;
         // read-ONLY buffers: the written one is in_flight_buf's to refuse; a reduce writes none and keeps all its read bits
         h->in_flight_reads = buf_dst < 0 ? reads : reads & ~(1u << buf_dst);
+        if (buf_dst2 >= 0) h->in_flight_reads &= ~(1u << buf_dst2);
         return BLZ_OK;
     }
 };
@@ -956,6 +964,51 @@ int blz_ntt_stream(blz_ntt* h, void** hip_stream, int* device_id) {
     if (device_id) *device_id = h->device;
     *hip_stream = (void*)h->stream;
     return BLZ_OK;
+}
+
+// A sumcheck step (ntt_sumcheck.hip.hpp): with r every table is folded in place and the round polynomial is taken of the
+// folded tables in the same pass; without r the round alone; points == 0 the folds alone.  With r BOTH transform buffers may be
+// tables and are then both written: the second is recorded in in_flight_buf2.
+int blz_ntt_sumcheck_step(blz_ntt* h, uint32_t gate, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c, const blz_vec_arg* d,
+                          const blz_vec_arg* r, uint32_t points, uint64_t len, void* d_out) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (gate != BLZ_GATE_PRODUCT && gate != BLZ_GATE_R1CS) return fail(BLZ_ERR_INVALID_PARAM, "unknown gate %u", gate);
+    const blz_vec_arg* const tv[4] = {a, b, c, d};
+    int k = 0;
+    while (k < 4 && tv[k]) ++k;
+    for (int j = k; j < 4; ++j)
+        if (tv[j]) return fail(BLZ_ERR_INVALID_PARAM, "a gate takes its tables as a, then b, then c, then d: %c is NULL while %c is set", 'a' + k, 'a' + j);
+    if (gate == BLZ_GATE_R1CS ? k != 4 : (k < 1 || k > 3))
+        return fail(BLZ_ERR_INVALID_PARAM, "%s, %d given", gate == BLZ_GATE_R1CS ? "BLZ_GATE_R1CS takes the four tables a, b, c, d" : "BLZ_GATE_PRODUCT takes 1 to 3 tables (d must be NULL)", k);
+    if (points > 4) return fail(BLZ_ERR_INVALID_PARAM, "points %u is not in [0, 4]", points);
+    if (points == 0 && (!r || d_out)) return fail(BLZ_ERR_INVALID_PARAM, "points 0 is a bind alone: it takes r and a NULL d_out");
+    if (points > 0 && !d_out) return fail(BLZ_ERR_INVALID_PARAM, "null d_out");
+    if (r && (!r->d_ptr || r->count != 1))
+        return fail(BLZ_ERR_INVALID_PARAM, "a sumcheck step takes the challenge as one device word: r.d_ptr != NULL, r.count == 1");
+    NttVecCall call{h};
+    BLZ_TRY(call.live_length(len));
+    if (r && points > 0 && len < 4) return fail(BLZ_ERR_INVALID_PARAM, "len %llu: a bind and a round need len >= 4", (unsigned long long)len);
+    BLZ_TRY(call.begin());
+    NttVecArg vt[4]{}, vr{};
+    BLZ_TRY(call.resolve({{"a", a, &vt[0]}, {"b", b, &vt[1]}, {"c", c, &vt[2]}, {"d", d, &vt[3]}, {"r", r, &vr}}, "d_out", d_out, points));
+    int wbuf[2] = {-1, -1};
+    if (r) {
+        const uint64_t half = len >> 1;
+        for (int j = 0; j < k; ++j) {
+            if (vt[j].mask + 1 < len)
+                return fail(BLZ_ERR_INVALID_PARAM, "operand %c: %llu words, read periodically over len %llu: a periodic table cannot be folded in place", 'a' + j,
+                            (unsigned long long)(vt[j].mask + 1), (unsigned long long)len);
+            for (int i = 0; i < j; ++i)
+                if (NttVecCall::words_meet(vt[i].p, len, vt[j].p, len))
+                    return fail(BLZ_ERR_INVALID_PARAM, "tables %c and %c overlap in their first len words: each is folded in place", 'a' + i, 'a' + j);
+            if (NttVecCall::words_meet(vr.p, 1, vt[j].p, half)) return fail(BLZ_ERR_INVALID_PARAM, "r lies in the words table %c receives", 'a' + j);
+            if (d_out && NttVecCall::words_meet(d_out, points, vt[j].p, len))
+                return fail(BLZ_ERR_INVALID_PARAM, "d_out lies in the live words of table %c", 'a' + j);
+            if (!tv[j]->d_ptr) wbuf[wbuf[0] < 0 ? 0 : 1] = (int)tv[j]->buf;
+        }
+    }
+    return call.enqueue(wbuf[0], [&](uint32_t*) { return h->ops->sumcheck_step(h->stream, gate, k, vt, r ? vr.p : nullptr, points, len, (uint32_t*)d_out, call.ws); },
+                        wbuf[1]);
 }
 
 int blz_ntt_last_kernel_ms(blz_ntt* h, float* out) {

@@ -137,6 +137,13 @@ struct NttFieldOps {
                          uint64_t len, uint32_t* ws);
     // dst[p] = eq(point, p), p < 2^m; point: m device words (not read when m == 0)
     int (*vec_mle_eq)(hipStream_t st, uint32_t* dst, const uint32_t* point, uint32_t m, uint32_t* ws);
+    // A sumcheck step (blz_ntt_sumcheck_step; kernels and the workspace's layout: ntt_sumcheck.hip.hpp) over the gate's k tables
+    // t[0 .. k) (BLZ_GATE_PRODUCT: 1 .. 3, BLZ_GATE_R1CS: 4), top-variable pairing.  r (one device word) != nullptr: every table
+    // is folded in place - it holds at least len words, no two overlap, len / 2 words of each are written - and out[t], t < points,
+    // is the round polynomial of the folded tables (len >= 4); points == 0: the folds alone (len >= 2), out is not looked at.
+    // r == nullptr: the round polynomial of the tables as they are (periodic ones allowed), nothing else is written
+    int (*sumcheck_step)(hipStream_t st, uint32_t gate, int k, const NttVecArg* t, const uint32_t* r, uint32_t points, uint64_t len,
+                         uint32_t* out, uint32_t* ws);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

@@ -10,6 +10,7 @@
 #include "ntt_gather.hip.hpp"
 #include "ntt_spmv.hip.hpp"
 #include "ntt_mle.hip.hpp"
+#include "ntt_sumcheck.hip.hpp"
 
 namespace blz {
 
@@ -526,6 +527,7 @@ NttFieldOps make_ntt_ops() {
     o.vec_mle_fold = &ntt_vec_mle_fold_t<Fr>;
     o.vec_mle_round = &ntt_vec_mle_round_t<Fr>;
     o.vec_mle_eq = &ntt_vec_mle_eq_t<Fr>;
+    o.sumcheck_step = &ntt_sumcheck_step_t<Fr>;
     return o;
 }
 

@@ -46,6 +46,7 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
     SCAN_EXCLUSIVE = 1                              # BLZ_SCAN_EXCLUSIVE
     HORNER_EXCLUSIVE, HORNER_REVERSE = 1, 2         # BLZ_HORNER_*
     MLE_LOW = 1                                     # BLZ_MLE_LOW
+    GATE_PRODUCT, GATE_R1CS = 0, 1                  # BLZ_GATE_*
 
     def __init__(self, _ptype: NTT, dclient: DriverClient, log_size: int = NTT_LOG_SIZE, inverse: bool = False,
                  field: str = "BLS381", flags: int = 0, root: Optional[int] = None):
@@ -303,6 +304,31 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
             m = 0 if point is None else point.nbytes // NTT_WORD_SIZE
         check(lib().blz_ntt_vec_mle_eq(self._h, None if vd is None else C.byref(vd), None if point is None else point.ptr, int(m)))
         self._vec_keep = (dst, point)
+
+    def sumcheck_step(self, tables, r: Optional[DeviceBuffer] = None, gate: int = GATE_PRODUCT, points: Optional[int] = None,
+                      length: Optional[int] = None, out: Optional[DeviceBuffer] = None) -> Optional[DeviceBuffer]:
+        """One step of a sumcheck in one pass (blz_ntt_sumcheck_step).  `tables` are the gate's operands in order - ints
+        (transform buffers) or DeviceBuffers -: GATE_PRODUCT takes 1 to 3 (G = a, a b, a b c), GATE_R1CS four (G = a (b c - d)).
+        With `r` (a one-word DeviceBuffer the host never reads) every table is folded IN PLACE, T[p] = T[p] + r (T[p + length / 2]
+        - T[p]) for p < length / 2 - exactly length / 2 words of each are written - and out[t], t < points, is the round
+        polynomial of the folded tables: what vec_mle_round at length / 2 would return.  Without `r` it is the round polynomial
+        of the tables as they are (a sumcheck's first round; nothing is written to a table).  points defaults to the gate's degree
+        + 1 (4 for GATE_R1CS); points=0 (with r) binds only and returns None - a sumcheck's last variable.  Otherwise returns the
+        DeviceBuffer of points x 32 bytes the canonical values land in (`out`, or a fresh one).  Both transform buffers may be
+        tables; with `r` neither can then be read or written until wait_result() has finished the op."""
+        tables = list(tables)
+        if len(tables) > 4:
+            raise ValueError(f"a gate takes at most four tables, {len(tables)} given")
+        if points is None:
+            points = 4 if gate == self.GATE_R1CS else len(tables) + 1
+        points = int(points)
+        if out is None and points > 0:
+            out = DeviceBuffer(self.driver_client.id, NTT_WORD_SIZE * points)
+        args = [self._vec_arg(x) for x in tables + [None] * (4 - len(tables)) + [r]]
+        check(lib().blz_ntt_sumcheck_step(self._h, int(gate), *[None if v is None else C.byref(v) for v in args], points,
+                                          self._mle_len(length, *(tables or [0])), None if out is None else out.ptr))
+        self._vec_keep = (*tables, r, out)
+        return out if points > 0 else None
 
     def scalar(self, value: int) -> DeviceBuffer:
         """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""

@@ -310,6 +310,15 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
         check(blz_ntt_vec_mle_round(h_, flags, a, b, c, points ? points : 2u + (b ? 1u : 0u) + (c ? 1u : 0u), len, d_out));
     }
     void vec_mle_eq(const blz_vec_arg* dst, const void* d_point, uint32_t m) { check(blz_ntt_vec_mle_eq(h_, dst, d_point, m)); }
+    // a sumcheck step in one pass (blz_ntt_sumcheck_step): with r (one device word) every table given (a, b, c, d; nullptr: not
+    // taken) is folded in place - len / 2 words of each are written - and d_out[t], t < points, is the round polynomial of the gate
+    // (BLZ_GATE_PRODUCT: a, a b, a b c; BLZ_GATE_R1CS: a (b c - d)) on the folded tables; without r the round polynomial of the
+    // tables as they are.  points defaults to the gate's degree + 1; bind_only (r, no d_out) folds and takes no round
+    void sumcheck_step(uint32_t gate, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c, const blz_vec_arg* d,
+                       const blz_vec_arg* r, uint64_t len, void* d_out, uint32_t points = 0, bool bind_only = false) {
+        const uint32_t degree = gate == BLZ_GATE_R1CS ? 3u : 1u + (b ? 1u : 0u) + (c ? 1u : 0u);
+        check(blz_ntt_sumcheck_step(h_, gate, a, b, c, d, r, bind_only ? 0u : points ? points : degree + 1u, len, d_out));
+    }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

@@ -628,6 +628,44 @@ int blz_ntt_vec_mle_eq(blz_ntt* h, const blz_vec_arg* dst, const void* d_point, 
  * scale the group count (n >> 18, at least 1). */
 int blz_ntt_banks_preprocess_device(blz_ntt* h, const void* d_in, void* d_banks);
 int blz_ntt_banks_postprocess_device(blz_ntt* h, const void* d_banks, void* d_out);
+/* A sumcheck step on resident tables: bind the top variable of every table to r and take the NEXT round polynomial in the same
+ * pass - the fold's output is the round's input, so one op reads each table once where a blz_ntt_vec_mle_fold per table and the
+ * blz_ntt_vec_mle_round calls behind them read the folded halves again - and a fourth operand, so that eq (Az o Bz - Cz) is one
+ * gate.  Everything is over the handle's field, by buffer POSITION, with the top-variable pairing of blz_ntt_vec_mle_fold
+ * ((T[p], T[p + len / 2]); BLZ_MLE_LOW is not offered: fused and in place a lane would write words another lane still reads).
+ *   Gates: BLZ_GATE_PRODUCT  G = a, a b or a b c - k = 1 .. 3 tables given as a, then b, then c; d must be NULL;
+ *          BLZ_GATE_R1CS     G = a (b c - d) - all four tables.
+ *   r != NULL - bind, then round.  r is one device word under BLZ_FOLD_EVAL's rule (d_ptr != NULL, count == 1); the host never
+ *     reads it.  Every table T given is folded IN PLACE: T[p] = T[p] + r (T[p + len / 2] - T[p]) for p < len / 2 - exactly len / 2
+ *     words of each table are written, every other byte keeps its value.  Then
+ *       d_out[t] = sum_{p < len / 4} G(.., T_j[p] + t (T_j[p + len / 4] - T_j[p]), ..) for t < points,
+ *     which is what blz_ntt_vec_mle_round at length len / 2 returns on the folded tables.  len >= 4, 1 <= points <= 4.
+ *     points == 0 with d_out == NULL is a bind alone: all k tables folded in one op, len >= 2, the gate ignored apart from its
+ *     operand-count rule - a sumcheck's last variable.
+ *   r == NULL - round only, a sumcheck's first round: d_out[t] = sum_{p < len / 2} G(.. lo_j + t (hi_j - lo_j) ..) with the pairs
+ *     (T[p], T[p + len / 2]).  No table is written; len >= 2, 1 <= points <= 4; periodic tables (count < len) are allowed, as in
+ *     blz_ntt_vec_mle_round.
+ *   Values: any 256-bit input word counts as its residue; every word written - table words and d_out alike - is canonical,
+ *   little-endian.  Tables are blz_vec_arg operands, checked by blz_ntt_vec_op's code.
+ *   A sumcheck of m variables is blz_ntt_vec_mle_eq, a step without r, m - 1 steps with r, and a bind alone: m + 2 ops.
+ *   Cost ("Sumcheck step"; derived from the code): with r each table's len words are read and len / 2
+ *   written, once; Montgomery products per quad of four input words per table: 2 k for the folds, plus points x (k - 1)
+ *   (PRODUCT) or 2 + 2 points (R1CS: 18 at 4 points, against 20 in the six ops the step replaces).
+ *   Protocol: that of blz_ntt_vec_mle_fold.  Everything is checked before anything is enqueued; the op runs on the compute
+ *   stream; blz_ntt_wait_result finishes it, blz_ntt_last_kernel_ms then reports it, blz_ntt_reset drops it.  With r BOTH
+ *   transform buffers may be tables and are then both written: while the op is in flight neither may be read, written or
+ *   exchanged.  Without r the buffers named are read-only, as for a reduce.  Memory behind every pointer stays valid until
+ *   blz_ntt_wait_result returns.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing: a null handle (refused before any other argument is looked at), an unknown gate, a
+ *   missing or surplus table, points above 4, points == 0 without r or with a d_out, a null d_out with points > 0, len not a
+ *   power of two in [2, n] ([4, n] for a bind and a round), r naming a buffer or with count != 1, an op in flight, any operand
+ *   error of blz_ntt_vec_op, a bad d_out or one that overlaps a d_ptr operand; with r: a table with count < len, two tables whose
+ *   first len words overlap (the same table named twice is an overlap), r inside the words written, d_out inside the first len
+ *   words of a table. */
+#define BLZ_GATE_PRODUCT 0u   /* G = a, a b or a b c (k = 1 .. 3 tables; d must be NULL) */
+#define BLZ_GATE_R1CS    1u   /* G = a (b c - d)     (all four tables) */
+int blz_ntt_sumcheck_step(blz_ntt* h, uint32_t gate, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c,
+                          const blz_vec_arg* d, const blz_vec_arg* r, uint32_t points, uint64_t len, void* d_out);
 
 /* ------------------------------------------------------------------ Poseidon octal Merkle tree (src/ingo_hash/poseidon_api.rs)
  *

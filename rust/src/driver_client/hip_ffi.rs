@@ -49,6 +49,10 @@ pub struct BlzVecCsr {
 }
 /// `BLZ_MLE_LOW`: `blz_ntt_vec_mle_fold` / `_round` pair (a\[2p\], a\[2p + 1\]) - variable 0 - instead of (a\[p\], a\[p + len / 2\]).
 pub const BLZ_MLE_LOW: u32 = 1;
+/// `BLZ_GATE_PRODUCT`: the gate of `blz_ntt_sumcheck_step` is the product of its 1 to 3 tables.
+pub const BLZ_GATE_PRODUCT: u32 = 0;
+/// `BLZ_GATE_R1CS`: the gate is a (b c - d) over its four tables.
+pub const BLZ_GATE_R1CS: u32 = 1;
 
 pub const BLZ_COMM_ID_BYTES: usize = 128;
 
@@ -142,6 +146,8 @@ extern "C" {
     pub fn blz_ntt_vec_mle_round(h: *mut BlzNtt, flags: u32, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg, points: u32,
                                  len: u64, d_out: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_mle_eq(h: *mut BlzNtt, dst: *const BlzVecArg, d_point: *const c_void, m: u32) -> c_int;
+    pub fn blz_ntt_sumcheck_step(h: *mut BlzNtt, gate: u32, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg, d: *const BlzVecArg,
+                                 r: *const BlzVecArg, points: u32, len: u64, d_out: *mut c_void) -> c_int;
 
     // ---- Poseidon tree: PoseidonClient (ingo_hash::poseidon_api)
     pub fn blz_poseidon_new(device_id: c_int, field: c_int, out: *mut *mut BlzPoseidon) -> c_int;

@@ -280,6 +280,26 @@ impl NTTClient {
         check(blz_ntt_vec_mle_eq(self.h, &rd, d_point, m))
     }
 
+    /// One step of a sumcheck in one pass (blz_ntt_sumcheck_step).  `tables` are the gate's operands a, b, c, d in order, the ones
+    /// not taken `None`: `BLZ_GATE_PRODUCT` takes 1 to 3 (G = a, a b, a b c), `BLZ_GATE_R1CS` (`r1cs`) four (G = a (b c - d)).  With `r` (one device word the host never reads)
+    /// every table is folded IN PLACE - T\[p\] = T\[p\] + r (T\[p + len / 2\] - T\[p\]) for p < `len` / 2, exactly len / 2 words
+    /// of each - and `d_out`\[t\], t < `points` (1 ..= 4), is the round polynomial of the folded tables: what `vec_mle_round` at
+    /// len / 2 would write.  Without `r` it is the round polynomial of the tables as they are and nothing else is written.
+    /// `points` = 0 with a null `d_out` (and `r`) binds only.  Both transform buffers may be tables; with `r` both are then
+    /// written.
+    ///
+    /// # Safety
+    /// As for `vec_mle_fold`: with `r`, device words named by `tables` are WRITTEN until `wait_result` returns; `d_out` as for
+    /// `vec_reduce`.
+    pub unsafe fn sumcheck_step(&self, r1cs: bool, tables: [Option<VecOperand>; 4], r: Option<VecOperand>, points: u32, len: u64,
+                                d_out: *mut std::os::raw::c_void) -> Result<()> {
+        let raw = tables.map(|v| v.map(|x| x.raw()));
+        let rr = r.map(|v| v.raw());
+        let p = |v: &Option<BlzVecArg>| v.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg);
+        check(blz_ntt_sumcheck_step(self.h, if r1cs { BLZ_GATE_R1CS } else { BLZ_GATE_PRODUCT }, p(&raw[0]), p(&raw[1]), p(&raw[2]), p(&raw[3]),
+                                    p(&rr), points, len, d_out))
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
