@@ -178,6 +178,8 @@ _AUX_SIGS = {
                                          C.c_char_p, C.c_size_t]),
     "blz_test_law_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     "blz_test_law_op": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _u8p, _u8p, C.c_size_t]),
+    "blz_test_rr_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    "blz_test_rr_op": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, _u8p, C.c_size_t]),
     "blz_test_sort_fits_beside": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "blz_test_poseidon_permute": (C.c_int, [C.c_int, C.c_int, _u8p, C.c_size_t, C.c_int, _u8p, _u8p, C.c_size_t]),
     "blz_test_poseidon_hash": (C.c_int, [C.c_int, C.c_int, _u8p, C.c_size_t, C.c_int, _u8p, _u8p, C.c_size_t]),

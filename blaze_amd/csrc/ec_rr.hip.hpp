@@ -119,7 +119,7 @@ __device__ __noinline__ XYZZRR<Q> ptrr_mdbl_val(Frr<Q, 1, 2> x, Frr<Q, 2, 4> y) 
     __builtin_amdgcn_sched_barrier(0);
     const auto X3 = rr_xfix(rr_sub_twice<2>(Msq, S));  // M^2 - 2S + 8m: (1, 10) | (1, 2)
     const auto D = rr_tn(rr_sub<RR_JX<Q>>(S, X3));     // S - X3 + 32m: (3, 34) | + 4m: (1, 6)
-    const auto nW = rr_neg<2>(W);                      // 4m - W: (2, 4)
+    const auto nW = rr_neg<2>(W);                      // 4m - W: (2, 5)
     rr_mul2(y3, M, D, nW, y);                          // M (S - X3) - W y
     r.x = rr_as<1, XYZZRR<Q>::VX>(X3);
     r.y = rr_as<1, XYZZRR<Q>::VY>(y3);
@@ -160,7 +160,7 @@ BLZ_DEV void ptrr_madd(XYZZRR<Q>& acc, const AffineRR<Q>& q, bool neg) {
     rr_mul_pair(acc.zzz, acc.zzz, PPP, Qv, acc.x, PP); // ZZZ3, Q
     const auto X3 = rr_xfix(rr_sub_twice<2>(rr_sub<2>(t, PPP), Qv));  // R^2 - PPP - 2Q + 12m: (1, 14) | (1, 2)
     const auto D = rr_tn(rr_sub<RR_JX<Q>>(Qv, X3));    // Q - X3 + 32m: (3, 34) | + 4m: (1, 6)
-    const auto nY = rr_neg<RR_JY<Q>>(acc.y);           // 8m - Y1: (2, 8) | 4m - Y1: (2, 4)
+    const auto nY = rr_neg<RR_JY<Q>>(acc.y);           // 8m - Y1: (2, 9) | 4m - Y1: (2, 5)
     rr_mul2(y3, R, D, nY, PPP);                        // R (Q - X3) - Y1 PPP, one reduction
     acc.x = rr_as<1, XYZZRR<Q>::VX>(X3);
     acc.y = rr_as<1, XYZZRR<Q>::VY>(y3);
@@ -190,7 +190,7 @@ BLZ_DEV void ptrr_aadd(XYZZRR<Q>& acc, const AffineRR<Q>& p, bool negp, const Af
     rr_sqr(t, R);
     const auto X3 = rr_xfix(rr_sub_twice<2>(rr_sub<2>(t, PPP), Qv));  // (1, 14) | (1, 2)
     const auto D = rr_tn(rr_sub<RR_JX<Q>>(Qv, X3));    // (3, 34) | (1, 6)
-    const auto nY = rr_neg<3>(y1);                     // (2, 8)
+    const auto nY = rr_neg<3>(y1);                     // (2, 9)
     rr_mul2(y3, R, D, nY, PPP);                        // R (Q - X3) - y1 PPP
     acc.x = rr_as<1, XYZZRR<Q>::VX>(X3);
     acc.y = rr_as<1, XYZZRR<Q>::VY>(y3);
@@ -225,7 +225,7 @@ BLZ_DEV void ptrr_jdbl(JacRR<Q>& p) {
     const auto X3 = rr_xfix(rr_sub_twice<RR_TIGHT<Q> ? 2 : 4>(E2, S4));   // E^2 - 8S + 32m: (1, 34) | + 8m: (1, 2)
     const auto D = rr_tn(rr_sub<JacRR<Q>::JX>(S4, X3));   // 4S - X3 + 128m: (3, 136) | + 4m: (1, 6)
     const auto b2 = rr_add(B, B);                      // (2, 4)
-    const auto nB4 = rr_neg<4>(rr_norm(rr_add(b2, b2)));   // 16m - 4 Y^2: (2, 16)
+    const auto nB4 = rr_neg<4>(rr_norm(rr_add(b2, b2)));   // 16m - 4 Y^2: (2, 17)
     // E (4S - X3) - 8 Y^4 = E D + (16m - 4 Y^2)(2 Y^2), one reduction: columns 9 + 4, values 816 + 64 | 1 + 4, 36 + 64
     rr_mul2(y3, E, D, nB4, b2);
     p.x = X3;
@@ -248,7 +248,7 @@ __device__ __noinline__ XYZZRR<Q> ptrr_dbl_val(XYZZRR<Q> p) {
     rr_sqr(Msq, M);
     const auto X3 = rr_xfix(rr_sub_twice<2>(Msq, S));  // (1, 10) | (1, 2)
     const auto D = rr_tn(rr_sub<RR_JX<Q>>(S, X3));     // (3, 34) | (1, 6)
-    const auto nW = rr_neg<2>(W);                      // (2, 4)
+    const auto nW = rr_neg<2>(W);                      // (2, 5)
     rr_mul2(y3, M, D, nW, p.y);                        // M (S - X3) - W Y1
     r.x = rr_as<1, XYZZRR<Q>::VX>(X3);
     r.y = rr_as<1, XYZZRR<Q>::VY>(y3);
@@ -284,7 +284,7 @@ BLZ_DEV void ptrr_add(XYZZRR<Q>& acc, const XYZZRR<Q>& q) {
     rr_sqr(t, R);
     const auto X3 = rr_xfix(rr_sub_twice<2>(rr_sub<2>(t, PPP), Qv));  // (1, 14) | (1, 2)
     const auto D = rr_tn(rr_sub<RR_JX<Q>>(Qv, X3));    // (3, 34) | (1, 6)
-    const auto nS1 = rr_neg<2>(S1);                    // (2, 4)
+    const auto nS1 = rr_neg<2>(S1);                    // (2, 5)
     rr_mul2(y3, R, D, nS1, PPP);                       // R (Q - X3) - S1 PPP
     acc.x = rr_as<1, XYZZRR<Q>::VX>(X3);
     acc.y = rr_as<1, XYZZRR<Q>::VY>(y3);

@@ -198,8 +198,12 @@ BLZ_DEV void rr_mul2(Frr<Q, 1, 2>& r, const Frr<Q, Fa, Va>& a, const Frr<Q, Fb, 
 // (NL^2 - 28 = 53 multiply-adds at NL = 9: the columns left out are worth < 2^-26 of q's unit, so q is that floor or one
 // below), then x w + q (Rrr - m), i.e. x w - q m modulo Rrr, in NL columns (90 multiply-adds): 143 against the Montgomery
 // product's 153, no quotient-digit chain between the columns (+14.6 % products per second at two waves per SIMD,
-// profiles/r03_shoup_probe.txt), the result the plain product x w - no Montgomery factor.  The truncation can leave the
-// result in [2m, 3m): a top-limb compare (T2M) and a rarely taken subtraction of m bring every result below 2m.
+// profiles/r03_shoup_probe.txt), the result the plain product x w - no Montgomery factor.  With q one below the floor at most,
+// the result is below (1 + x / Rrr + F NL 2^-B) m: for an x the type admits (x < 2^HEAD m = 2^-BITS m Rrr) that is below 1.59 m
+// (BLS12-377), 1.91 m (BLS12-381) and 1.76 m (BN254), so the top-limb compare (T2M) and the subtraction of m behind it are not
+// reached from typed operands: the exact model of these columns (tests/rr_image_util.py shoup_model), on inputs crafted to sit on
+// the truncation and at the top of the range, never takes it (the test prints the largest result it meets), and the device agrees
+// with the model limb for limb (tests/test_gpu_rr_primitives.py).  The branch stays: it guards an operand beyond its type.
 // x: any limbs the column bound admits (F <= 6 at 9 x 29 bits), value < Rrr (guaranteed by the type: V m < Rrr).
 template <class Q>
 struct RRShoup {
@@ -471,22 +475,25 @@ BLZ_DEV Frr<Q, Fa + 4, Va + (2 << J)> rr_sub_twice(const Frr<Q, Fa, Va>& a, cons
     for (int i = 0; i < Q::NL; ++i) r.v[i] = a.v[i] + 2u * (Q::KM[J - 1][i] - b.v[i]);
     return r;
 }
-// 2^J m - b
+// 2^J m - b.  For b = 0 this IS 2^J m, so the value bound is 2^J + 1: the result is an operand of products only, where the
+// extra m costs nothing (the value budgets of ec_rr.hip.hpp's rr_mul2 have room for it).
 template <int J, class Q, int Vb>
-BLZ_DEV Frr<Q, 2, (1 << J)> rr_neg(const Frr<Q, 1, Vb>& b) {
+BLZ_DEV Frr<Q, 2, (1 << J) + 1> rr_neg(const Frr<Q, 1, Vb>& b) {
     static_assert(J >= 1 && J <= Q::NKM && Vb <= (1 << (J - 1)), "multiple of m too small");
-    Frr<Q, 2, (1 << J)> r;
+    Frr<Q, 2, (1 << J) + 1> r;
 #pragma unroll
     for (int i = 0; i < Q::NL; ++i) r.v[i] = Q::KM[J - 1][i] - b.v[i];
     return r;
 }
-// sign ? 2^J m - b : b   (per lane)
+// sign && b != 0 ? 2^J m - b : b   (per lane).  A literal zero stays zero: 2^J m - 0 would be one past the "< 2^J m" of the
+// result, which - unlike rr_neg's - is stored and subtracted (an accumulator's y, rr_sub's b) and has to keep its bound.
 template <int J, class Q, int Vb>
 BLZ_DEV Frr<Q, 2, (1 << J)> rr_cneg(const Frr<Q, 1, Vb>& b, bool sign) {
     static_assert(J >= 1 && J <= Q::NKM && Vb <= (1 << (J - 1)), "multiple of m too small");
     Frr<Q, 2, (1 << J)> r;
+    const bool flip = sign && !rr_all_zero(b);
 #pragma unroll
-    for (int i = 0; i < Q::NL; ++i) r.v[i] = sign ? Q::KM[J - 1][i] - b.v[i] : b.v[i];
+    for (int i = 0; i < Q::NL; ++i) r.v[i] = flip ? Q::KM[J - 1][i] - b.v[i] : b.v[i];
     return r;
 }
 // carry propagation: limbs < 2^B again (the top limb keeps the rest; V m < Rrr by the type's own bound)

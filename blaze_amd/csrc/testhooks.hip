@@ -5,7 +5,9 @@
 #include "ec_row.hip.hpp"
 #include "ec_law.hip.hpp"
 #include "poseidon_engine.hpp"
+#include "poseidon_impl.hip.hpp"   // rr_dot
 #include "msm_engine.hpp"
+#include "../../include/blaze_hip_aux.h"
 
 namespace blz {
 
@@ -727,6 +729,502 @@ static int test_law_dispatch(int curve, int repr, int law, LawLayout* layout, co
     return fail(BLZ_ERR_INVALID_PARAM, "no group laws for curve %d with arithmetic %d", curve, repr);
 }
 
+// ---- the reduced-radix primitives one by one, operands at the top of what their types admit (include/blaze_hip_aux.h
+// blz_test_rr_op).  A VARIANT is one instantiation of one primitive: its operand and result types are the whole description - the
+// layout reads (F, V) off them with rr_bounds, and a variant whose types a static_assert refuses does not compile, so the lists
+// below hold only what the code admits.  Images go in and out limb for limb.
+enum { RR_MUL = 0, RR_SQR, RR_MUL2, RR_PAIR, RR_DOT, RR_SHOUP, RR_SHOUP_U, RR_SHOUP_QUOT, RR_NORM, RR_REDUCE2M, RR_SUB, RR_SUB_TWICE, RR_NEG,
+       RR_CNEG, RR_BFLY, RR_CANON, RR_ZERO, RR_WORDS, RR_DFT8 };
+
+// images that are no Frr: flags (dword j = flag j), N32 raw 32-bit words, normalised limbs of any integer below Rrr
+struct RrFlags {};
+template <class Q> struct RrWords {};
+template <class Q> struct RrRaw {};
+template <> struct rr_bounds<RrFlags> { static constexpr int f = 0, v = 0; };
+template <class Q> struct rr_bounds<RrWords<Q>> { static constexpr int f = 0, v = 1; };
+template <class Q> struct rr_bounds<RrRaw<Q>> { static constexpr int f = 1, v = 0; };
+
+template <class... T> struct TL { static constexpr int n = sizeof...(T); };
+template <class... L> struct Cat { using type = TL<>; };
+template <class... A> struct Cat<TL<A...>> { using type = TL<A...>; };
+template <class... A, class... B, class... R> struct Cat<TL<A...>, TL<B...>, R...> : Cat<TL<A..., B...>, R...> {};
+template <class... L> using cat_t = typename Cat<L...>::type;
+template <int N, class T> struct Rep { using type = cat_t<TL<T>, typename Rep<N - 1, T>::type>; };
+template <class T> struct Rep<0, T> { using type = TL<>; };
+template <bool C, class T> using only_if = std::conditional_t<C, TL<T>, TL<>>;   // (naming T does not instantiate it)
+template <class O> struct OctTypes;
+template <class... T> struct OctTypes<RROct<T...>> { using type = TL<T...>; };
+
+template <class T>
+BLZ_DEV T rr_img(const uint32_t* in, int k) {
+    constexpr int NL = sizeof(T) / 4;
+    T r;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) r.v[i] = in[k * NL + i];
+    return r;
+}
+template <class T>
+BLZ_DEV void rr_put(uint32_t* out, int k, const T& a) {
+    constexpr int NL = sizeof(T) / 4;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) out[k * NL + i] = a.v[i];
+}
+template <int NL, int N>
+BLZ_DEV void rr_put_words(uint32_t* out, int k, const uint32_t (&w)[N]) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) out[k * NL + i] = i < N ? w[i] : 0u;
+}
+
+// the widest bounds the static_asserts of field_rr.hip.hpp admit for a field
+template <class Q>
+struct RrLim {
+    static constexpr int H = rr_head<Q>(), VMAX = 1 << H, FMAX = (1 << (32 - Q::B)) - 1;   // Frr's own limits
+    static constexpr int fs() { int f = 1; while (rr_cols_ok<Q>(f + 1)) ++f; return f; }
+    static constexpr int FS = fs();                        // the largest sum of F products a column admits
+    static constexpr int F1 = FS < FMAX ? FS : FMAX;       // the largest F against a normalised operand
+    static constexpr int isqrt(int x) { int r = 1; while ((r + 1) * (r + 1) <= x) ++r; return r; }
+    static constexpr int FBA = isqrt(FS), FBB = FS / FBA;  // the most balanced pair
+    static constexpr int VBA = 1 << (H / 2), VBB = 1 << (H - H / 2);
+    static constexpr int FSQ = 2 * isqrt(FS) <= FMAX ? isqrt(FS) : FMAX / 2;
+    static constexpr int FM2 = isqrt(FS - 1);              // a b + c d balanced: FM2^2 + 1 (FS - FM2^2)
+    static constexpr int FM2A = FS - 1 < FMAX ? FS - 1 : FMAX;   // ... and one-sided: FM2A 1 + (FS - FM2A) 1
+    static constexpr int VHA = 1 << ((H - 1) / 2), VHB = 1 << (H - 1 - (H - 1) / 2);
+    static constexpr bool r2m_ok(unsigned long long v) {
+        return 4ull * (v + 1) <= Q::MOD[Q::NL - 1] && (v + 1) * (Q::MOD[Q::NL - 1] + 1ull) <= (1ull << 30);
+    }
+    static constexpr int r2m_v() { int v = 1; while (v < VMAX && r2m_ok(v + 1)) ++v; return v; }
+    static constexpr int VR2M = r2m_v();                   // the largest V rr_reduce2m's two static_asserts admit
+    static constexpr int VIN1 = 1 << (32 * Q::N32 + 1 - Q::BITS);   // a wire word as the first NTT pass reads it (ntt_rr.hip.hpp)
+};
+
+template <class Q, int VAR, int Fa, int Va, int Fb, int Vb>
+struct RrvMul {
+    using RQ = Q;
+    static constexpr int op = RR_MUL, var = VAR, param = 0;
+    using A = Frr<Q, Fa, Va>;
+    using Bt = Frr<Q, Fb, Vb>;
+    using In = TL<A, Bt>;
+    using Out = TL<Frr<Q, 1, 2>, Frr<Q, 1, 2>>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        const A a = rr_img<A>(in, 0);
+        const Bt b = rr_img<Bt>(in, 1);
+        Frr<Q, 1, 2> r, s;
+        rr_mul(r, a, b);
+        rr_mul_ref(s, a, b);
+        rr_put(out, 0, r);
+        rr_put(out, 1, s);
+    }
+};
+template <class Q, int VAR, int Fa, int Va>
+struct RrvSqr {
+    using RQ = Q;
+    static constexpr int op = RR_SQR, var = VAR, param = 0;
+    using A = Frr<Q, Fa, Va>;
+    using In = TL<A>;
+    using Out = TL<Frr<Q, 1, 2>>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        Frr<Q, 1, 2> r;
+        rr_sqr(r, rr_img<A>(in, 0));
+        rr_put(out, 0, r);
+    }
+};
+template <class Q, int VAR, int Fa, int Va, int Fb, int Vb, int Fc, int Vc, int Fd, int Vd>
+struct RrvMul2 {
+    using RQ = Q;
+    static constexpr int op = RR_MUL2, var = VAR, param = 0;
+    using A = Frr<Q, Fa, Va>;
+    using Bt = Frr<Q, Fb, Vb>;
+    using Ct = Frr<Q, Fc, Vc>;
+    using Dt = Frr<Q, Fd, Vd>;
+    using In = TL<A, Bt, Ct, Dt>;
+    using Out = TL<Frr<Q, 1, 2>>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        Frr<Q, 1, 2> r;
+        rr_mul2(r, rr_img<A>(in, 0), rr_img<Bt>(in, 1), rr_img<Ct>(in, 2), rr_img<Dt>(in, 3));
+        rr_put(out, 0, r);
+    }
+};
+template <class Q, int VAR, int Fa, int Va, int Fb, int Vb, int Fc, int Vc, int Fd, int Vd>
+struct RrvMulPair {
+    using RQ = Q;
+    static constexpr int op = RR_PAIR, var = VAR, param = 0;
+    using A = Frr<Q, Fa, Va>;
+    using Bt = Frr<Q, Fb, Vb>;
+    using Ct = Frr<Q, Fc, Vc>;
+    using Dt = Frr<Q, Fd, Vd>;
+    using In = TL<A, Bt, Ct, Dt>;
+    using Out = TL<Frr<Q, 1, 2>, Frr<Q, 1, 2>>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        Frr<Q, 1, 2> r1, r2;
+        rr_mul_pair(r1, rr_img<A>(in, 0), rr_img<Bt>(in, 1), r2, rr_img<Ct>(in, 2), rr_img<Dt>(in, 3));
+        rr_put(out, 0, r1);
+        rr_put(out, 1, r2);
+    }
+};
+template <class Q, int VAR, int Fa, int Va, int Fb, int Vb>
+struct RrvSqrPair {
+    using RQ = Q;
+    static constexpr int op = RR_PAIR, var = VAR, param = 1;
+    using A = Frr<Q, Fa, Va>;
+    using Bt = Frr<Q, Fb, Vb>;
+    using In = TL<A, Bt>;
+    using Out = TL<Frr<Q, 1, 2>, Frr<Q, 1, 2>>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        Frr<Q, 1, 2> r1, r2;
+        rr_sqr_pair(r1, rr_img<A>(in, 0), r2, rr_img<Bt>(in, 1));
+        rr_put(out, 0, r1);
+        rr_put(out, 1, r2);
+    }
+};
+template <class Q, int VAR, int N, int Fa, int Va, int Fb, int Vb>
+struct RrvDot {
+    using RQ = Q;
+    static constexpr int op = RR_DOT, var = VAR, param = N;
+    using A = Frr<Q, Fa, Va>;
+    using Bt = Frr<Q, Fb, Vb>;
+    using In = cat_t<typename Rep<N, A>::type, typename Rep<N, Bt>::type>;
+    using Out = TL<Frr<Q, 1, 2>>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        A a[N];
+        Bt b[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            a[i] = rr_img<A>(in, i);
+            b[i] = rr_img<Bt>(in, N + i);
+        }
+        Frr<Q, 1, 2> r;
+        rr_dot<Q>(r, a, b);
+        rr_put(out, 0, r);
+    }
+};
+template <class Q, int VAR, int F, int V, bool U>
+struct RrvShoup {
+    using RQ = Q;
+    static constexpr int op = U ? RR_SHOUP_U : RR_SHOUP, var = VAR, param = 0;
+    using X = Frr<Q, F, V>;
+    using In = TL<X, Frr<Q, 1, 1>>;
+    using Out = TL<Frr<Q, 1, 2>, Frr<Q, 1, 1>, RrRaw<Q>>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        const X x = rr_img<X>(in, 0);
+        RRShoup<Q> t;
+        rr_shoup_quot<Q>(t, rr_img<Frr<Q, 1, 1>>(in, 1));
+        Frr<Q, 1, 2> r;
+        if constexpr (U) {
+            RRShoupU<Q> u;
+            rr_shoup_uniform<Q>(u, t);
+            rr_mul_shoup(r, x, u);
+            rr_put_words<Q::NL>(out, 1, u.w);
+            rr_put_words<Q::NL>(out, 2, u.wq);
+        } else {
+            rr_mul_shoup(r, x, t);
+            rr_put_words<Q::NL>(out, 1, t.w);
+            rr_put_words<Q::NL>(out, 2, t.wq);
+        }
+        rr_put(out, 0, r);
+    }
+};
+template <class Q, int VAR>
+struct RrvShoupQuot {   // VAR 0: from the canonical w; 1: from w Rrr (rr_shoup_from_mont)
+    using RQ = Q;
+    static constexpr int op = RR_SHOUP_QUOT, var = VAR, param = VAR;
+    using W = Frr<Q, 1, VAR == 0 ? 1 : 2>;
+    using In = TL<W>;
+    using Out = TL<Frr<Q, 1, 1>, RrRaw<Q>>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        RRShoup<Q> t;
+        if constexpr (VAR == 0) rr_shoup_quot<Q>(t, rr_img<W>(in, 0));
+        else rr_shoup_from_mont<Q>(t, rr_img<W>(in, 0));
+        rr_put_words<Q::NL>(out, 0, t.w);
+        rr_put_words<Q::NL>(out, 1, t.wq);
+    }
+};
+template <class Q, int VAR, int F, int V>
+struct RrvNorm {
+    using RQ = Q;
+    static constexpr int op = RR_NORM, var = VAR, param = 0;
+    using A = Frr<Q, F, V>;
+    using In = TL<A>;
+    using Out = TL<decltype(rr_norm(std::declval<const A&>()))>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) { rr_put(out, 0, rr_norm(rr_img<A>(in, 0))); }
+};
+template <class Q, int VAR, class A>
+struct RrvReduce2m {
+    using RQ = Q;
+    static constexpr int op = RR_REDUCE2M, var = VAR, param = 0;
+    using In = TL<A>;
+    using Out = TL<decltype(rr_reduce2m(std::declval<const A&>()))>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) { rr_put(out, 0, rr_reduce2m(rr_img<A>(in, 0))); }
+};
+// a - b + 2^J m and its kin, b at Vb = 2^(J-1), a at the largest (Fa, Va) whose result type Frr still admits
+template <class Q, int J, int OP>
+constexpr bool rr_subj_legal() {   // does Frr admit the result's V (Va + 2^J, Va + 2^(J+1), 2^J + 1, 2^J) with Va >= 1?
+    return OP == RR_SUB || OP == RR_SUB_TWICE ? RrLim<Q>::VMAX - (OP == RR_SUB_TWICE ? 2 : 1) * (1 << J) >= 1
+                                              : (1 << J) + (OP == RR_NEG ? 1 : 0) <= RrLim<Q>::VMAX;
+}
+template <class Q, int J, int OP>
+struct RrvSubJ {
+    using RQ = Q;
+    using L = RrLim<Q>;
+    static constexpr int op = OP, var = J, param = J;
+    static constexpr int GROW = OP == RR_SUB_TWICE ? 2 : 1;   // the result is Fa + 2 GROW, Va + GROW 2^J
+    using A = Frr<Q, L::FMAX - 2 * GROW, L::VMAX - GROW * (1 << J)>;
+    using Bt = Frr<Q, 1, 1 << (J - 1)>;
+    static BLZ_DEV auto apply(const uint32_t* in) {
+        if constexpr (OP == RR_SUB) return rr_sub<J>(rr_img<A>(in, 0), rr_img<Bt>(in, 1));
+        else if constexpr (OP == RR_SUB_TWICE) return rr_sub_twice<J>(rr_img<A>(in, 0), rr_img<Bt>(in, 1));
+        else if constexpr (OP == RR_NEG) return rr_neg<J>(rr_img<Bt>(in, 0));
+        else return rr_cneg<J>(rr_img<Bt>(in, 0), in[Q::NL] != 0u);
+    }
+    using In = std::conditional_t<OP == RR_NEG, TL<Bt>, std::conditional_t<OP == RR_CNEG, TL<Bt, RrFlags>, TL<A, Bt>>>;
+    using Out = TL<decltype(apply(nullptr))>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) { rr_put(out, 0, apply(in)); }
+};
+template <class Q, int OP, int... Js>
+auto rr_sub_list(std::integer_sequence<int, Js...>) -> cat_t<only_if<rr_subj_legal<Q, Js + 1, OP>(), RrvSubJ<Q, Js + 1, OP>>...>;
+template <class Q, int OP>
+using rr_sub_list_t = decltype(rr_sub_list<Q, OP>(std::make_integer_sequence<int, Q::NKM>{}));
+
+template <class Q, int VAR, class Tu, class Tv>
+struct RrvBfly {
+    using RQ = Q;
+    using R = decltype(rr_bfly(std::declval<const Tu&>(), std::declval<const Tv&>()));
+    static constexpr int op = RR_BFLY, var = VAR;
+    static constexpr int param = rr_bounds<Tv>::f < 2 ? 0 : rr_bfly_lazy_fits<Q, rr_bounds<Tu>::f, rr_bounds<Tv>::f>() ? 2 : 1;
+    using In = TL<Tu, Tv>;
+    using Out = TL<decltype(R::s), decltype(R::d)>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        const auto r = rr_bfly(rr_img<Tu>(in, 0), rr_img<Tv>(in, 1));
+        rr_put(out, 0, r.s);
+        rr_put(out, 1, r.d);
+    }
+};
+// the operand types of dft8_rr's twelve butterflies, from its own first stage on
+template <class Q, int VIN>
+struct RrDftTypes {
+    using A = Frr<Q, 1, VIN>;
+    using P = decltype(rr_bfly(std::declval<const A&>(), std::declval<const A&>()));
+    using Ps = decltype(P::s);
+    using Pd = decltype(P::d);
+    using M = Frr<Q, 1, 2>;                                                                       // a twiddled value
+    using Q02 = decltype(rr_bfly(std::declval<const Ps&>(), std::declval<const Ps&>()));
+    using Q13 = decltype(rr_bfly(std::declval<const Pd&>(), std::declval<const M&>()));
+    using Q02s = decltype(Q02::s);
+    using Q02d = decltype(Q02::d);
+    using Q13s = decltype(Q13::s);
+    using Q13d = decltype(Q13::d);
+};
+template <class Q, int VAR>
+struct RrvCanon {
+    using RQ = Q;
+    static constexpr int op = RR_CANON, var = VAR, param = 0;
+    using A = Frr<Q, 1, 2>;
+    using In = TL<A>;
+    using Out = TL<decltype(rr_canon(std::declval<const A&>()))>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) { rr_put(out, 0, rr_canon(rr_img<A>(in, 0))); }
+};
+template <class Q, int VAR, int Fa, int Va, int Fb, int Vb>
+struct RrvZero {
+    using RQ = Q;
+    static constexpr int op = RR_ZERO, var = VAR, param = 0;
+    using A = Frr<Q, Fa, Va>;
+    using Bt = Frr<Q, Fb, Vb>;
+    using In = TL<A, Bt>;
+    using Out = TL<RrFlags>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        const A a = rr_img<A>(in, 0);
+        const Bt b = rr_img<Bt>(in, 1);
+        const uint32_t f[4] = {rr_is_zero(a) ? 1u : 0u, rr_all_zero(a) ? 1u : 0u, rr_maybe_equal(a, b) ? 1u : 0u, rr_is_zero(b) ? 1u : 0u};
+        rr_put_words<Q::NL>(out, 0, f);
+    }
+};
+template <class Q, int VAR>
+struct RrvWords {   // 0: words in; 1: words out; 2: 32-bit Montgomery words in
+    using RQ = Q;
+    static constexpr int op = RR_WORDS, var = VAR, param = VAR == 2 ? 3 : 0;   // (rr_from_mont32_words reads its words as < 3m)
+    static constexpr int VRAW = 1 << (32 * Q::N32 - Q::BITS + 1);
+    using In = std::conditional_t<VAR == 1, TL<Frr<Q, 1, 2>>, TL<RrWords<Q>>>;
+    using Out = std::conditional_t<VAR == 0, TL<Frr<Q, 1, VRAW>, Frr<Q, 1, 2>>, std::conditional_t<VAR == 1, TL<RrWords<Q>, RrWords<Q>>, TL<Frr<Q, 1, 2>>>>;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        if constexpr (VAR == 1) {
+            const auto a = rr_img<Frr<Q, 1, 2>>(in, 0);
+            uint32_t w[Q::N32], w32[Q::N32];
+            rr_to_words<Q>(w, a);
+            rr_to_mont32_words<Q>(w32, a);
+            rr_put_words<Q::NL>(out, 0, w);
+            rr_put_words<Q::NL>(out, 1, w32);
+        } else {
+            uint32_t w[Q::N32];
+#pragma unroll
+            for (int i = 0; i < Q::N32; ++i) w[i] = in[i];
+            Frr<Q, 1, 2> r;
+            if constexpr (VAR == 0) {
+                Frr<Q, 1, VRAW> x;
+                rr_from_words<Q>(x, w);
+                rr_to_mont_from_words<Q>(r, w);
+                rr_put(out, 0, x);
+                rr_put(out, 1, r);
+            } else {
+                rr_from_mont32_words<Q>(r, w);
+                rr_put(out, 0, r);
+            }
+        }
+    }
+};
+template <class Q, int VAR, int VIN, bool U>
+struct RrvDft8 {
+    using RQ = Q;
+    static constexpr int op = RR_DFT8, var = VAR, param = U ? 0 : 1;
+    using A = Frr<Q, 1, VIN>;
+    using W = std::conditional_t<U, RRShoupU<Q>, RRShoup<Q>>;
+    using O = decltype(dft8_rr<Q>(std::declval<const A (&)[8]>(), std::declval<const W&>(), std::declval<const W&>(), std::declval<const W&>()));
+    using In = cat_t<typename Rep<8, A>::type, typename Rep<3, Frr<Q, 1, 1>>::type>;
+    using Out = typename OctTypes<O>::type;
+    static BLZ_DEV void run(const uint32_t* in, uint32_t* out) {
+        A a[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] = rr_img<A>(in, j);
+        RRShoup<Q> t[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) rr_shoup_quot<Q>(t[j], rr_img<Frr<Q, 1, 1>>(in, 8 + j));
+        if constexpr (U) {
+            RRShoupU<Q> u[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) rr_shoup_uniform<Q>(u[j], t[j]);
+            auto o = dft8_rr<Q>(a, u[0], u[1], u[2]);
+            BLZ_RR_FOR8(o, { rr_put(out, K, X); })
+        } else {
+            auto o = dft8_rr<Q>(a, t[0], t[1], t[2]);
+            BLZ_RR_FOR8(o, { rr_put(out, K, X); })
+        }
+    }
+};
+
+// the variants of a field.  0 ..: the widest bounds; 100 ..: bounds the product uses (ec_rr.hip.hpp's mixed addition in its tight
+// and loose budgets, ec_quad.hip.hpp rrq_diff, the butterflies and reductions of dft8_rr, Poseidon's row products)
+template <class Q>
+struct RrList {
+    using L = RrLim<Q>;
+    static constexpr bool SH = Q::NL == 9, TIGHT = RR_TIGHT<Q>;   // SH: the constant-operand columns exist (Shoup products)
+    static constexpr int VX = XYZZRR<Q>::VX;
+    static constexpr bool DFT = SH && !std::is_same_v<Q, Fq_BN254::RR>;   // the scalar fields: BN254's base field (q = 3 mod 4) has no w8
+    using D2 = RrDftTypes<Q, 2>;
+    using D1 = RrDftTypes<Q, L::VIN1>;
+    using Mul = TL<RrvMul<Q, 0, L::F1, L::VMAX, 1, 1>, RrvMul<Q, 1, 1, 1, L::F1, L::VMAX>, RrvMul<Q, 2, L::FBA, L::VBA, L::FBB, L::VBB>,
+                   RrvMul<Q, 100, 1, VX, 1, 2>>;
+    using Sqr = TL<RrvSqr<Q, 0, L::FSQ, L::VBA>, std::conditional_t<TIGHT, RrvSqr<Q, 100, 1, 6>, RrvSqr<Q, 100, 3, 10>>>;
+    using Mul2 = TL<RrvMul2<Q, 0, L::FM2A, L::VMAX / 2, 1, 1, L::FS - L::FM2A, 1, 1, L::VMAX / 2>,
+                    RrvMul2<Q, 1, L::FM2, L::VHA, L::FM2, L::VHB, 1, L::VHB, L::FS - L::FM2 * L::FM2, L::VHA>,
+                    std::conditional_t<TIGHT, RrvMul2<Q, 100, 3, 6, 1, 6, 2, 4, 1, 2>, RrvMul2<Q, 100, 3, 10, 3, 34, 2, 8, 1, 2>>>;
+    using Pair = TL<RrvMulPair<Q, 0, L::F1, L::VMAX, 1, 1, L::FBA, L::VBA, L::FBB, L::VBB>, RrvSqrPair<Q, 1, L::FSQ, L::VBA, 1, 1>,
+                    RrvMulPair<Q, 100, 1, 2, 1, 2, 2, 4, 1, 2>,
+                    std::conditional_t<TIGHT, RrvSqrPair<Q, 101, 1, 6, 1, 6>, RrvSqrPair<Q, 101, 3, 34, 3, 10>>>;
+    template <int... Ns>
+    static auto dots(std::integer_sequence<int, Ns...>) -> TL<RrvDot<Q, Ns + 1, Ns + 1, 1, L::VMAX / (Ns + 1), 1, 1>...>;
+    // every N the column bound admits (6 at 9 x 29 bits, 17 at 14 x 28); 100 / 101: poseidon_impl's Elem at t > 12, poseidon_hades'
+    using Dot = cat_t<decltype(dots(std::make_integer_sequence<int, L::FS>{})),
+                      only_if<SH, RrvDot<Q, 100, POS_DOT, 1, 7, 1, 1>>, only_if<SH, RrvDot<Q, 101, POS_DOT, 1, 3, 1, 1>>>;
+    using Shoup = std::conditional_t<SH,
+        TL<RrvShoup<Q, 0, 1, L::VMAX, false>, RrvShoup<Q, 1, L::F1, L::VMAX, false>, RrvShoup<Q, 100, 3, 6, false>, RrvShoup<Q, 101, 1, L::VIN1, false>,
+           RrvShoup<Q, 0, 1, L::VMAX, true>, RrvShoup<Q, 1, L::F1, L::VMAX, true>, RrvShoup<Q, 100, 3, 6, true>, RrvShoup<Q, 101, 1, L::VIN1, true>,
+           RrvShoupQuot<Q, 0>, RrvShoupQuot<Q, 1>>,
+        TL<>>;
+    using Lin = cat_t<TL<RrvNorm<Q, 0, L::FMAX, L::VMAX>, RrvNorm<Q, 100, 2, 4>, RrvReduce2m<Q, 0, Frr<Q, L::FMAX, L::VR2M>>,
+                         RrvReduce2m<Q, 100, Frr<Q, 3, 6>>>,
+                      only_if<SH, RrvReduce2m<Q, 101, typename D2::Q02s>>, only_if<SH, RrvReduce2m<Q, 102, typename D1::Q02s>>,
+                      rr_sub_list_t<Q, RR_SUB>, rr_sub_list_t<Q, RR_SUB_TWICE>, rr_sub_list_t<Q, RR_NEG>, rr_sub_list_t<Q, RR_CNEG>>;
+    using Bfly = cat_t<TL<RrvBfly<Q, 0, typename D2::A, typename D2::A>, RrvBfly<Q, 1, typename D2::Pd, typename D2::M>,
+                          RrvBfly<Q, 2, typename D2::Ps, typename D2::Ps>, RrvBfly<Q, 3, typename D2::Q02s, typename D2::Q02s>,
+                          RrvBfly<Q, 4, typename D2::Q13s, typename D2::M>, RrvBfly<Q, 5, typename D2::Q02d, typename D2::M>,
+                          RrvBfly<Q, 6, Frr<Q, 1, 2>, Frr<Q, 2, 4>>>,
+                       only_if<SH, RrvBfly<Q, 10, typename D1::A, typename D1::A>>, only_if<SH, RrvBfly<Q, 11, typename D1::Pd, typename D1::M>>,
+                       only_if<SH, RrvBfly<Q, 12, typename D1::Ps, typename D1::Ps>>, only_if<SH, RrvBfly<Q, 13, typename D1::Q02s, typename D1::Q02s>>>;
+    using Rest = cat_t<TL<RrvCanon<Q, 0>, RrvZero<Q, 0, L::F1, L::VMAX, L::F1, L::VMAX>, RrvZero<Q, 100, 3, 6, 1, 2>, RrvWords<Q, 0>, RrvWords<Q, 1>,
+                          RrvWords<Q, 2>>,
+                       only_if<DFT, RrvDft8<Q, 0, 2, true>>, only_if<DFT, RrvDft8<Q, 1, L::VIN1, true>>, only_if<DFT, RrvDft8<Q, 2, 2, false>>>;
+    using type = cat_t<Mul, Sqr, Mul2, Pair, Dot, Shoup, Lin, Bfly, Rest>;
+};
+
+struct RrOp {
+    int op, var;
+    const uint32_t* in;
+    uint32_t* out;
+    size_t n;
+};
+// one lane per case.  Every lane of the last wave runs (the SGPR-uniform forms read the wave's first lane): a surplus lane repeats
+// case n - 1 and writes into the padding of `out`, which holds a whole number of waves.
+template <class Vt>
+__global__ __launch_bounds__(64) void k_test_rr(const uint32_t* in, uint32_t* out, uint32_t n) {
+    constexpr uint32_t NL = Vt::RQ::NL;
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    const uint32_t e = i < n ? i : n - 1u;
+    Vt::run(in + (size_t)e * Vt::In::n * NL, out + (size_t)i * Vt::Out::n * NL);
+}
+template <class Vt>
+int rr_run(const RrOp& o) {
+    constexpr size_t NL = Vt::RQ::NL;
+    const size_t waves = (o.n + 63) / 64, in_bytes = o.n * Vt::In::n * NL * 4, out_bytes = o.n * Vt::Out::n * NL * 4;
+    Tmp tmp;
+    void *din, *dout;
+    BLZ_TRY(tmp.alloc(&din, in_bytes));
+    BLZ_TRY(tmp.alloc(&dout, waves * 64 * Vt::Out::n * NL * 4));
+    BLZ_HIP(hipMemcpy(din, o.in, in_bytes, hipMemcpyHostToDevice), BLZ_ERR_WRITE);
+    BLZ_HIP(hipMemset(dout, 0, waves * 64 * Vt::Out::n * NL * 4), BLZ_ERR_UNKNOWN);
+    hipLaunchKernelGGL(k_test_rr<Vt>, dim3((unsigned)waves), dim3(64), 0, 0, (const uint32_t*)din, (uint32_t*)dout, (uint32_t)o.n);
+    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
+    BLZ_TRY(sync_stream_bounded(nullptr, "reduced-radix primitive test kernel"));
+    BLZ_HIP(hipMemcpy(o.out, dout, out_bytes, hipMemcpyDeviceToHost), BLZ_ERR_READ);
+    return BLZ_OK;
+}
+template <class... T>
+void rr_emit_bounds(std::vector<uint32_t>& w, TL<T...>) {
+    ((w.push_back((uint32_t)rr_bounds<T>::f), w.push_back((uint32_t)rr_bounds<T>::v)), ...);
+}
+template <class Vt>
+void rr_emit(std::vector<uint32_t>& w) {
+    const uint32_t head[5] = {(uint32_t)Vt::op, (uint32_t)Vt::var, (uint32_t)Vt::In::n, (uint32_t)Vt::Out::n, (uint32_t)Vt::param};
+    w.insert(w.end(), head, head + 5);
+    rr_emit_bounds(w, typename Vt::In{});
+    rr_emit_bounds(w, typename Vt::Out{});
+}
+// lay: the records of every variant; o: run the one variant (op, var)
+template <class... Vs>
+int rr_each(TL<Vs...>, std::vector<uint32_t>* lay, const RrOp* o) {
+    int rc = -1;
+    ([&] {
+        if (lay) rr_emit<Vs>(*lay);
+        if (o && Vs::op == o->op && Vs::var == o->var) rc = rr_run<Vs>(*o);
+    }(), ...);
+    if (!o) return BLZ_OK;
+    return rc == -1 ? fail(BLZ_ERR_INVALID_PARAM, "the field has no variant %d of reduced-radix op %d", o->var, o->op) : rc;
+}
+template <class Q>
+int test_rr_field(uint32_t* layout, const RrOp* o) {
+    using L = RrLim<Q>;
+    std::vector<uint32_t> rec;
+    BLZ_TRY(rr_each(typename RrList<Q>::type{}, layout ? &rec : nullptr, o));
+    if (layout) {
+        constexpr size_t R0 = 16 + Q::NL;
+        if (R0 + rec.size() > BLZ_RR_LAYOUT_WORDS) return fail(BLZ_ERR_UNKNOWN, "the layout needs %zu words", R0 + rec.size());
+        memset(layout, 0, BLZ_RR_LAYOUT_WORDS * sizeof(uint32_t));
+        const uint32_t head[11] = {(uint32_t)Q::B, (uint32_t)Q::NL, (uint32_t)L::H, (uint32_t)Q::NKM, (uint32_t)L::FS, (uint32_t)(Q::B * Q::NL),
+                                   (uint32_t)Q::N32, (uint32_t)POS_DOT, Q::T2M, (uint32_t)RrList<Q>::type::n, (uint32_t)(R0 + rec.size())};
+        memcpy(layout, head, sizeof(head));
+        for (int i = 0; i < Q::NL; ++i) layout[16 + i] = Q::MOD[i];
+        memcpy(layout + R0, rec.data(), rec.size() * sizeof(uint32_t));
+    }
+    return BLZ_OK;
+}
+static int test_rr_dispatch(int curve, int field, uint32_t* layout, const RrOp* o) {
+    if (field == 0 || field == 1) {
+        switch (curve) {
+            case BLZ_BLS377: return field ? test_rr_field<Fr_BLS377::RR>(layout, o) : test_rr_field<Fq_BLS377::RR>(layout, o);
+            case BLZ_BLS381: return field ? test_rr_field<Fr_BLS381::RR>(layout, o) : test_rr_field<Fq_BLS381::RR>(layout, o);
+            case BLZ_BN254: return field ? test_rr_field<Fr_BN254::RR>(layout, o) : test_rr_field<Fq_BN254::RR>(layout, o);
+        }
+    }
+    return fail(BLZ_ERR_INVALID_PARAM, "no reduced-radix field %d of curve %d", field, curve);
+}
+
 }  // namespace blz
 
 using namespace blz;
@@ -879,6 +1377,19 @@ int blz_test_law_op(int device_id, int curve, int repr, int law, int program, in
     BLZ_TRY(use_device(device_id));
     const LawOp op = {program, exit, k, arg, in, out, n};
     return test_law_dispatch(curve, repr, law, nullptr, &op);
+}
+
+int blz_test_rr_layout(int curve, int field, uint32_t* out) {
+    if (!out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    return test_rr_dispatch(curve, field, out, nullptr);
+}
+
+int blz_test_rr_op(int device_id, int curve, int field, int op, int variant, const uint32_t* in, uint32_t* out, size_t n) {
+    if (!in || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    if (n == 0 || n > (1u << 20)) return fail(BLZ_ERR_INVALID_PARAM, "%zu cases (1 .. 2^20)", n);
+    BLZ_TRY(use_device(device_id));
+    const RrOp o = {op, variant, in, out, n};
+    return test_rr_dispatch(curve, field, nullptr, &o);
 }
 
 int blz_test_sort_fits_beside(int acc_vgprs, int sort_vgprs, int acc_lds, int sort_lds) {

@@ -82,6 +82,47 @@ int blz_test_law_layout(int curve, int repr, int law, uint32_t out[32]);
 int blz_test_law_op(int device_id, int curve, int repr, int law, int program, int exit, uint32_t k, uint32_t arg, const uint32_t* in,
                     uint32_t* out, size_t n);
 
+/* The reduced-radix primitives (field_rr.hip.hpp; rr_bfly / rr_canon / dft8_rr of ntt_rr.hip.hpp, rr_dot of poseidon_impl.hip.hpp), one
+ * by one on RAW limb images with operands at the top of what their TYPES admit: Frr<Q, F, V> is "every limb < F 2^B, integer < V m".
+ * field: 0 Fq, 1 Fr of `curve`; all six fields have a reduced-radix twin (BLS12-377 / 381 Fq at 14 x 28 bits, the others 9 x 29).
+ * An image is NL dwords, limb i at dword i, the integer sum limb_i 2^(B i) whatever the limbs' size; no conversion on the way.
+ * blz_test_rr_layout (host only): out[BLZ_RR_LAYOUT_WORDS] =
+ *   [0] B, [1] NL, [2] HEAD (Rrr / 2^BITS = 2^HEAD: value factors V reach 2^HEAD), [3] NKM, [4] the largest fsum rr_cols_ok admits,
+ *   [5] the Montgomery exponent B NL, [6] N32 (32-bit words of the wire form), [7] POS_DOT, [8] T2M, [9] the number of records,
+ *   [10] the words used, [16 ..) the NL limbs of m, then the records, one per (op, variant) the hook instantiates:
+ *     op, variant, k_in, k_out, param, then k_in + k_out pairs (F, V) read off the operand and result types with rr_bounds.
+ *     F = 0 is no limb image: V = 0 a flag image (dword j = flag j), V = 1 N32 raw 32-bit words.  F = 1, V = 0: limbs < 2^B, any
+ *     integer below Rrr (a Shoup quotient).
+ *   Every op is instantiated at the widest bounds its own static_asserts admit for the field (variants 0 ..) and at bounds the product
+ *   uses where they differ (variants 100 ..: ec_rr.hip.hpp, ntt_rr.hip.hpp, poseidon_impl / poseidon_hades).
+ * blz_test_rr_op: n cases (host pointers) of k_in images each, one lane per case, k_out images per case out, limb for limb as the
+ *   primitive left them.  An (op, variant) the field has no record of is BLZ_ERR_INVALID_PARAM.  Ops (in -> out; param):
+ *    0 MUL        a, b -> rr_mul, rr_mul_ref
+ *    1 SQR        a -> rr_sqr
+ *    2 MUL2       a, b, c, d -> rr_mul2 (a b + c d)
+ *    3 PAIR       variant 0 / 100: a1, b1, a2, b2 -> rr_mul_pair; variant 1 / 101: a1, a2 -> rr_sqr_pair (param 1)
+ *    4 DOT        a_0 .. a_N-1, b_0 .. b_N-1 -> rr_dot; param N
+ *    5 SHOUP      x, w (canonical, plain) -> rr_mul_shoup(x, entry), entry.w, entry.wq; the entry made by rr_shoup_quot.  9 limbs only
+ *    6 SHOUP_U    the same through the SGPR-uniform entry: every lane of a wave (64 consecutive cases) multiplies by the w of the
+ *                 wave's FIRST case, and returns that entry
+ *    7 SHOUP_QUOT variant 0: w -> rr_shoup_quot's w, wq; variant 1 (param 1): w Rrr (< 2m) -> rr_shoup_from_mont's w, wq
+ *    8 NORM       a -> rr_norm
+ *    9 REDUCE2M   a -> rr_reduce2m
+ *   10 SUB        a, b -> rr_sub<J>;   11 SUB_TWICE a, b -> rr_sub_twice<J>;   12 NEG b -> rr_neg<J>;
+ *   13 CNEG       b, flag image (dword 0: sign) -> rr_cneg<J> (a literal zero stays zero).  variant = param = J, 1 .. NKM where the
+ *                 result type exists (rr_neg's is Frr<Q, 2, 2^J + 1>: 2^J m - 0 is 2^J m)
+ *   14 BFLY       u, v -> rr_bfly's sum, difference; param 0 normalised v, 1 lazy v carry-propagated first, 2 lazy v against (Fv + 1)
+ *                 times the borrow form.  The difference is u - v + (V_d - V_u) m.
+ *   15 CANON      a -> rr_canon
+ *   16 ZERO       a, b -> flag image: rr_is_zero(a), rr_all_zero(a), rr_maybe_equal(a, b), rr_is_zero(b)
+ *   17 WORDS      variant 0: words -> rr_from_words, rr_to_mont_from_words; 1: a -> rr_to_words, rr_to_mont32_words;
+ *                 2: words (an integer < param m) -> rr_from_mont32_words
+ *   18 DFT8       a_0 .. a_7 (x0, x4, x2, x6, x1, x5, x3, x7), w8, w8^2, w8^3 (canonical, plain) -> dft8_rr's eight outputs; param
+ *                 0: RRShoupU entries (the first case's of the wave), 1: RRShoup.  The three scalar fields only */
+#define BLZ_RR_LAYOUT_WORDS 8192
+int blz_test_rr_layout(int curve, int field, uint32_t* out);
+int blz_test_rr_op(int device_id, int curve, int field, int op, int variant, const uint32_t* in, uint32_t* out, size_t n);
+
 /* MsmEngine::begin()'s test for hiding a task's digit sort under another task's accumulation: 1 when a block of the sort (sort_vgprs
  * registers per lane, sort_lds bytes of LDS) fits on a CU beside the accumulation's blocks of 128 lanes (acc_vgprs, acc_lds), else 0.
  * Host only.  A count <= 0 is "not known" and is taken to fit. */
