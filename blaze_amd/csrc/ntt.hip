@@ -936,8 +936,9 @@ int blz_ntt_vec_mle_round(blz_ntt* h, uint32_t flags, const blz_vec_arg* a, cons
     NttVecArg va{}, vb{}, vc{};
     BLZ_TRY(call.resolve({{"a", a, &va}, {"b", b, &vb}, {"c", c, &vc}}, "d_out", d_out, points));
     const int k = c ? 3 : b ? 2 : 1;
+    const NttVecArg vt[3] = {va, vb, vc};
     return call.enqueue(-1, [&](uint32_t*) {
-        return h->ops->vec_mle_round(h->stream, flags, (uint32_t*)d_out, k, va, b ? vb : va, c ? vc : va, points, len, call.ws);
+        return h->ops->sumcheck_step(h->stream, BLZ_GATE_PRODUCT, flags, k, vt, nullptr, points, len, (uint32_t*)d_out, call.ws);
     });
 }
 
@@ -1007,7 +1008,7 @@ int blz_ntt_sumcheck_step(blz_ntt* h, uint32_t gate, const blz_vec_arg* a, const
             if (!tv[j]->d_ptr) wbuf[wbuf[0] < 0 ? 0 : 1] = (int)tv[j]->buf;
         }
     }
-    return call.enqueue(wbuf[0], [&](uint32_t*) { return h->ops->sumcheck_step(h->stream, gate, k, vt, r ? vr.p : nullptr, points, len, (uint32_t*)d_out, call.ws); },
+    return call.enqueue(wbuf[0], [&](uint32_t*) { return h->ops->sumcheck_step(h->stream, gate, 0, k, vt, r ? vr.p : nullptr, points, len, (uint32_t*)d_out, call.ws); },
                         wbuf[1]);
 }
 

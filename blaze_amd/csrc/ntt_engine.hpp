@@ -126,24 +126,22 @@ struct NttFieldOps {
     // val == nullptr: coefficients 1.  dst must NOT overlap x's words
     int (*vec_spmv)(hipStream_t st, uint32_t* dst, NttVecArg x, const uint32_t* row_ptr, const uint32_t* col, const uint32_t* val,
                     uint64_t rows, uint64_t nnz, uint64_t n, uint32_t* ws);
-    // Multilinear tables (blz_ntt_vec_mle_fold / _round / _eq; kernels and the workspace's layout: ntt_mle.hip.hpp).  len = 2^m,
-    // 2 <= len, is the live length; flags: BLZ_MLE_LOW.  None of them writes past the words named here.
+    // Multilinear tables (blz_ntt_vec_mle_fold / _eq; kernels and the workspace's layout: ntt_mle.hip.hpp).  len = 2^m, 2 <= len,
+    // is the live length; flags: BLZ_MLE_LOW.  None of them writes past the words named here.  blz_ntt_vec_mle_round has no entry
+    // of its own: it is sumcheck_step below with BLZ_GATE_PRODUCT, no r and its flags.
     // dst[p] = lo + r (hi - lo), p < len / 2; r: one device word.  dst may be a.p without BLZ_MLE_LOW, and must not overlap a's
     // words otherwise
     int (*vec_mle_fold)(hipStream_t st, uint32_t flags, uint32_t* dst, NttVecArg a, const uint32_t* r, uint64_t len);
-    // out[t] = sum_p prod_{j < k} (lo_j + t (hi_j - lo_j)), t < points (1 .. 4): `points` words; k = 1 .. 3 operands a, b, c (the
-    // ones not taken: a again)
-    int (*vec_mle_round)(hipStream_t st, uint32_t flags, uint32_t* out, int k, NttVecArg a, NttVecArg b, NttVecArg c, uint32_t points,
-                         uint64_t len, uint32_t* ws);
     // dst[p] = eq(point, p), p < 2^m; point: m device words (not read when m == 0)
     int (*vec_mle_eq)(hipStream_t st, uint32_t* dst, const uint32_t* point, uint32_t m, uint32_t* ws);
     // A sumcheck step (blz_ntt_sumcheck_step; kernels and the workspace's layout: ntt_sumcheck.hip.hpp) over the gate's k tables
     // t[0 .. k) (BLZ_GATE_PRODUCT: 1 .. 3, BLZ_GATE_R1CS: 4), top-variable pairing.  r (one device word) != nullptr: every table
     // is folded in place - it holds at least len words, no two overlap, len / 2 words of each are written - and out[t], t < points,
     // is the round polynomial of the folded tables (len >= 4); points == 0: the folds alone (len >= 2), out is not looked at.
-    // r == nullptr: the round polynomial of the tables as they are (periodic ones allowed), nothing else is written
-    int (*sumcheck_step)(hipStream_t st, uint32_t gate, int k, const NttVecArg* t, const uint32_t* r, uint32_t points, uint64_t len,
-                         uint32_t* out, uint32_t* ws);
+    // r == nullptr: the round polynomial of the tables as they are (periodic ones allowed), nothing else is written; flags:
+    // BLZ_MLE_LOW pairs (2p, 2p + 1), for BLZ_GATE_PRODUCT without r alone
+    int (*sumcheck_step)(hipStream_t st, uint32_t gate, uint32_t flags, int k, const NttVecArg* t, const uint32_t* r, uint32_t points,
+                         uint64_t len, uint32_t* out, uint32_t* ws);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

@@ -525,7 +525,6 @@ NttFieldOps make_ntt_ops() {
     o.vec_gather = &ntt_vec_gather_t<Fr>;
     o.vec_spmv = &ntt_vec_spmv_t<Fr>;
     o.vec_mle_fold = &ntt_vec_mle_fold_t<Fr>;
-    o.vec_mle_round = &ntt_vec_mle_round_t<Fr>;
     o.vec_mle_eq = &ntt_vec_mle_eq_t<Fr>;
     o.sumcheck_step = &ntt_sumcheck_step_t<Fr>;
     return o;

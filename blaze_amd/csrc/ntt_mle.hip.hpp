@@ -11,17 +11,8 @@
 //   Without LOW dst may be a's words: a lane reads p and p + len / 2 before it writes p, and no other lane touches either.
 //   With LOW lane p writes a word lane p / 2 reads: in place goes through the handle's scratch and a copy (ntt.hip).
 //
-// ROUND  out[t] = sum_{p < len / 2} prod_{j < K} (lo_j + t (hi_j - lo_j)), t < points <= 4, K <= 3 operands.
-//   k_mle_round_part: the grid of k_fold_part - lane g of S = blocks x 256 owns the pairs g, g + S, ... - with `points`
-//   accumulators per lane.  Per pair: 2 K loads through vec_canon, value and difference per operand; per point K - 1 raw
-//   Montgomery products (the value of operand 0 times the others') and one addition into the point's accumulator, then t advances
-//   by ONE addition per operand.  The loop over t is unrolled to 4 and predicated on `points`, which is wave-uniform.
-//   Products per pair: points x (K - 1) - none at K = 1, 3 at K = 2 with 3 points, 8 at K = 3 with 4.
-//   Each raw product leaves a factor 1 / R: every term of a sum carries the same R^-(K-1), which comes off ONCE, where the
-//   final word is made (K - 1 products by R^2: DOT's rule).  One fold_block_tree per point; a call whose pairs fit one block
-//   (len <= 512) finishes there and writes d_out itself - no workspace, which small handles do not have: 4 words need n >= 4 -,
-//   any other writes one partial per block and point and k_mle_round_fin, one block, folds them.
-//   Workspace: blocks x points words with blocks = len / 512 >= 2, so at most 4 len / 512 < len <= n words.
+// ROUND  out[t] = sum_{p < len / 2} prod_{j < K} (lo_j + t (hi_j - lo_j)): the PRODUCT gate of ntt_sumcheck.hip.hpp without r, the
+//   one kernel that takes every round polynomial; mle_pair below is the pairing both share.
 //
 // EQ     dst[p] = prod_{i < m} (x_i tau_i + (1 - x_i)(1 - tau_i)), p < 2^m.
 //   By doubling: the table of s variables becomes that of s + 1 by new[q + 2^s] = old[q] tau_s, new[q] = old[q] - new[q + 2^s]:
@@ -73,90 +64,6 @@ __global__ __launch_bounds__(VEC_THREADS) void k_mle_fold(uint32_t* dst, NttVecA
         fp_add(d, lo, d);
         fp_reduce(d);
         fp_store(dst + p * 8, d);
-    }
-}
-
-// x R^-(K-1) -> x, canonical: K - 1 products by R^2
-template <class Fr>
-BLZ_DEV void mle_round_close(Fp<Fr>& x, int k) {
-#pragma unroll 1
-    for (int j = 1; j < k; ++j) fp_to_mont(x, x);
-    fp_reduce(x);
-}
-
-// direct != 0 (one block): out = d_out, `points` canonical words; else out = the workspace, word t * gridDim.x + block = the
-// block's partial of point t, with the stray R^-(K-1)
-template <class Fr, int K, bool LOW>
-__global__ __launch_bounds__(VEC_THREADS) void k_mle_round_part(uint32_t* out, NttVecArg a, NttVecArg b, NttVecArg c, uint64_t half,
-                                                                 int log_stride, uint32_t points, uint32_t direct) {
-    using E = Fp<Fr>;
-    __shared__ __attribute__((aligned(16))) uint32_t x[VEC_THREADS * 8];
-    const uint64_t stride = 1ull << log_stride;   // gridDim.x * VEC_THREADS, a power of two
-    E acc[MLE_MAX_POINTS];
-#pragma unroll
-    for (int t = 0; t < MLE_MAX_POINTS; ++t) fp_zero(acc[t]);
-#pragma unroll 1
-    for (uint64_t p = (uint64_t)blockIdx.x * VEC_THREADS + threadIdx.x; p < half; p += stride) {
-        E v[K], d[K];
-        mle_pair<Fr, LOW>(v[0], d[0], a, p, half);
-        if constexpr (K > 1) mle_pair<Fr, LOW>(v[1], d[1], b, p, half);
-        if constexpr (K > 2) mle_pair<Fr, LOW>(v[2], d[2], c, p, half);
-#pragma unroll
-        for (int t = 0; t < MLE_MAX_POINTS; ++t) {
-            if (t < (int)points) {
-                E pr = v[0];
-#pragma unroll
-                for (int j = 1; j < K; ++j) fp_mul(pr, pr, v[j]);
-                fp_add(acc[t], acc[t], pr);
-                if (t + 1 < MLE_MAX_POINTS) {
-#pragma unroll
-                    for (int j = 0; j < K; ++j) fp_add(v[j], v[j], d[j]);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < MLE_MAX_POINTS; ++t) {
-        if (t < (int)points) {
-            fold_block_tree<Fr>(x, acc[t], [](E& l, const E& r, int) { fp_add(l, l, r); });
-            if (direct) {
-                if (threadIdx.x == 0) {
-                    E s;
-                    fp_load(s, x);
-                    mle_round_close(s, K);
-                    fp_store(out + t * 8, s);
-                }
-            } else {
-                vec_copy32(out + ((size_t)t * gridDim.x + blockIdx.x) * 8, x);
-            }
-            __syncthreads();   // x is the next point's
-        }
-    }
-}
-
-// out[t] = the fold of the `count` partials of point t (a power of two, <= VEC_MAX_BLOCKS), closed; one block
-template <class Fr>
-__global__ __launch_bounds__(VEC_THREADS) void k_mle_round_fin(uint32_t* out, const uint32_t* partial, uint32_t count, uint32_t points, int k) {
-    using E = Fp<Fr>;
-    __shared__ __attribute__((aligned(16))) uint32_t x[VEC_THREADS * 8];
-#pragma unroll 1
-    for (uint32_t t = 0; t < points; ++t) {
-        E acc;
-        fp_zero(acc);
-#pragma unroll 1
-        for (uint32_t e = threadIdx.x; e < count; e += VEC_THREADS) {
-            E v;
-            fp_load(v, partial + ((size_t)t * count + e) * 8);
-            fp_add(acc, acc, v);
-        }
-        fold_block_tree<Fr>(x, acc, [](E& l, const E& r, int) { fp_add(l, l, r); });
-        if (threadIdx.x == 0) {
-            E s;
-            fp_load(s, x);
-            mle_round_close(s, k);
-            fp_store(out + t * 8, s);
-        }
-        __syncthreads();
     }
 }
 
@@ -228,36 +135,6 @@ int ntt_vec_mle_fold_t(hipStream_t st, uint32_t flags, uint32_t* dst, NttVecArg 
     const dim3 grid((unsigned)(blocks < VEC_MAX_BLOCKS ? blocks : VEC_MAX_BLOCKS)), thr(VEC_THREADS);
     if (flags & MLE_LOW) hipLaunchKernelGGL((k_mle_fold<Fr, true>), grid, thr, 0, st, dst, a, r, half);
     else hipLaunchKernelGGL((k_mle_fold<Fr, false>), grid, thr, 0, st, dst, a, r, half);
-    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
-    return BLZ_OK;
-}
-
-template <class Fr, int K>
-void mle_round_launch(hipStream_t st, bool low, dim3 grid, uint32_t* out, NttVecArg a, NttVecArg b, NttVecArg c, uint64_t half, int ls,
-                      uint32_t points, uint32_t direct) {
-    if (low) hipLaunchKernelGGL((k_mle_round_part<Fr, K, true>), grid, dim3(VEC_THREADS), 0, st, out, a, b, c, half, ls, points, direct);
-    else hipLaunchKernelGGL((k_mle_round_part<Fr, K, false>), grid, dim3(VEC_THREADS), 0, st, out, a, b, c, half, ls, points, direct);
-}
-
-// k operands (the ones not taken: any valid NttVecArg), 1 <= points <= 4; out: `points` words; ws: the handle's scratch
-template <class Fr>
-int ntt_vec_mle_round_t(hipStream_t st, uint32_t flags, uint32_t* out, int k, NttVecArg a, NttVecArg b, NttVecArg c, uint32_t points,
-                        uint64_t len, uint32_t* ws) {
-    const uint64_t half = len >> 1;
-    uint64_t blocks = (half + VEC_THREADS - 1) / VEC_THREADS;   // a power of two: half is
-    if (blocks > VEC_MAX_BLOCKS) blocks = VEC_MAX_BLOCKS;
-    const int ls = fold_log2(blocks) + FOLD_LOG_THREADS;
-    const bool low = (flags & MLE_LOW) != 0;
-    const uint32_t direct = blocks == 1 ? 1u : 0u;
-    uint32_t* const part = direct ? out : ws;
-    const dim3 grid((unsigned)blocks);
-    switch (k) {
-        case 1: mle_round_launch<Fr, 1>(st, low, grid, part, a, b, c, half, ls, points, direct); break;
-        case 2: mle_round_launch<Fr, 2>(st, low, grid, part, a, b, c, half, ls, points, direct); break;
-        case 3: mle_round_launch<Fr, 3>(st, low, grid, part, a, b, c, half, ls, points, direct); break;
-        default: return fail(BLZ_ERR_INVALID_PARAM, "a round polynomial takes 1 to %d operands", MLE_MAX_OPERANDS);
-    }
-    if (!direct) hipLaunchKernelGGL(k_mle_round_fin<Fr>, dim3(1), dim3(VEC_THREADS), 0, st, out, (const uint32_t*)ws, (uint32_t)blocks, points, k);
     BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     return BLZ_OK;
 }

@@ -1,9 +1,9 @@
 """Multilinear tables on resident buffers (blz_ntt_vec_mle_fold / _round / _eq), the part that needs no device: the three entry
 points and BLZ_MLE_LOW exist in every layer with the documented signatures and in the header's order, a null handle is refused
 whatever else is passed, the pointer checks still exist once, and the shipped gfx950 code object holds what the kernels
-promise - the same set of k_mle_* kernels for the three scalar fields and nothing else, no scratch, at most 128 VGPRs (168 for
-k_mle_round_part at K = 3), no name another ISA test counts, a Montgomery product in the fold, more multiply-adds in the round at
-K = 3 than at K = 2 and less than one product at K = 1."""
+promise - the same set of k_mle_* kernels for the three scalar fields and nothing else, no scratch, at most 128 VGPRs, no name
+another ISA test counts, a Montgomery product in the fold and in the equality table.  The round's kernels are the sumcheck
+step's (test_ntt_sumcheck_step.py)."""
 import ctypes
 import os
 import re
@@ -87,7 +87,7 @@ def test_entry_points_in_every_layer():
     impl = _read("blaze_amd", "csrc", "ntt_impl.hip.hpp")
     eng = _read("blaze_amd", "csrc", "ntt_engine.hpp")
     assert '#include "ntt_mle.hip.hpp"' in impl
-    for f in ("vec_mle_fold", "vec_mle_round", "vec_mle_eq"):
+    for f in ("vec_mle_fold", "vec_mle_eq"):
         assert f"o.{f} = " in impl and re.search(rf"\(\*{f}\)\s*\(\s*hipStream_t\s+st\s*,", eng), f
     # one pointer check for every op: the new destinations, outputs and the point go through operand / device_range
     ntt = _read("blaze_amd", "csrc", "ntt.hip")
@@ -96,6 +96,9 @@ def test_entry_points_in_every_layer():
     body = ntt[ntt.index("int blz_ntt_vec_mle_fold("):ntt.index("int blz_ntt_stream(")]
     assert body.count("call.destination(") == 2 and body.count("call.resolve(") == 2
     assert re.search(r'device_range\("[^"]*",\s*"d_point"', body)
+    # the round is the sumcheck step's PRODUCT gate without r: its entry point goes through that entry of NttFieldOps
+    body = body[body.index("int blz_ntt_vec_mle_round("):body.index("int blz_ntt_vec_mle_eq(")]
+    assert "h->ops->sumcheck_step(" in body and "o.vec_mle_round" not in impl and "(*vec_mle_round)" not in eng
     # documented where the other ops are
     for doc in ("README.md", "DESIGN.md", "INTEGRATION.md", "HISTORY.md"):
         text = _read(doc)
@@ -120,31 +123,27 @@ def test_mle_kernels_stay_out_of_scratch_and_within_their_vgprs(code):
     names = sorted(n for n in vgprs if re.match(r"_ZN3blz\d+k_mle_", n))
     print({n: (vgprs[n], scratch[n]) for n in names})
     per_field = [[n for n in names if re.match(rf"_ZN3blz\d+k_mle_\w+?INS_{f}E", n)] for f in FIELDS]
-    # fold x 2 pairings, round_part x 3 operand counts x 2 pairings, round_fin, eq
-    assert len(per_field[0]) == 10 and len({len(p) for p in per_field}) == 1, per_field
+    # fold x 2 pairings, round_fin, eq
+    assert len(per_field[0]) == 4 and len({len(p) for p in per_field}) == 1, per_field
     assert sum(len(p) for p in per_field) == len(names), names    # instantiated on the three scalar fields and nothing else
     assert len({tuple(re.sub(r"INS_\d+Fr_[A-Z0-9]+E", "", n) for n in p) for p in per_field}) == 1, per_field
     for n in names:
         assert scratch[n] == 0, (n, scratch[n])
-        cap = 168 if re.match(r"_ZN3blz\d+k_mle_round_partINS_\d+Fr_[A-Z0-9]+ELi3E", n) else 128
-        assert vgprs[n] <= cap, (n, vgprs[n], cap)
+        assert vgprs[n] <= 128, (n, vgprs[n])
         # the other ISA tests select kernels by these fragments: the new ones stay out of their sets
-        for family in (r"k_fold_", r"k_vec_", r"k_horner_", r"k_gather_", r"k_spmv_", r"k3t?_"):
+        for family in (r"k_sc_", r"k_fold_", r"k_vec_", r"k_horner_", r"k_gather_", r"k_spmv_", r"k3t?_"):
             assert not re.match(rf"_ZN3blz\d+{family}", n), (n, family)
         assert "k_ntt512_rr" not in n and "poseidon" not in n
 
 
 def test_multiplies_per_kernel(code):
     """v_mad_u64_u32 is the multiplier of field.hip.hpp: a Montgomery product of 8 limbs is 128 of them, vec_canon at most 8.
-    The fold holds the product of its loop (and r's conversion); a round at K = 1 holds none - its pairs cost two canons per
-    operand -, and every further operand adds a product per point."""
+    The fold holds the product of its loop (and r's conversion), the equality table its doubling's and its outer word's."""
     vgprs, _, text = code
     mads = {n: count(function_instructions(text, n), "v_mad_u64_u32") for n in vgprs if re.match(r"_ZN3blz\d+k_mle_", n)}
     print(mads)
-    assert len(mads) == 30
+    assert len(mads) == 12
     for f in FIELDS:
         for low in (0, 1):
             assert mads[_kernel(mads, rf"k_mle_foldINS_{f}ELb{low}E")] >= 128, (f, low)
-            k1, k2, k3 = (mads[_kernel(mads, rf"k_mle_round_partINS_{f}ELi{k}ELb{low}E")] for k in (1, 2, 3))
-            assert k1 < 128 <= k2 < k3, (f, low, k1, k2, k3)
         assert mads[_kernel(mads, rf"k_mle_eqINS_{f}E")] >= 128, f

@@ -1,9 +1,9 @@
 """The fused sumcheck step on resident tables (blz_ntt_sumcheck_step), the part that needs no device: the entry point and the two
 gates exist in every layer with the documented signature, behind the bank permutations, a null handle is refused whatever else
-is passed, the kernels live in their own header and reach the handle through NttFieldOps, the pointer checks still exist once,
-and the shipped gfx950 code object holds what the kernels promise - the same set of k_sc_* kernels for the three scalar fields
-and nothing else, no scratch, VGPRs within the occupancy step DESIGN.md records, a bind that holds its fold's product, and a
-gate that grows with every table."""
+is passed, the one round kernel lives in its own header and reaches the handle through NttFieldOps, the pointer checks still exist
+once, and the shipped gfx950 code object holds what the kernels promise - the same set of k_sc_round instantiations (pair rounds,
+vec_mle_round's included, and quad binds) for the three scalar fields and nothing else, no scratch, VGPRs within the occupancy
+step DESIGN.md records, a bind that holds its fold's product, and a gate that grows with every table."""
 import ctypes
 import os
 import re
@@ -67,8 +67,15 @@ def test_kernels_in_their_own_header_behind_the_field_ops():
     assert '#include "ntt_sumcheck.hip.hpp"' in impl
     assert "o.sumcheck_step = " in impl and re.search(r"\(\*sumcheck_step\)\s*\(\s*hipStream_t\s+st\s*,", eng)
     src = _read("blaze_amd", "csrc", "ntt_sumcheck.hip.hpp")
-    # PRODUCT without r is vec_mle_round, a bind alone is vec_mle_fold: their launchers, not second copies
-    assert "ntt_vec_mle_round_t<Fr>(" in src and "ntt_vec_mle_fold_t<Fr>(" in src and "k_mle_round_fin<Fr>" in src
+    # a bind alone is vec_mle_fold's launcher, not a second copy; every round polynomial - vec_mle_round's too - is ONE kernel over
+    # a pair source and a gate, and the block reduction of its accumulators is written once
+    assert "ntt_vec_mle_fold_t<Fr>(" in src and "k_mle_round_fin<Fr>" in src
+    both = _read("blaze_amd", "csrc", "ntt_mle.hip.hpp") + src
+    kernels = re.findall(r"template\s*<([^>]*)>\s*__global__[^\n;{]*?\bvoid\s+(\w+)\s*\(", both)
+    assert sorted(k for _, k in kernels) == ["k_mle_eq", "k_mle_fold", "k_mle_round_fin", "k_sc_round"], kernels
+    assert [k for params, k in kernels if "GATE" in params] == ["k_sc_round"], kernels
+    assert both.count("fold_block_tree<Fr>(x, acc[t]") == 1
+    assert "o.vec_mle_round" not in impl and "(*vec_mle_round)" not in eng
     statements = re.sub(r"//[^\n]*", "", src)
     for banned in ("atomic", "alloc", "volatile"):   # no atomics, no flags, no allocation
         assert banned not in statements, banned
@@ -89,7 +96,7 @@ def test_documented_where_the_other_ops_are():
         text = _read(doc)
         assert "sumcheck_step" in text, doc
     design = _read("DESIGN.md")
-    assert "BLZ_GATE_R1CS" in design and "k_sc_bind" in design and "k_sc_round_r1cs" in design
+    assert "BLZ_GATE_R1CS" in design and "k_sc_round<Fr, Source, GATE, K>" in design and "ScPairs" in design and "ScQuads" in design
 
 
 @pytest.fixture(scope="module")
@@ -106,9 +113,14 @@ def _kernel(names, pattern):
 
 
 # The next occupancy step (128, 168 or 256 VGPRs: 4, 3 or 2 waves per SIMD) above what the compiler reports (DESIGN.md section 4,
-# "Sumcheck step": bind K = 1 138 - 140, K = 2 129 - 144, K = 3 167 - 170, R1CS 192 - 201, round-only R1CS 134 - 144)
-VGPR_CAP = {r"k_sc_bindINS_\d+Fr_[A-Z0-9]+ELi0ELi1E": 168, r"k_sc_bindINS_\d+Fr_[A-Z0-9]+ELi0ELi2E": 168, r"k_sc_bindINS_\d+Fr_[A-Z0-9]+ELi0ELi3E": 256,
-            r"k_sc_bindINS_\d+Fr_[A-Z0-9]+ELi1ELi4E": 256, r"k_sc_round_r1csINS_\d+Fr_[A-Z0-9]+E": 168}
+# "Sumcheck step": pair rounds K = 1 73 - 77, K = 2 98 - 101, K = 3 118 - 128, R1CS 134 - 144; quad binds K = 1 138 - 140,
+# K = 2 160 - 164, K = 3 167 - 170, R1CS 192 - 201).  k_sc_round<Fr, Source, GATE, K>: GATE 0 = PRODUCT, 1 = R1CS
+FR = r"INS_\d+Fr_[A-Z0-9]+E"
+PAIRS, QUADS = r"NS_\d+ScPairsILb[01]EEE", r"NS_\d+ScQuadsE"
+VGPR_CAP = {rf"k_sc_round{FR}{PAIRS}Li0ELi1E": 128, rf"k_sc_round{FR}{PAIRS}Li0ELi2E": 128, rf"k_sc_round{FR}{PAIRS}Li0ELi3E": 168,
+            rf"k_sc_round{FR}{PAIRS}Li1ELi4E": 168,
+            rf"k_sc_round{FR}{QUADS}Li0ELi1E": 168, rf"k_sc_round{FR}{QUADS}Li0ELi2E": 168, rf"k_sc_round{FR}{QUADS}Li0ELi3E": 256,
+            rf"k_sc_round{FR}{QUADS}Li1ELi4E": 256}
 
 
 def test_sc_kernels_stay_out_of_scratch_and_within_their_vgprs(code):
@@ -116,8 +128,9 @@ def test_sc_kernels_stay_out_of_scratch_and_within_their_vgprs(code):
     names = sorted(n for n in vgprs if re.match(r"_ZN3blz\d+k_sc_", n))
     print({n: (vgprs[n], scratch[n]) for n in names})
     per_field = [[n for n in names if re.match(rf"_ZN3blz\d+k_sc_\w+?INS_{f}E", n)] for f in FIELDS]
-    # four bind kernels (PRODUCT K = 1, 2, 3; R1CS), one round-only R1CS kernel; the finish is k_mle_round_fin
-    assert len(per_field[0]) == 5 and len({len(p) for p in per_field}) == 1, per_field
+    # six PRODUCT pair rounds (K = 1, 2, 3 x the two pairings), one R1CS pair round, four quad binds (PRODUCT K = 1, 2, 3; R1CS)
+    # and nothing else - no R1CS with the low pairing, no low quads; the finish is k_mle_round_fin
+    assert len(per_field[0]) == 11 and len({len(p) for p in per_field}) == 1, per_field
     assert sum(len(p) for p in per_field) == len(names), names    # instantiated on the three scalar fields and nothing else
     assert len({tuple(re.sub(r"INS_\d+Fr_[A-Z0-9]+E", "", n) for n in p) for p in per_field}) == 1, per_field
     for n in names:
@@ -131,16 +144,20 @@ def test_sc_kernels_stay_out_of_scratch_and_within_their_vgprs(code):
 
 
 def test_multiplies_per_kernel(code):
-    """v_mad_u64_u32 is the multiplier of field.hip.hpp: a Montgomery product of 8 limbs is 128 of them.  Every bind kernel holds
-    the product of its fold (and r's conversion), and each table a gate takes adds multiply-adds."""
+    """v_mad_u64_u32 is the multiplier of field.hip.hpp: a Montgomery product of 8 limbs is 128 of them, vec_canon at most 8.  A
+    pair round at K = 1 holds no product - its pairs cost two canons per operand -, every bind kernel holds the product of its
+    fold (and r's conversion), and each table a gate takes adds multiply-adds."""
     vgprs, _, text = code
     mads = {n: count(function_instructions(text, n), "v_mad_u64_u32") for n in vgprs if re.match(r"_ZN3blz\d+k_sc_", n)}
     print(mads)
-    assert len(mads) == 15
+    assert len(mads) == 33
     for f in FIELDS:
-        k1, k2, k3 = (mads[_kernel(mads, rf"k_sc_bindINS_{f}ELi0ELi{k}E")] for k in (1, 2, 3))
-        r1cs = mads[_kernel(mads, rf"k_sc_bindINS_{f}ELi1ELi4E")]
-        rnd = mads[_kernel(mads, rf"k_sc_round_r1csINS_{f}E")]
+        for low in (0, 1):
+            k1, k2, k3 = (mads[_kernel(mads, rf"k_sc_roundINS_{f}ENS_\d+ScPairsILb{low}EEELi0ELi{k}E")] for k in (1, 2, 3))
+            assert k1 < 128 <= k2 < k3, (f, low, k1, k2, k3)
+        k1, k2, k3 = (mads[_kernel(mads, rf"k_sc_roundINS_{f}E{QUADS}Li0ELi{k}E")] for k in (1, 2, 3))
+        r1cs = mads[_kernel(mads, rf"k_sc_roundINS_{f}E{QUADS}Li1ELi4E")]
+        rnd = mads[_kernel(mads, rf"k_sc_roundINS_{f}ENS_\d+ScPairsILb0EEELi1ELi4E")]
         assert 128 <= k1 < k2 < k3, (f, k1, k2, k3)
         assert r1cs >= 128 and rnd >= 128, (f, r1cs, rnd)
         assert rnd < r1cs, (f, rnd, r1cs)   # the bind is the round's gate plus the folds
