@@ -44,6 +44,20 @@ class BlzVecView(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("stride", C.c_uint64), ("len", C.c_uint64)]
 
 
+GATE_MAX_TABLES, GATE_MAX_TERMS, GATE_MAX_FACTORS, GATE_MAX_POINTS = 12, 8, 4, 6   # BLZ_GATE_MAX_* (include/blaze_hip.h)
+
+
+class BlzGateTerm(C.Structure):
+    """struct blz_gate_term (include/blaze_hip.h), 8 bytes: one signed product of tables of a caller-defined gate."""
+    _fields_ = [("nfactors", C.c_uint8), ("negate", C.c_uint8), ("factor", C.c_uint8 * GATE_MAX_FACTORS), ("reserved", C.c_uint8 * 2)]
+
+
+class BlzSumGate(C.Structure):
+    """struct blz_sum_gate (include/blaze_hip.h), 80 bytes: the gate blz_ntt_sumcheck_gate takes, T[common] x a signed sum of terms."""
+    _fields_ = [("ntables", C.c_uint32), ("nterms", C.c_uint32), ("common", C.c_int32), ("reserved", C.c_uint32),
+                ("term", BlzGateTerm * GATE_MAX_TERMS)]
+
+
 class BlzVecCsr(C.Structure):
     """struct blz_vec_csr (include/blaze_hip.h): the sparse matrix blz_ntt_vec_spmv multiplies by, CSR arrays in device memory."""
     _fields_ = [("d_row_ptr", C.c_void_p), ("d_col", C.c_void_p), ("d_val", C.c_void_p), ("rows", C.c_uint64), ("nnz", C.c_uint64)]
@@ -134,6 +148,7 @@ _SIGS = {
     "blz_ntt_banks_postprocess_device": (C.c_int, [C.c_void_p, _u8p, _u8p]),
     "blz_ntt_sumcheck_step": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg),
                                         C.POINTER(BlzVecArg), C.c_uint32, C.c_uint64, C.c_void_p]),
+    "blz_ntt_sumcheck_gate": (C.c_int, [C.c_void_p, C.POINTER(BlzSumGate), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_uint32, C.c_uint64, C.c_void_p]),
     "blz_poseidon_new": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "blz_poseidon_free": (None, [C.c_void_p]),
     "blz_poseidon_loaded_binary_parameters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),

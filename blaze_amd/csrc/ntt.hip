@@ -1012,6 +1012,73 @@ int blz_ntt_sumcheck_step(blz_ntt* h, uint32_t gate, const blz_vec_arg* a, const
                         wbuf[1]);
 }
 
+// The step for a caller-defined gate (ntt_gate.hip.hpp).  The description is checked and packed here - the longest term's
+// length F, each term's deficit F - nfactors, the close power - and travels to the kernel by value; the tables then walk
+// blz_ntt_sumcheck_step's protocol as tables[0 .. ntables).
+int blz_ntt_sumcheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* tables, const blz_vec_arg* r, uint32_t points, uint64_t len,
+                          void* d_out) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (!gate || !tables) return fail(BLZ_ERR_INVALID_PARAM, "a gate step takes %s", !gate ? "a gate: gate is NULL" : "the gate's tables: tables is NULL");
+    if (gate->ntables < 1 || gate->ntables > BLZ_GATE_MAX_TABLES) return fail(BLZ_ERR_INVALID_PARAM, "gate: ntables %u is not in [1, %d]", gate->ntables, BLZ_GATE_MAX_TABLES);
+    if (gate->nterms < 1 || gate->nterms > BLZ_GATE_MAX_TERMS) return fail(BLZ_ERR_INVALID_PARAM, "gate: nterms %u is not in [1, %d]", gate->nterms, BLZ_GATE_MAX_TERMS);
+    if (gate->common < -1 || gate->common >= (int32_t)gate->ntables)
+        return fail(BLZ_ERR_INVALID_PARAM, "gate: common %d is neither -1 nor a table index below ntables %u", gate->common, gate->ntables);
+    if (gate->reserved != 0) return fail(BLZ_ERR_INVALID_PARAM, "gate: reserved must be 0");
+    const int nt = (int)gate->ntables;
+    NttGate g{};
+    g.ntables = gate->ntables;
+    g.nterms = gate->nterms;
+    g.common = gate->common;
+    uint32_t longest = 0;
+    for (uint32_t m = 0; m < gate->nterms; ++m) {
+        const blz_gate_term& t = gate->term[m];
+        if (t.nfactors < 1 || t.nfactors > BLZ_GATE_MAX_FACTORS) return fail(BLZ_ERR_INVALID_PARAM, "gate: term %u: nfactors %u is not in [1, %d]", m, t.nfactors, BLZ_GATE_MAX_FACTORS);
+        if (t.negate > 1) return fail(BLZ_ERR_INVALID_PARAM, "gate: term %u: negate %u is not 0 or 1", m, t.negate);
+        if (t.reserved[0] != 0 || t.reserved[1] != 0) return fail(BLZ_ERR_INVALID_PARAM, "gate: term %u: reserved must be 0", m);
+        for (uint32_t j = 0; j < t.nfactors; ++j)
+            if (t.factor[j] >= gate->ntables)
+                return fail(BLZ_ERR_INVALID_PARAM, "gate: term %u: factor %u names table %u, ntables is %u", m, j, t.factor[j], gate->ntables);
+        if (t.nfactors > longest) longest = t.nfactors;
+    }
+    for (uint32_t m = 0; m < gate->nterms; ++m) {
+        const blz_gate_term& t = gate->term[m];
+        g.term[m] = t.nfactors | (uint32_t)t.negate << 3 | (longest - t.nfactors) << 4;
+        for (uint32_t j = 0; j < t.nfactors; ++j) g.term[m] |= (uint32_t)t.factor[j] << (8 + 4 * j);
+    }
+    g.close_k = longest + (gate->common >= 0 ? 1u : 0u);
+    if (points > BLZ_GATE_MAX_POINTS) return fail(BLZ_ERR_INVALID_PARAM, "points %u is not in [0, %d]", points, BLZ_GATE_MAX_POINTS);
+    if (points == 0 && (!r || d_out)) return fail(BLZ_ERR_INVALID_PARAM, "points 0 is a bind alone: it takes r and a NULL d_out");
+    if (points > 0 && !d_out) return fail(BLZ_ERR_INVALID_PARAM, "null d_out");
+    if (r && (!r->d_ptr || r->count != 1))
+        return fail(BLZ_ERR_INVALID_PARAM, "a sumcheck step takes the challenge as one device word: r.d_ptr != NULL, r.count == 1");
+    NttVecCall call{h};
+    BLZ_TRY(call.live_length(len));
+    if (r && points > 0 && len < 4) return fail(BLZ_ERR_INVALID_PARAM, "len %llu: a bind and a round need len >= 4", (unsigned long long)len);
+    BLZ_TRY(call.begin());
+    static const char* const names[BLZ_GATE_MAX_TABLES] = {"tables[0]", "tables[1]", "tables[2]", "tables[3]", "tables[4]",  "tables[5]",
+                                                           "tables[6]", "tables[7]", "tables[8]", "tables[9]", "tables[10]", "tables[11]"};
+    auto tab = [&](int i) { return NttVecCall::Operand{names[i], i < nt ? tables + i : nullptr, &g.t[i]}; };
+    NttVecArg vr{};
+    BLZ_TRY(call.resolve({tab(0), tab(1), tab(2), tab(3), tab(4), tab(5), tab(6), tab(7), tab(8), tab(9), tab(10), tab(11), {"r", r, &vr}}, "d_out", d_out, points));
+    int wbuf[2] = {-1, -1};
+    if (r) {
+        const uint64_t half = len >> 1;
+        for (int j = 0; j < nt; ++j) {
+            if (g.t[j].mask + 1 < len)
+                return fail(BLZ_ERR_INVALID_PARAM, "operand %s: %llu words, read periodically over len %llu: a periodic table cannot be folded in place", names[j],
+                            (unsigned long long)(g.t[j].mask + 1), (unsigned long long)len);
+            for (int i = 0; i < j; ++i)
+                if (NttVecCall::words_meet(g.t[i].p, len, g.t[j].p, len))
+                    return fail(BLZ_ERR_INVALID_PARAM, "%s and %s overlap in their first len words: each is folded in place", names[i], names[j]);
+            if (NttVecCall::words_meet(vr.p, 1, g.t[j].p, half)) return fail(BLZ_ERR_INVALID_PARAM, "r lies in the words %s receives", names[j]);
+            if (d_out && NttVecCall::words_meet(d_out, points, g.t[j].p, len))
+                return fail(BLZ_ERR_INVALID_PARAM, "d_out lies in the live words of %s", names[j]);
+            if (!tables[j].d_ptr) wbuf[wbuf[0] < 0 ? 0 : 1] = (int)tables[j].buf;
+        }
+    }
+    return call.enqueue(wbuf[0], [&](uint32_t*) { return h->ops->sumcheck_gate(h->stream, g, r ? vr.p : nullptr, points, len, (uint32_t*)d_out, call.ws); }, wbuf[1]);
+}
+
 int blz_ntt_last_kernel_ms(blz_ntt* h, float* out) {
     if (!h || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
     *out = h->last_ms;

@@ -76,7 +76,18 @@ struct NttVecArg {
     const uint32_t* p;
     uint64_t mask;
 };
-constexpr int NTT_VEC_OPS = 6;               // enum blz_vec_op: ADD SUB MUL MULADD MULSUB INV
+// A caller-defined gate (blz_sum_gate, checked and packed by ntt.hip; kernels: ntt_gate.hip.hpp), by value in the kernel arguments.
+// term[m] = nfactors | negate << 3 | deficit << 4 | factor j << (8 + 4 j): deficit = F - nfactors, F the longest term's nfactors;
+// close_k = F + (common >= 0), the operands of the longest product: what the finish strips
+constexpr int NTT_GATE_MAX_TABLES = 12, NTT_GATE_MAX_TERMS = 8, NTT_GATE_MAX_FACTORS = 4, NTT_GATE_MAX_POINTS = 6;   // BLZ_GATE_MAX_*
+struct NttGate {
+    uint32_t ntables, nterms;
+    int32_t common;   // < 0: none
+    uint32_t close_k;
+    uint32_t term[NTT_GATE_MAX_TERMS];
+    NttVecArg t[NTT_GATE_MAX_TABLES];
+};
+constexpr int NTT_VEC_OPS = 6;              // enum blz_vec_op: ADD SUB MUL MULADD MULSUB INV
 constexpr uint64_t NTT_VEC_INV_TILE = 1024;  // batch inversion: elements per block (256 lanes x 4); one 32-byte total per tile
 constexpr int NTT_FOLD_OPS = 3;              // enum blz_fold_op: SUM DOT EVAL
 constexpr int NTT_SCAN_OPS = 2;              // enum blz_scan_op: SUM PROD
@@ -142,6 +153,9 @@ struct NttFieldOps {
     // BLZ_MLE_LOW pairs (2p, 2p + 1), for BLZ_GATE_PRODUCT without r alone
     int (*sumcheck_step)(hipStream_t st, uint32_t gate, uint32_t flags, int k, const NttVecArg* t, const uint32_t* r, uint32_t points,
                          uint64_t len, uint32_t* out, uint32_t* ws);
+    // The same step for a caller-defined gate (blz_ntt_sumcheck_gate; kernels: ntt_gate.hip.hpp): g's tables take the place of
+    // t[0 .. k) under the same rules, EVERY table of g is folded with r, points <= NTT_GATE_MAX_POINTS
+    int (*sumcheck_gate)(hipStream_t st, const NttGate& g, const uint32_t* r, uint32_t points, uint64_t len, uint32_t* out, uint32_t* ws);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

@@ -11,6 +11,7 @@
 #include "ntt_spmv.hip.hpp"
 #include "ntt_mle.hip.hpp"
 #include "ntt_sumcheck.hip.hpp"
+#include "ntt_gate.hip.hpp"
 
 namespace blz {
 
@@ -527,6 +528,7 @@ NttFieldOps make_ntt_ops() {
     o.vec_mle_fold = &ntt_vec_mle_fold_t<Fr>;
     o.vec_mle_eq = &ntt_vec_mle_eq_t<Fr>;
     o.sumcheck_step = &ntt_sumcheck_step_t<Fr>;
+    o.sumcheck_gate = &ntt_sumcheck_gate_t<Fr>;
     return o;
 }
 

@@ -134,11 +134,11 @@ BLZ_DEV void mle_round_close(Fp<Fr>& x, int k) {
 
 // The block's accumulators: direct != 0 (one block): out = d_out, `points` canonical words; else out = the workspace, word
 // t * gridDim.x + block = the block's partial of point t, with the stray power of 1 / R
-template <class Fr>
-BLZ_DEV void sc_block_sums(uint32_t* x, uint32_t* out, const Fp<Fr> (&acc)[MLE_MAX_POINTS], uint32_t points, uint32_t direct, int close_k) {
+template <class Fr, int NP>
+BLZ_DEV void sc_block_sums(uint32_t* x, uint32_t* out, const Fp<Fr> (&acc)[NP], uint32_t points, uint32_t direct, int close_k) {
     using E = Fp<Fr>;
 #pragma unroll
-    for (int t = 0; t < MLE_MAX_POINTS; ++t) {
+    for (int t = 0; t < NP; ++t) {
         if (t < (int)points) {
             fold_block_tree<Fr>(x, acc[t], [](E& l, const E& r, int) { fp_add(l, l, r); });
             if (direct) {

@@ -6,7 +6,7 @@ import enum
 from dataclasses import dataclass
 from typing import Optional
 
-from ._lib import BlzVecArg, BlzVecCsr, BlzVecView, DeviceBuffer, buf_ptr, check, lib
+from ._lib import GATE_MAX_FACTORS, GATE_MAX_TABLES, GATE_MAX_TERMS, BlzSumGate, BlzVecArg, BlzVecCsr, BlzVecView, DeviceBuffer, buf_ptr, check, lib
 from .driver_client import DriverClient, DriverPrimitive
 
 NTT_LOG_SIZE = 27  # ntt_data.rs:65: NTT_SIZE = 2^27
@@ -327,6 +327,44 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         args = [self._vec_arg(x) for x in tables + [None] * (4 - len(tables)) + [r]]
         check(lib().blz_ntt_sumcheck_step(self._h, int(gate), *[None if v is None else C.byref(v) for v in args], points,
                                           self._mle_len(length, *(tables or [0])), None if out is None else out.ptr))
+        self._vec_keep = (*tables, r, out)
+        return out if points > 0 else None
+
+    def sumcheck_gate(self, tables, terms, common: Optional[int] = None, r: Optional[DeviceBuffer] = None, points: Optional[int] = None,
+                      length: Optional[int] = None, out: Optional[DeviceBuffer] = None) -> Optional[DeviceBuffer]:
+        """sumcheck_step for a caller-defined gate (blz_ntt_sumcheck_gate): G = tables[common] x sum of the signed products
+        `terms`, a list of (sign, [table indices]) - sign +1 / -1, 1 to 4 indices into `tables` (at most 12 ints / DeviceBuffers),
+        an index may repeat, `common` (None: no common factor) may also be a factor.  A vanilla PLONK zerocheck over
+        [eq, qL, qR, qM, qO, qC, a, b, c] is common=0, terms=[(1, [1, 6]), (1, [2, 7]), (1, [3, 6, 7]), (-1, [4, 8]), (1, [5])].
+        With `r` EVERY table is folded in place - named by a term or not - and out[t], t < points, is the round polynomial of
+        the folded tables; without `r` the round alone (nothing is written; periodic tables allowed, a constant selector is a
+        one-word DeviceBuffer).  points defaults to the gate's degree + 1 and is at most 6; points=0 (with r) binds only and
+        returns None.  length=None means the longest table named."""
+        tables, terms = list(tables), list(terms)
+        if len(tables) > GATE_MAX_TABLES or len(terms) > GATE_MAX_TERMS:
+            raise ValueError(f"a gate takes at most {GATE_MAX_TABLES} tables and {GATE_MAX_TERMS} terms, {len(tables)} and {len(terms)} given")
+        gate = BlzSumGate(len(tables), len(terms), -1 if common is None else int(common), 0)
+        degree = 0
+        for m, (sign, factors) in enumerate(terms):
+            factors = [int(f) for f in factors]
+            if sign not in (1, -1) or len(factors) > 255 or any(f < 0 or f > 255 for f in factors):
+                raise ValueError(f"term {m}: a term is (+1 | -1, [table indices])")
+            gate.term[m].nfactors, gate.term[m].negate = len(factors), int(sign < 0)
+            for j, f in enumerate(factors[:GATE_MAX_FACTORS]):   # (a longer term is the library's to refuse: nfactors says so)
+                gate.term[m].factor[j] = f
+            degree = max(degree, len(factors))
+        if points is None:
+            points = degree + (common is not None) + 1
+        points = int(points)
+        if out is None and points > 0:
+            out = DeviceBuffer(self.driver_client.id, NTT_WORD_SIZE * points)
+        args = (BlzVecArg * max(len(tables), 1))(*[self._vec_arg(x) for x in tables])
+        vr = self._vec_arg(r)
+        if length is None:
+            n = 1 << self.log_size
+            length = max([x.nbytes // NTT_WORD_SIZE if isinstance(x, DeviceBuffer) else n for x in tables] or [0])
+        check(lib().blz_ntt_sumcheck_gate(self._h, C.byref(gate), args, None if vr is None else C.byref(vr), points, int(length),
+                                          None if out is None else out.ptr))
         self._vec_keep = (*tables, r, out)
         return out if points > 0 else None
 

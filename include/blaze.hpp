@@ -319,6 +319,16 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
         const uint32_t degree = gate == BLZ_GATE_R1CS ? 3u : 1u + (b ? 1u : 0u) + (c ? 1u : 0u);
         check(blz_ntt_sumcheck_step(h_, gate, a, b, c, d, r, bind_only ? 0u : points ? points : degree + 1u, len, d_out));
     }
+    // the same step for a caller-defined gate (blz_ntt_sumcheck_gate): G = tables[common] x sum of the gate's signed products of
+    // tables; `tables` holds gate.ntables operands and with r EVERY one is folded in place.  points defaults to the gate's degree
+    // + 1 (the longest term's factors, plus one for a common factor), at most BLZ_GATE_MAX_POINTS
+    void sumcheck_gate(const blz_sum_gate& gate, const blz_vec_arg* tables, const blz_vec_arg* r, uint64_t len, void* d_out, uint32_t points = 0,
+                       bool bind_only = false) {
+        uint32_t degree = 0;
+        for (uint32_t m = 0; m < gate.nterms && m < BLZ_GATE_MAX_TERMS; ++m) degree = gate.term[m].nfactors > degree ? gate.term[m].nfactors : degree;
+        degree += gate.common >= 0 ? 1u : 0u;
+        check(blz_ntt_sumcheck_gate(h_, &gate, tables, r, bind_only ? 0u : points ? points : degree + 1u, len, d_out));
+    }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

@@ -584,7 +584,8 @@ int blz_ntt_vec_spmv(blz_ntt* h, size_t buf_dst, const blz_vec_arg* x, const blz
  *                          polynomial of the product of k tables at the points 0, 1, 2, 3; pairing as in the fold.  k = 1 .. 3 is
  *                          the number of operands, given as a, then b, then c, the ones not taken NULL (b NULL with c set is
  *                          refused); the same table may be named twice.  points = 1 .. 4 is independent of k: a gate that is a
- *                          sum of products of different degrees is one call per product at the same `points`, and the outputs add.
+ *                          sum of products of different degrees is one call per product at the same `points`, and the outputs add
+ *                          (or ONE blz_ntt_sumcheck_gate, below).
  *                          out[0] + out[1] is the sum (k = 1) or the dot product (k = 2) of the live prefix.
  *   blz_ntt_vec_mle_eq     dst[p] = prod_{i < m} (x_i tau_i + (1 - x_i)(1 - tau_i)) for p < 2^m, tau_i = word i of d_point, x_i =
  *                          bit i of p.  0 <= m <= log_size; m = 0 writes the single word 1.  out_len = 2^m.
@@ -666,6 +667,64 @@ int blz_ntt_banks_postprocess_device(blz_ntt* h, const void* d_banks, void* d_ou
 #define BLZ_GATE_R1CS    1u   /* G = a (b c - d)     (all four tables) */
 int blz_ntt_sumcheck_step(blz_ntt* h, uint32_t gate, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c,
                           const blz_vec_arg* d, const blz_vec_arg* r, uint32_t points, uint64_t len, void* d_out);
+/* The same step for a CALLER-DEFINED gate: a common factor times a signed sum of products of tables,
+ *     G = T[common] x sum_{m < nterms} (+/-) prod_{j < nfactors_m} T[factor_mj]        (common == -1: no common factor)
+ * which is what a PLONK zerocheck eq (qL a + qR b + qM a b - qO c + qC), a GKR layer add (x + y) + mul x y or a batched Spartan
+ * second sumcheck need: up to BLZ_GATE_MAX_TABLES tables, BLZ_GATE_MAX_TERMS terms of up to BLZ_GATE_MAX_FACTORS factors (the
+ * common factor not counted) and BLZ_GATE_MAX_POINTS points, in ONE op fused with the bind.  The gate is data, not code: the
+ * description below is read on the host, checked, and handed to one kernel.
+ *   Layout (fixed; mirrored byte for byte by blaze_amd/_lib.py, include/blaze.hpp and rust/src/driver_client/hip_ffi.rs):
+ *     blz_gate_term, 8 bytes:  0 nfactors (1 .. 4) | 1 negate (0: added, 1: subtracted) | 2 .. 5 factor[4], table indices, the
+ *       first nfactors are read | 6 .. 7 reserved, must be 0.
+ *     blz_sum_gate, 80 bytes:  0 ntables (1 .. 12) | 4 nterms (1 .. 8) | 8 common (-1, or a table index) | 12 reserved, must
+ *       be 0 | 16 term[8], the first nterms are read.
+ *   A table index may repeat inside a term (a a) and across terms, and common may also be a factor.  tables[] holds ntables
+ *   operands; messages name them tables[i].
+ *   Semantics: those of blz_ntt_sumcheck_step with G in the gate's place.
+ *   r != NULL - bind, then round: EVERY table of tables[] is folded in place, T[p] = T[p] + r (T[p + len / 2] - T[p]) for
+ *     p < len / 2, once, whether a term names it or not (tables that only ride along are bound by the same op) - exactly len / 2
+ *     words of each are written, every other byte keeps its value.  Then
+ *       d_out[t] = sum_{p < len / 4} G(.., T_j[p] + t (T_j[p + len / 4] - T_j[p]), ..) for t < points.
+ *     len >= 4, 1 <= points <= BLZ_GATE_MAX_POINTS whatever the gate's degree.  points == 0 with d_out == NULL is a bind alone
+ *     (len >= 2): one fold per table in the one op; the description is still checked.
+ *   r == NULL - round only: d_out[t] = sum_{p < len / 2} G(.. lo_j + t (hi_j - lo_j) ..) over the pairs (T[p], T[p + len / 2]).
+ *     Nothing is written to a table; periodic tables (count < len) are allowed - a constant selector is a one-word table.
+ *   Values: any 256-bit input word counts as its residue; every word written - table words and d_out alike - is canonical,
+ *   little-endian.
+ *   Cost ("Caller-defined gates"; derived from the code): with r each table's len words are read and
+ *   len / 2 written, once, and the lane's own two folded words are read again (from cache) once per time a term or common names
+ *   the table.  Montgomery products per quad: 2 ntables for the folds, plus per term of f factors points x (f - 1) and
+ *   2 (F - f), F the longest term's f, plus points for a common factor: R1CS as common = eq, + Az Bz, - Cz is 8 + 6 + 4 = 18
+ *   at 4 points, BLZ_GATE_R1CS's count; the PLONK gate above, 9 tables at 5 points, 58.
+ *   Protocol, in-flight rules and operand checks: blz_ntt_sumcheck_step's, by the same code.  With r both transform buffers may
+ *   be tables and neither may then be read, written or exchanged until blz_ntt_wait_result; without r the buffers named are
+ *   read-only.  Memory behind every pointer stays valid until blz_ntt_wait_result returns; the description is copied.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing: a null handle (refused before any other argument is looked at), a null gate or
+ *   tables, ntables outside 1 .. 12, nterms outside 1 .. 8, common below -1 or not below ntables, a term's nfactors outside
+ *   1 .. 4, negate above 1, a factor index not below ntables, a nonzero reserved byte, points above 6, points == 0 without r or
+ *   with a d_out, a null d_out with points > 0, len not a power of two in [2, n] ([4, n] for a bind and a round), r naming a
+ *   buffer or with count != 1, an op in flight, any operand error of blz_ntt_vec_op, a bad d_out or one that overlaps a d_ptr
+ *   operand; with r: a table with count < len, two tables whose first len words overlap, r inside the words written, d_out
+ *   inside the first len words of a table. */
+#define BLZ_GATE_MAX_TABLES  12
+#define BLZ_GATE_MAX_TERMS    8
+#define BLZ_GATE_MAX_FACTORS  4   /* per term, the common factor not counted */
+#define BLZ_GATE_MAX_POINTS   6
+typedef struct blz_gate_term {
+    uint8_t nfactors;                       /* 1 .. BLZ_GATE_MAX_FACTORS */
+    uint8_t negate;                         /* 0: the term is added, 1: subtracted */
+    uint8_t factor[BLZ_GATE_MAX_FACTORS];   /* table indices; the first nfactors are read */
+    uint8_t reserved[2];                    /* must be 0 */
+} blz_gate_term;
+typedef struct blz_sum_gate {
+    uint32_t ntables;    /* 1 .. BLZ_GATE_MAX_TABLES */
+    uint32_t nterms;     /* 1 .. BLZ_GATE_MAX_TERMS */
+    int32_t common;      /* -1: none; else the table every term is multiplied by */
+    uint32_t reserved;   /* must be 0 */
+    blz_gate_term term[BLZ_GATE_MAX_TERMS];   /* the first nterms are read */
+} blz_sum_gate;
+int blz_ntt_sumcheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* tables, const blz_vec_arg* r, uint32_t points,
+                          uint64_t len, void* d_out);
 
 /* ------------------------------------------------------------------ Poseidon octal Merkle tree (src/ingo_hash/poseidon_api.rs)
  *

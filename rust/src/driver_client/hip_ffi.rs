@@ -53,6 +53,30 @@ pub const BLZ_MLE_LOW: u32 = 1;
 pub const BLZ_GATE_PRODUCT: u32 = 0;
 /// `BLZ_GATE_R1CS`: the gate is a (b c - d) over its four tables.
 pub const BLZ_GATE_R1CS: u32 = 1;
+/// The limits of a caller-defined gate (`blz_ntt_sumcheck_gate`): tables, terms, factors per term (the common factor not counted), points.
+pub const BLZ_GATE_MAX_TABLES: usize = 12;
+pub const BLZ_GATE_MAX_TERMS: usize = 8;
+pub const BLZ_GATE_MAX_FACTORS: usize = 4;
+pub const BLZ_GATE_MAX_POINTS: u32 = 6;
+/// `struct blz_gate_term` (8 bytes): one signed product of `nfactors` tables, named by their index in the call's `tables`.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct BlzGateTerm {
+    pub nfactors: u8,
+    pub negate: u8,
+    pub factor: [u8; BLZ_GATE_MAX_FACTORS],
+    pub reserved: [u8; 2],
+}
+/// `struct blz_sum_gate` (80 bytes): G = T\[common\] x the signed sum of the first `nterms` terms; `common` = -1: no common factor.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct BlzSumGate {
+    pub ntables: u32,
+    pub nterms: u32,
+    pub common: i32,
+    pub reserved: u32,
+    pub term: [BlzGateTerm; BLZ_GATE_MAX_TERMS],
+}
 
 pub const BLZ_COMM_ID_BYTES: usize = 128;
 
@@ -148,6 +172,8 @@ extern "C" {
     pub fn blz_ntt_vec_mle_eq(h: *mut BlzNtt, dst: *const BlzVecArg, d_point: *const c_void, m: u32) -> c_int;
     pub fn blz_ntt_sumcheck_step(h: *mut BlzNtt, gate: u32, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg, d: *const BlzVecArg,
                                  r: *const BlzVecArg, points: u32, len: u64, d_out: *mut c_void) -> c_int;
+    pub fn blz_ntt_sumcheck_gate(h: *mut BlzNtt, gate: *const BlzSumGate, tables: *const BlzVecArg, r: *const BlzVecArg, points: u32, len: u64,
+                                 d_out: *mut c_void) -> c_int;
 
     // ---- Poseidon tree: PoseidonClient (ingo_hash::poseidon_api)
     pub fn blz_poseidon_new(device_id: c_int, field: c_int, out: *mut *mut BlzPoseidon) -> c_int;

@@ -300,6 +300,31 @@ impl NTTClient {
                                     p(&rr), points, len, d_out))
     }
 
+    /// The same step for a caller-defined gate (blz_ntt_sumcheck_gate): G = T\[common\] x the signed sum of `terms`, each
+    /// `(negate, table indices)` a product of 1 ..= 4 of the `tables` (at most 12; an index may repeat; `common` may also be a
+    /// factor).  With `r` EVERY table is folded in place, named by a term or not; `points` is 1 ..= 6, or 0 with a null `d_out`
+    /// (and `r`) to bind only.  Without `r` the round alone, periodic tables allowed.
+    ///
+    /// # Safety
+    /// As for `sumcheck_step`.
+    pub unsafe fn sumcheck_gate(&self, tables: &[VecOperand], terms: &[(bool, &[u8])], common: Option<u8>, r: Option<VecOperand>, points: u32,
+                                len: u64, d_out: *mut std::os::raw::c_void) -> Result<()> {
+        let mut gate = BlzSumGate { ntables: tables.len() as u32, nterms: terms.len() as u32, common: common.map_or(-1, |c| c as i32), reserved: 0,
+                                    term: [BlzGateTerm::default(); BLZ_GATE_MAX_TERMS] };
+        for (slot, (negate, factors)) in gate.term.iter_mut().zip(terms.iter()) {
+            // a count the library refuses stays refusable: it is passed on, the indices that fit are copied
+            slot.nfactors = factors.len().min(255) as u8;
+            slot.negate = *negate as u8;
+            for (f, t) in slot.factor.iter_mut().zip(factors.iter()) {
+                *f = *t;
+            }
+        }
+        let raw: Vec<BlzVecArg> = tables.iter().map(|x| x.raw()).collect();
+        let rr = r.map(|v| v.raw());
+        check(blz_ntt_sumcheck_gate(self.h, &gate, if raw.is_empty() { std::ptr::null() } else { raw.as_ptr() },
+                                    rr.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg), points, len, d_out))
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
