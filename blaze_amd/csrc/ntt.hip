@@ -710,19 +710,23 @@ struct NttVecCall {
 
     // The operands in order, then the output words (d_out / d_total; nullptr: none): out_words x 32 bytes checked like an
     // operand's d_ptr, and kept off the words of every d_ptr operand.
-    int resolve(std::initializer_list<Operand> ops, const char* out_name = nullptr, void* d_out = nullptr, uint64_t out_words = 1) {
-        for (const Operand& o : ops)
-            if (o.v) BLZ_TRY(operand(o.name, o.v, *o.out, o.max_count ? o.max_count : n));
+    int resolve(const Operand* ops, size_t count, const char* out_name = nullptr, void* d_out = nullptr, uint64_t out_words = 1) {
+        for (size_t i = 0; i < count; ++i)
+            if (ops[i].v) BLZ_TRY(operand(ops[i].name, ops[i].v, *ops[i].out, ops[i].max_count ? ops[i].max_count : n));
         if (!d_out) return BLZ_OK;
         char who[48];
         snprintf(who, sizeof who, "operand %s", out_name);
         BLZ_TRY(device_range(who, "d_ptr", d_out, out_words * 32, 16, out_words, "elements"));
-        for (const Operand& o : ops) {
+        for (size_t i = 0; i < count; ++i) {
+            const Operand& o = ops[i];
             if (!o.v || !o.v->d_ptr) continue;
             const char *lo = (const char*)o.v->d_ptr, *hi = lo + o.v->count * 32, *q = (const char*)d_out;
             if (q < hi && q + out_words * 32 > lo) return fail(BLZ_ERR_INVALID_PARAM, "%s overlaps the words of a d_ptr operand", out_name);
         }
         return BLZ_OK;
+    }
+    int resolve(std::initializer_list<Operand> ops, const char* out_name = nullptr, void* d_out = nullptr, uint64_t out_words = 1) {
+        return resolve(ops.begin(), ops.size(), out_name, d_out, out_words);
     }
 
     // A destination that may be the caller's device words (the multilinear ops): an operand's checks - a transform buffer, or
@@ -766,6 +770,49 @@ struct NttVecCall {
         return BLZ_OK;
     }
 };
+
+// What blz_ntt_sumcheck_step and blz_ntt_sumcheck_gate share, behind each one's checks of its gate: the shape of points, d_out
+// and r, the live length, begin, ONE resolve (the tables in order, then r, then d_out), the bind rules - with r every table is
+// folded in place, so none is periodic, no two meet in their first len words, r is outside the len / 2 words a table receives
+// and d_out outside a table's live words - and the enqueue with both written buffers.  tables: the k tables, none NULL, each with
+// its name in a message ("a" / "tables[1]") and the slot it resolves to; one, two: what stands in front of one name and of a pair
+// ("table ", "tables " / nothing).  dispatch(r's word, or nullptr) launches.
+// blz_ntt_vec_mle_round does not come here: its points range, its flags and its operand rule are its own, and it binds nothing.
+template <class Dispatch>
+int ntt_step_protocol(NttVecCall& call, const NttVecCall::Operand* tables, int k, const char* one, const char* two, const blz_vec_arg* r,
+                      uint32_t points, uint32_t max_points, uint64_t len, void* d_out, Dispatch&& dispatch) {
+    if (points > max_points) return fail(BLZ_ERR_INVALID_PARAM, "points %u is not in [0, %u]", points, max_points);
+    if (points == 0 && (!r || d_out)) return fail(BLZ_ERR_INVALID_PARAM, "points 0 is a bind alone: it takes r and a NULL d_out");
+    if (points > 0 && !d_out) return fail(BLZ_ERR_INVALID_PARAM, "null d_out");
+    if (r && (!r->d_ptr || r->count != 1))
+        return fail(BLZ_ERR_INVALID_PARAM, "a sumcheck step takes the challenge as one device word: r.d_ptr != NULL, r.count == 1");
+    BLZ_TRY(call.live_length(len));
+    if (r && points > 0 && len < 4) return fail(BLZ_ERR_INVALID_PARAM, "len %llu: a bind and a round need len >= 4", (unsigned long long)len);
+    BLZ_TRY(call.begin());
+    NttVecCall::Operand ops[BLZ_GATE_MAX_TABLES + 1];   // the tables and r; blz_ntt_sumcheck_step's four fit
+    NttVecArg vr{};
+    std::copy_n(tables, k, ops);
+    ops[k] = {"r", r, &vr};
+    BLZ_TRY(call.resolve(ops, (size_t)k + 1, "d_out", d_out, points));
+    int wbuf[2] = {-1, -1};
+    if (r) {
+        const uint64_t half = len >> 1;
+        for (int j = 0; j < k; ++j) {
+            const NttVecArg& tj = *ops[j].out;
+            if (tj.mask + 1 < len)
+                return fail(BLZ_ERR_INVALID_PARAM, "operand %s: %llu words, read periodically over len %llu: a periodic table cannot be folded in place", ops[j].name,
+                            (unsigned long long)(tj.mask + 1), (unsigned long long)len);
+            for (int i = 0; i < j; ++i)
+                if (NttVecCall::words_meet(ops[i].out->p, len, tj.p, len))
+                    return fail(BLZ_ERR_INVALID_PARAM, "%s%s and %s overlap in their first len words: each is folded in place", two, ops[i].name, ops[j].name);
+            if (NttVecCall::words_meet(vr.p, 1, tj.p, half)) return fail(BLZ_ERR_INVALID_PARAM, "r lies in the words %s%s receives", one, ops[j].name);
+            if (d_out && NttVecCall::words_meet(d_out, points, tj.p, len))
+                return fail(BLZ_ERR_INVALID_PARAM, "d_out lies in the live words of %s%s", one, ops[j].name);
+            if (!ops[j].v->d_ptr) wbuf[wbuf[0] < 0 ? 0 : 1] = (int)ops[j].v->buf;
+        }
+    }
+    return call.enqueue(wbuf[0], [&](uint32_t*) { return dispatch(r ? vr.p : nullptr); }, wbuf[1]);
+}
 }  // extern "C++"
 
 int blz_ntt_vec_op(blz_ntt* h, int op, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c) {
@@ -981,35 +1028,12 @@ int blz_ntt_sumcheck_step(blz_ntt* h, uint32_t gate, const blz_vec_arg* a, const
         if (tv[j]) return fail(BLZ_ERR_INVALID_PARAM, "a gate takes its tables as a, then b, then c, then d: %c is NULL while %c is set", 'a' + k, 'a' + j);
     if (gate == BLZ_GATE_R1CS ? k != 4 : (k < 1 || k > 3))
         return fail(BLZ_ERR_INVALID_PARAM, "%s, %d given", gate == BLZ_GATE_R1CS ? "BLZ_GATE_R1CS takes the four tables a, b, c, d" : "BLZ_GATE_PRODUCT takes 1 to 3 tables (d must be NULL)", k);
-    if (points > 4) return fail(BLZ_ERR_INVALID_PARAM, "points %u is not in [0, 4]", points);
-    if (points == 0 && (!r || d_out)) return fail(BLZ_ERR_INVALID_PARAM, "points 0 is a bind alone: it takes r and a NULL d_out");
-    if (points > 0 && !d_out) return fail(BLZ_ERR_INVALID_PARAM, "null d_out");
-    if (r && (!r->d_ptr || r->count != 1))
-        return fail(BLZ_ERR_INVALID_PARAM, "a sumcheck step takes the challenge as one device word: r.d_ptr != NULL, r.count == 1");
     NttVecCall call{h};
-    BLZ_TRY(call.live_length(len));
-    if (r && points > 0 && len < 4) return fail(BLZ_ERR_INVALID_PARAM, "len %llu: a bind and a round need len >= 4", (unsigned long long)len);
-    BLZ_TRY(call.begin());
-    NttVecArg vt[4]{}, vr{};
-    BLZ_TRY(call.resolve({{"a", a, &vt[0]}, {"b", b, &vt[1]}, {"c", c, &vt[2]}, {"d", d, &vt[3]}, {"r", r, &vr}}, "d_out", d_out, points));
-    int wbuf[2] = {-1, -1};
-    if (r) {
-        const uint64_t half = len >> 1;
-        for (int j = 0; j < k; ++j) {
-            if (vt[j].mask + 1 < len)
-                return fail(BLZ_ERR_INVALID_PARAM, "operand %c: %llu words, read periodically over len %llu: a periodic table cannot be folded in place", 'a' + j,
-                            (unsigned long long)(vt[j].mask + 1), (unsigned long long)len);
-            for (int i = 0; i < j; ++i)
-                if (NttVecCall::words_meet(vt[i].p, len, vt[j].p, len))
-                    return fail(BLZ_ERR_INVALID_PARAM, "tables %c and %c overlap in their first len words: each is folded in place", 'a' + i, 'a' + j);
-            if (NttVecCall::words_meet(vr.p, 1, vt[j].p, half)) return fail(BLZ_ERR_INVALID_PARAM, "r lies in the words table %c receives", 'a' + j);
-            if (d_out && NttVecCall::words_meet(d_out, points, vt[j].p, len))
-                return fail(BLZ_ERR_INVALID_PARAM, "d_out lies in the live words of table %c", 'a' + j);
-            if (!tv[j]->d_ptr) wbuf[wbuf[0] < 0 ? 0 : 1] = (int)tv[j]->buf;
-        }
-    }
-    return call.enqueue(wbuf[0], [&](uint32_t*) { return h->ops->sumcheck_step(h->stream, gate, 0, k, vt, r ? vr.p : nullptr, points, len, (uint32_t*)d_out, call.ws); },
-                        wbuf[1]);
+    NttVecArg vt[4]{};
+    const NttVecCall::Operand tables[4] = {{"a", a, &vt[0]}, {"b", b, &vt[1]}, {"c", c, &vt[2]}, {"d", d, &vt[3]}};
+    return ntt_step_protocol(call, tables, k, "table ", "tables ", r, points, 4, len, d_out, [&](const uint32_t* rw) {
+        return h->ops->sumcheck_step(h->stream, gate, 0, k, vt, rw, points, len, (uint32_t*)d_out, call.ws);
+    });
 }
 
 // The step for a caller-defined gate (ntt_gate.hip.hpp).  The description is checked and packed here - the longest term's
@@ -1046,37 +1070,16 @@ int blz_ntt_sumcheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_ar
         for (uint32_t j = 0; j < t.nfactors; ++j) g.term[m] |= (uint32_t)t.factor[j] << (8 + 4 * j);
     }
     g.close_k = longest + (gate->common >= 0 ? 1u : 0u);
-    if (points > BLZ_GATE_MAX_POINTS) return fail(BLZ_ERR_INVALID_PARAM, "points %u is not in [0, %d]", points, BLZ_GATE_MAX_POINTS);
-    if (points == 0 && (!r || d_out)) return fail(BLZ_ERR_INVALID_PARAM, "points 0 is a bind alone: it takes r and a NULL d_out");
-    if (points > 0 && !d_out) return fail(BLZ_ERR_INVALID_PARAM, "null d_out");
-    if (r && (!r->d_ptr || r->count != 1))
-        return fail(BLZ_ERR_INVALID_PARAM, "a sumcheck step takes the challenge as one device word: r.d_ptr != NULL, r.count == 1");
-    NttVecCall call{h};
-    BLZ_TRY(call.live_length(len));
-    if (r && points > 0 && len < 4) return fail(BLZ_ERR_INVALID_PARAM, "len %llu: a bind and a round need len >= 4", (unsigned long long)len);
-    BLZ_TRY(call.begin());
-    static const char* const names[BLZ_GATE_MAX_TABLES] = {"tables[0]", "tables[1]", "tables[2]", "tables[3]", "tables[4]",  "tables[5]",
-                                                           "tables[6]", "tables[7]", "tables[8]", "tables[9]", "tables[10]", "tables[11]"};
-    auto tab = [&](int i) { return NttVecCall::Operand{names[i], i < nt ? tables + i : nullptr, &g.t[i]}; };
-    NttVecArg vr{};
-    BLZ_TRY(call.resolve({tab(0), tab(1), tab(2), tab(3), tab(4), tab(5), tab(6), tab(7), tab(8), tab(9), tab(10), tab(11), {"r", r, &vr}}, "d_out", d_out, points));
-    int wbuf[2] = {-1, -1};
-    if (r) {
-        const uint64_t half = len >> 1;
-        for (int j = 0; j < nt; ++j) {
-            if (g.t[j].mask + 1 < len)
-                return fail(BLZ_ERR_INVALID_PARAM, "operand %s: %llu words, read periodically over len %llu: a periodic table cannot be folded in place", names[j],
-                            (unsigned long long)(g.t[j].mask + 1), (unsigned long long)len);
-            for (int i = 0; i < j; ++i)
-                if (NttVecCall::words_meet(g.t[i].p, len, g.t[j].p, len))
-                    return fail(BLZ_ERR_INVALID_PARAM, "%s and %s overlap in their first len words: each is folded in place", names[i], names[j]);
-            if (NttVecCall::words_meet(vr.p, 1, g.t[j].p, half)) return fail(BLZ_ERR_INVALID_PARAM, "r lies in the words %s receives", names[j]);
-            if (d_out && NttVecCall::words_meet(d_out, points, g.t[j].p, len))
-                return fail(BLZ_ERR_INVALID_PARAM, "d_out lies in the live words of %s", names[j]);
-            if (!tables[j].d_ptr) wbuf[wbuf[0] < 0 ? 0 : 1] = (int)tables[j].buf;
-        }
+    char name[BLZ_GATE_MAX_TABLES][16];
+    NttVecCall::Operand ops[BLZ_GATE_MAX_TABLES];
+    for (int j = 0; j < nt; ++j) {
+        snprintf(name[j], sizeof name[j], "tables[%d]", j);
+        ops[j] = {name[j], tables + j, &g.t[j]};
     }
-    return call.enqueue(wbuf[0], [&](uint32_t*) { return h->ops->sumcheck_gate(h->stream, g, r ? vr.p : nullptr, points, len, (uint32_t*)d_out, call.ws); }, wbuf[1]);
+    NttVecCall call{h};
+    return ntt_step_protocol(call, ops, nt, "", "", r, points, BLZ_GATE_MAX_POINTS, len, d_out, [&](const uint32_t* rw) {
+        return h->ops->sumcheck_gate(h->stream, g, rw, points, len, (uint32_t*)d_out, call.ws);
+    });
 }
 
 int blz_ntt_last_kernel_ms(blz_ntt* h, float* out) {

@@ -29,9 +29,7 @@
 //   R1CS as eq (+ Az Bz, - Cz) at 4 points: 8 + (4 + 2) + 4 = 18, the count of BLZ_GATE_R1CS.  The vanilla PLONK gate
 //   eq (qL a + qR b + qM a b - qO c + qC), 9 tables, F = 3, at 5 points: 18 + (5+2) + (5+2) + 10 + (5+2) + 4 + 5 = 58 per quad.
 //
-// REDUCTION and launch geometry: those of ntt_sumcheck_step_t - one block (len <= 1024 with r, <= 512 without) closes the sums
-//   and writes d_out itself, any other grid writes word t x blocks + block of the handle's scratch and k_mle_round_fin closes.
-//   Workspace: blocks x points words, blocks = min(work / 256, 2048) >= 2: at most 6 len / 512 < len <= n words.
+// REDUCTION, launch geometry and workspace: ntt_sumcheck.hip.hpp's (sc_plan, sc_finish), with points <= 6.
 #pragma once
 #include "ntt_sumcheck.hip.hpp"
 
@@ -176,21 +174,11 @@ __global__ __launch_bounds__(VEC_THREADS) void k_gate_round(uint32_t* out, NttGa
 // may be periodic.  out: `points` <= 6 words; ws: the handle's scratch
 template <class Fr>
 int ntt_sumcheck_gate_t(hipStream_t st, const NttGate& g, const uint32_t* r, uint32_t points, uint64_t len, uint32_t* out, uint32_t* ws) {
-    if (r && points == 0) {
-        for (uint32_t j = 0; j < g.ntables; ++j) BLZ_TRY(ntt_vec_mle_fold_t<Fr>(st, 0, const_cast<uint32_t*>(g.t[j].p), g.t[j], r, len));
-        return BLZ_OK;
-    }
-    const uint64_t work = r ? len >> 2 : len >> 1;   // quads, or pairs
-    uint64_t blocks = (work + VEC_THREADS - 1) / VEC_THREADS;   // a power of two: work is
-    if (blocks > VEC_MAX_BLOCKS) blocks = VEC_MAX_BLOCKS;
-    const int ls = fold_log2(blocks) + FOLD_LOG_THREADS;
-    const uint32_t direct = blocks == 1 ? 1u : 0u;
-    if (r) hipLaunchKernelGGL((k_gate_round<Fr, ScQuads>), dim3((unsigned)blocks), dim3(VEC_THREADS), 0, st, direct ? out : ws, g, r, work, ls, points, direct);
-    else hipLaunchKernelGGL((k_gate_round<Fr, ScPairs<false>>), dim3((unsigned)blocks), dim3(VEC_THREADS), 0, st, direct ? out : ws, g, r, work, ls, points, direct);
-    if (!direct)
-        hipLaunchKernelGGL(k_mle_round_fin<Fr>, dim3(1), dim3(VEC_THREADS), 0, st, out, (const uint32_t*)ws, (uint32_t)blocks, points, (int)g.close_k);
-    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
-    return BLZ_OK;
+    if (r && points == 0) return sc_bind_only<Fr>(st, (int)g.ntables, g.t, r, len);
+    const ScPlan p = sc_plan(r != nullptr, len);
+    const auto kernel = r ? &k_gate_round<Fr, ScQuads> : &k_gate_round<Fr, ScPairs<false>>;
+    hipLaunchKernelGGL(kernel, dim3(p.blocks), dim3(VEC_THREADS), 0, st, p.sums(out, ws), g, r, p.work, p.log_stride, points, p.direct);
+    return sc_finish<Fr>(st, p, out, ws, points, (int)g.close_k);
 }
 
 }  // namespace blz

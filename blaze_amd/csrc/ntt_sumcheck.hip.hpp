@@ -33,14 +33,17 @@
 //     at R1CS before a product's own temporaries.  The compiler reports 192 - 201 VGPRs for the R1CS bind and 167 - 170 at K = 3
 //     (two waves per SIMD), no scratch; asked for three waves (168) it spills 44 and 12 bytes per lane, so it is not asked.
 //
-// BIND ONLY  (points == 0: a sumcheck's last variable) K launches of k_mle_fold, in place, in the one enqueue.
+// BIND ONLY  (points == 0: a sumcheck's last variable) K launches of k_mle_fold, in place, in the one enqueue (sc_bind_only).
 //
-// REDUCTION  one fold_block_tree per point.  A call whose items fit one block - len <= 1024 with r, len <= 512 without - closes
-//   the sums there and writes d_out itself: no workspace, which small handles do not have (4 words need n >= 4).  Any other
-//   writes one partial per block and point, word t x blocks + block of the handle's scratch, and k_mle_round_fin, one block,
-//   folds and closes them.
-//   Workspace: blocks x points words with blocks = min(len / 1024, 2048) (len / 512 without r): at most 4 len / 512 < len <= n.
+// REDUCTION and launch geometry, of k_sc_round and of k_gate_round (ntt_gate.hip.hpp) alike: sc_plan and sc_finish.  One
+//   fold_block_tree per point.  A call whose items fit one block - len <= 1024 with r, len <= 512 without - closes the sums there
+//   and writes d_out itself: no workspace, which small handles do not have (4 words need n >= 4).  Any other writes one partial per
+//   block and point, word t x blocks + block of the handle's scratch, and k_mle_round_fin, one block, folds and closes them.
+//   Workspace: blocks x points words with blocks = min(len / 1024, 2048) (len / 512 without r) >= 2 and points <= 6 (a caller's
+//   gate; 4 here): at most 6 len / 512 < len <= n.
 #pragma once
+#include <algorithm>
+
 #include "ntt_mle.hip.hpp"
 
 namespace blz {
@@ -222,21 +225,41 @@ ScRoundKernel sc_round_kernel(bool bind, bool low) {
     return &k_sc_round<Fr, ScPairs<false>, GATE, K>;
 }
 
+// The launch of a round kernel over a call's items: work quads (bind) or pairs, blocks a power of two as work is, direct: one
+// block, which writes d_out itself
+struct ScPlan {
+    uint64_t work; unsigned blocks; int log_stride; uint32_t direct;
+    uint32_t* sums(uint32_t* out, uint32_t* ws) const { return direct ? out : ws; }   // where the round kernel writes
+};
+inline ScPlan sc_plan(bool bind, uint64_t len) {
+    const uint64_t work = bind ? len >> 2 : len >> 1;
+    const uint64_t blocks = std::min<uint64_t>((work + VEC_THREADS - 1) / VEC_THREADS, VEC_MAX_BLOCKS);
+    return {work, (unsigned)blocks, fold_log2(blocks) + FOLD_LOG_THREADS, blocks == 1 ? 1u : 0u};
+}
+
+// the bind alone: each of the k tables folded in place by vec_mle_fold's launcher
+template <class Fr>
+int sc_bind_only(hipStream_t st, int k, const NttVecArg* t, const uint32_t* r, uint64_t len) {
+    for (int j = 0; j < k; ++j) BLZ_TRY(ntt_vec_mle_fold_t<Fr>(st, 0, const_cast<uint32_t*>(t[j].p), t[j], r, len));
+    return BLZ_OK;
+}
+
+// behind the round kernel's launch: the partials in ws folded and closed into out unless the one block has done it
+template <class Fr>
+int sc_finish(hipStream_t st, const ScPlan& p, uint32_t* out, const uint32_t* ws, uint32_t points, int close_k) {
+    if (!p.direct) hipLaunchKernelGGL(k_mle_round_fin<Fr>, dim3(1), dim3(VEC_THREADS), 0, st, out, ws, (uint32_t)p.blocks, points, close_k);
+    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
+    return BLZ_OK;
+}
+
 // t: the gate's k tables (PRODUCT 1 .. 3, R1CS 4).  r != nullptr: every table holds at least len words, no two overlap, and
 // their first len / 2 words are written; points == 0: bind only (len >= 2), else len >= 4.  r == nullptr: round only, tables
 // may be periodic, 1 <= points; flags: MLE_LOW, honoured for PRODUCT without r alone.  out: `points` words; ws: the handle's scratch
 template <class Fr>
 int ntt_sumcheck_step_t(hipStream_t st, uint32_t gate, uint32_t flags, int k, const NttVecArg* t, const uint32_t* r, uint32_t points, uint64_t len,
                         uint32_t* out, uint32_t* ws) {
-    if (r && points == 0) {
-        for (int j = 0; j < k; ++j) BLZ_TRY(ntt_vec_mle_fold_t<Fr>(st, 0, const_cast<uint32_t*>(t[j].p), t[j], r, len));
-        return BLZ_OK;
-    }
-    const uint64_t work = r ? len >> 2 : len >> 1;   // quads, or pairs
-    uint64_t blocks = (work + VEC_THREADS - 1) / VEC_THREADS;   // a power of two: work is
-    if (blocks > VEC_MAX_BLOCKS) blocks = VEC_MAX_BLOCKS;
-    const int ls = fold_log2(blocks) + FOLD_LOG_THREADS;
-    const uint32_t direct = blocks == 1 ? 1u : 0u;
+    if (r && points == 0) return sc_bind_only<Fr>(st, k, t, r, len);
+    const ScPlan p = sc_plan(r != nullptr, len);
     const bool low = (flags & MLE_LOW) != 0;
     ScOperands tb{};
     for (int j = 0; j < k && j < SC_MAX_TABLES; ++j) tb.t[j] = t[j];
@@ -251,12 +274,8 @@ int ntt_sumcheck_step_t(hipStream_t st, uint32_t gate, uint32_t flags, int k, co
             default: return fail(BLZ_ERR_INVALID_PARAM, "a product gate takes 1 to %d tables", MLE_MAX_OPERANDS);
         }
     }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(VEC_THREADS), 0, st, direct ? out : ws, tb, r, work, ls, points, direct);
-    if (!direct)
-        hipLaunchKernelGGL(k_mle_round_fin<Fr>, dim3(1), dim3(VEC_THREADS), 0, st, out, (const uint32_t*)ws, (uint32_t)blocks, points,
-                           gate == SC_GATE_R1CS ? 3 : k);
-    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
-    return BLZ_OK;
+    hipLaunchKernelGGL(kernel, dim3(p.blocks), dim3(VEC_THREADS), 0, st, p.sums(out, ws), tb, r, p.work, p.log_stride, points, p.direct);
+    return sc_finish<Fr>(st, p, out, ws, points, gate == SC_GATE_R1CS ? 3 : k);
 }
 
 }  // namespace blz

@@ -16,6 +16,12 @@ def _read(*parts):
     return open(os.path.join(ROOT, *parts)).read()
 
 
+def function_body(text, head):
+    """A top-level function of a source text, from `head` (as "int name(") to its closing brace in column 0."""
+    body = text[text.index(head):]
+    return body[:body.index("\n}\n")]
+
+
 def tools_available() -> bool:
     return all(os.path.exists(os.path.join(LLVM, t)) for t in ("llvm-objcopy", "llvm-objdump", "llvm-readelf", "clang-offload-bundler"))
 

@@ -1,17 +1,11 @@
-"""What the tests of blz_ntt_sumcheck_gate share: the Python-integer reference of a caller-defined gate, the fold, the gate
-catalogue and the house input recipe (ntt_spmv_util._inputs: the edge words 0, 1, r - 1, r, r + 1, 2^256 - 1 first, unmasked
+"""What the tests of blz_ntt_sumcheck_gate share beyond tests/ntt_mle_util.py: the Python-integer reference of a caller-defined
+gate, the gate catalogue and the house input recipe (ntt_spmv_util._inputs: the edge words 0, 1, r - 1, r, r + 1, 2^256 - 1 first, unmasked
 random 256-bit words behind)."""
 import ctypes as C
 
 import blaze_amd
 from blaze_amd._lib import BlzSumGate, BlzVecArg
 from ntt_spmv_util import _inputs
-from ntt_vec_util import _words
-
-
-def fold_ref(a, r, rr, length):
-    half = length // 2
-    return [(a[p] + rr * (a[p + half] - a[p])) % r for p in range(half)]
 
 
 def gate_value(v, terms, common, r):
@@ -35,12 +29,6 @@ def sum_gate_ref(tables, terms, common, r, length, points):
             s += gate_value([a[p % len(a)] + t * (a[(p + half) % len(a)] - a[p % len(a)]) for a in tables], terms, common, r)
         out.append(s % r)
     return out
-
-
-def challenges(r, seed):
-    """0, 1, r - 1, r + 1 and a random word >= r"""
-    big = next(v for v in _words(seed, 16) if v >= r)
-    return [0, 1, r - 1, r + 1, big]
 
 
 def gate_inputs(r, ntables, length, seed):
@@ -86,16 +74,3 @@ def raw_gate(cl, gate, tables, r, points, length, d_out):
     vr = r if isinstance(r, BlzVecArg) or r is None else cl._vec_arg(r)
     return blaze_amd.lib().blz_ntt_sumcheck_gate(cl._h, None if gate is None else C.byref(gate), arr, None if vr is None else C.byref(vr),
                                                  points, length, d_out)
-
-
-def interpolate(s, x, r):
-    """The polynomial through (t, s[t]), t < len(s), at x"""
-    acc = 0
-    for i, si in enumerate(s):
-        num = den = 1
-        for j in range(len(s)):
-            if j != i:
-                num = num * (x - j) % r
-                den = den * (i - j) % r
-        acc += si * num * pow(den, -1, r)
-    return acc % r

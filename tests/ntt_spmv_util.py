@@ -26,6 +26,13 @@ def row_ptr_of(lengths, first=0):
     return rp
 
 
+def sparse_rows(rng, r, rows, width, per_row=(1, 4)):
+    """Random sparse rows over the columns [0, width): (row_ptr, col, val)"""
+    lengths = [rng.randint(*per_row) for _ in range(rows)]
+    rp = row_ptr_of(lengths)
+    return rp, [rng.randrange(width) for _ in range(rp[-1])], [rng.randrange(r) for _ in range(rp[-1])]
+
+
 def spmv_ref(x, r, n, col, row_ptr=None, val=None, rows=None):
     """dst as a list of n integers: dst[p] = sum val[k] x[col[k] % count] % r over row_ptr[p] <= k < row_ptr[p + 1] for
     p < rows, 0 above.  row_ptr None: row p is nonzero p.  val None: coefficients 1.  rows None: all the rows there are."""

@@ -12,7 +12,8 @@ import blaze_amd
 from blaze_amd import DeviceBuffer, DriverClientError
 from blaze_amd._lib import BlzVecArg
 from blaze_amd.ingo_ntt import NTTClient, NTTInput
-from ntt_spmv_util import _inputs, _u32, row_ptr_of, spmv_ref
+from ntt_mle_util import challenges, fill as _fill, fold_ref, interpolate, pairs   # `fill` is a local name in the tests below
+from ntt_spmv_util import _inputs, _u32, sparse_rows, spmv_ref
 from ntt_vec_util import FIELDS, TOP, _client, _dev, _pack, _unpack, _word, _words
 from oracle import pyref
 
@@ -21,24 +22,8 @@ SUM, DOT = NTTClient.FOLD_SUM, NTTClient.FOLD_DOT
 LOGNS = [1, 6, 9, 11]   # one pair; less than a block; one block; several blocks (the round: through the workspace)
 
 
-def _fill(nwords, seed):
-    return random.Random(seed).randbytes(32 * nwords)
-
-
-def _pairs(a, length, low):
-    """(lo, hi) of every output position; a is read periodically, as the op reads `count` device words."""
-    half, cnt = length // 2, len(a)
-    if low:
-        return [(a[(2 * p) % cnt], a[(2 * p + 1) % cnt]) for p in range(half)]
-    return [(a[p % cnt], a[(p + half) % cnt]) for p in range(half)]
-
-
-def fold_ref(a, r, rr, length, low):
-    return [(lo + rr * (hi - lo)) % r for lo, hi in _pairs(a, length, low)]
-
-
 def round_ref(tables, r, length, points, low):
-    prs = [_pairs(a, length, low) for a in tables]
+    prs = [pairs(a, length, low) for a in tables]
     out = []
     for t in range(points):
         s = 0
@@ -59,12 +44,6 @@ def eq_ref(tau, r):
     return tab
 
 
-def _challenges(r, seed):
-    """0, 1, r - 1, r + 1 and a random word >= r"""
-    big = next(v for v in _words(seed, 16) if v >= r)
-    return [0, 1, r - 1, r + 1, big]
-
-
 @pytest.mark.parametrize("field", FIELDS)
 @pytest.mark.parametrize("logn", LOGNS)
 def test_fold_against_python_integers(gpu, field, logn):
@@ -77,7 +56,7 @@ def test_fold_against_python_integers(gpu, field, logn):
     a = _inputs(r, n, 900 * logn + len(field))
     ab = _pack(a)
     cl = _client(field, logn)
-    rs = _challenges(r, logn)
+    rs = challenges(r, logn)
     drs = [cl.scalar(v) for v in rs]
     src, dstw = _dev(ab), DeviceBuffer(0, 32 * n)
     periodic = [(_dev(ab[:32 * c]), a[:c]) for c in (1, 4) if c <= n]
@@ -323,25 +302,6 @@ def test_eq_second_turn_of_the_tile_loop(gpu):
         d.free()
 
 
-def _sparse_rows(rng, r, rows, width, per_row=(1, 4)):
-    lengths = [rng.randint(*per_row) for _ in range(rows)]
-    rp = row_ptr_of(lengths)
-    return rp, [rng.randrange(width) for _ in range(rp[-1])], [rng.randrange(r) for _ in range(rp[-1])]
-
-
-def _interpolate(s, x, r):
-    """The polynomial through (t, s[t]), t < len(s), at x"""
-    acc = 0
-    for i, si in enumerate(s):
-        num = den = 1
-        for j in range(len(s)):
-            if j != i:
-                num = num * (x - j) % r
-                den = den * (i - j) % r
-        acc += si * num * pow(den, -1, r)
-    return acc % r
-
-
 def _sumcheck(field, low):
     """A satisfied random R1CS of 2^10 constraints (a witness of 2n words, the upper half chosen so that A z o B z = C z) through
     vec_spmv to A z, B z, C z; eq(tau); then ten rounds of sumcheck for sum_p eq(p) (Az(p) Bz(p) - Cz(p)) = 0: the round polynomial
@@ -352,7 +312,7 @@ def _sumcheck(field, low):
     r = pyref.CURVES[field]["r"]
     rng = random.Random(len(field) + 40 + low)
     z = [rng.randrange(r) for _ in range(n)]
-    A, B, Cf = (_sparse_rows(rng, r, n, n) for _ in range(3))
+    A, B, Cf = (sparse_rows(rng, r, n, n) for _ in range(3))
     az, bz, cf = (spmv_ref(z, r, n, mat[1], mat[0], mat[2]) for mat in (A, B, Cf))
     z += [(az[p] * bz[p] - cf[p]) % r for p in range(n)]
     rpC, colC, valC = [], [], []
@@ -391,7 +351,7 @@ def _sumcheck(field, low):
         for table in (0, 1, d_cz, d_eq):
             cl.vec_mle_fold(table, table, dc, length, low); cl.wait_result()
         dc.free()
-        claim = _interpolate(s, c, r)
+        claim = interpolate(s, c, r)
     finals = [_unpack(cl.result(0))[0], _unpack(cl.result(1))[0], _word(d_cz), _word(d_eq)]
     assert claim == finals[3] * (finals[0] * finals[1] - finals[2]) % r
     # each word is the original table at the challenges: DOT(table, eq(challenges)) on the device; the top variable was bound first

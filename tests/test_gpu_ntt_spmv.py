@@ -13,8 +13,8 @@ import blaze_amd
 from blaze_amd import DriverClientError
 from blaze_amd._lib import BlzVecArg, BlzVecCsr
 from blaze_amd.ingo_ntt import NTTClient, NTTInput, NttInit
-from ntt_spmv_util import (TILE, _inputs, _u32, random_cols, random_vals, row_ptr_of, shaped_lengths, split_rows, spmv_ref,
-                           spmv_want)
+from ntt_spmv_util import (TILE, _inputs, _u32, random_cols, random_vals, row_ptr_of, shaped_lengths, sparse_rows, split_rows,
+                           spmv_ref, spmv_want)
 from ntt_vec_util import FIELDS, _client, _dev, _pack, _transform, _words
 from oracle import pyref
 
@@ -22,8 +22,8 @@ pytestmark = pytest.mark.gpu
 MUL, MULSUB, SSUM = NTTClient.MUL, NTTClient.MULSUB, NTTClient.SCAN_SUM
 
 
-def _fill(n, seed):
-    return _pack([v | 1 for v in _words(seed, n)])   # no zero word: a position the op must zero shows
+def _fill(n, seed):   # not ntt_mle_util.fill (random bytes): n words none of which is zero, so that a position the op must zero shows
+    return _pack([v | 1 for v in _words(seed, n)])
 
 
 def _run(cl, dst, x, col, row_ptr=None, val=None, **kw):
@@ -190,13 +190,6 @@ def test_second_turn_of_the_grid_stride_loop(gpu):
         d.free()
 
 
-def _sparse_rows(rng, r, rows, width, per_row=(1, 4)):
-    """Random sparse rows over the columns [0, width): (row_ptr, col, val)"""
-    lengths = [rng.randint(*per_row) for _ in range(rows)]
-    rp = row_ptr_of(lengths)
-    return rp, [rng.randrange(width) for _ in range(rp[-1])], [rng.randrange(r) for _ in range(rp[-1])]
-
-
 @pytest.mark.parametrize("field", FIELDS)
 def test_r1cs_instance_end_to_end(gpu, field):
     """n = 2^10 constraints over a witness of 2n words.  A, B and the free part of C are random sparse over the first n
@@ -209,7 +202,7 @@ def test_r1cs_instance_end_to_end(gpu, field):
     r = pyref.CURVES[field]["r"]
     rng = random.Random(len(field) + 10)
     w = [rng.randrange(r) for _ in range(n)]
-    A, B, Cf = (_sparse_rows(rng, r, n, n) for _ in range(3))
+    A, B, Cf = (sparse_rows(rng, r, n, n) for _ in range(3))
     # a long row in A: row 5 takes 300 nonzeros
     rpA, colA, valA = A
     k = rpA[5]

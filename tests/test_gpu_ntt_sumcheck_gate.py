@@ -13,8 +13,8 @@ import blaze_amd
 from blaze_amd import DeviceBuffer, DriverClientError
 from blaze_amd._lib import BlzVecArg
 from blaze_amd.ingo_ntt import NTTClient, NTTInput
-from ntt_gate_util import (CATALOGUE, PLONK_TERMS, challenges, fold_ref, gate_inputs, gate_value, interpolate, make_gate, raw_gate,
-                           sum_gate_ref)
+from ntt_gate_util import CATALOGUE, PLONK_TERMS, gate_inputs, gate_value, make_gate, raw_gate, sum_gate_ref
+from ntt_mle_util import challenges, check_order_of_checks, fill, fold_ref, interpolate
 from ntt_spmv_util import _inputs
 from ntt_vec_util import FIELDS, _client, _dev, _pack, _unpack, _word, _words
 from oracle import pyref
@@ -26,10 +26,6 @@ R1CS, PRODUCT = NTTClient.GATE_R1CS, NTTClient.GATE_PRODUCT
 # pairs: len = 512 is exactly one block, 1024 and 2048 take the workspace
 SIZES = [(2, 4), (6, 64), (10, 1024), (11, 2048), (11, 512)]
 MAXP = 6
-
-
-def _fill(nwords, seed):
-    return random.Random(seed).randbytes(32 * nwords)
 
 
 def _bytes_of(cl, t):
@@ -69,14 +65,14 @@ def test_bind_and_round_against_python_integers(gpu, field, logn, length):
         which = (turn + logn + len(field)) % 5
         rr, dr = rs[which], drs[which]
         vals = gate_inputs(r, nt, length, 7000 * logn + 100 * turn + len(field))
-        before = [_pack(v) + _fill(n - length, turn * 12 + j) for j, v in enumerate(vals)]
+        before = [_pack(v) + fill(n - length, turn * 12 + j) for j, v in enumerate(vals)]
         buffers = [turn % nt, (turn + 3) % nt] if nt > 1 else ([0] if turn % 2 == 0 else [])
         folded = [fold_ref(v, r, rr, length) for v in vals]
         want = sum_gate_ref(folded, terms, common, r, half, MAXP)
         gate = make_gate(nt, terms, common)
         for points in range(1, MAXP + 1):
             tabs = _place(cl, words, buffers, before)
-            gfill = _fill(MAXP + 2, turn + 50 + points)
+            gfill = fill(MAXP + 2, turn + 50 + points)
             guard.upload(gfill)
             assert raw_gate(cl, gate, tabs, dr, points, length, guard.ptr + 32) == 0, blaze_amd.lib().blz_last_error_message()
             cl.wait_result()
@@ -117,7 +113,7 @@ def test_round_only(gpu, field, logn, length):
     for turn, (name, tt, vv, terms, common) in enumerate(cases):
         want = sum_gate_ref(vv, terms, common, r, length, MAXP)
         for points in (1 + turn % MAXP, 1 + (turn + 3) % MAXP):
-            out = _dev(_fill(points, points) + mark)
+            out = _dev(fill(points, points) + mark)
             got = cl.sumcheck_gate(tt, terms, common, points=points, length=length, out=out)
             cl.wait_result()
             assert got is out and bytes(out.download()) == _pack(want[:points]) + mark, (name, points)
@@ -359,6 +355,66 @@ def test_refusals(gpu):
     assert bytes(cl.result(0)) == ab and bytes(out.download()) == mark
     cl.close()
     for d in (words, words2, one_word, out, big):
+        d.free()
+
+
+def test_order_of_checks(gpu):
+    """A call wrong in two ways reports the earlier check, in blz_ntt_sumcheck_step's order behind the description's own: the
+    description, points, d_out, r's shape, the live length, len >= 4 for a bind with a round, an op in flight, the operands, then
+    per table a periodic one, an overlap, r in the words it receives.  Checks that read the same argument cannot all meet in one
+    call (points above 6 and points 0; points 0 and a NULL d_out with points): each is set against the nearest check it can meet."""
+    field, logn = "BLS381", 3
+    n = 1 << logn
+    r = pyref.CURVES[field]["r"]
+    L = blaze_amd.lib()
+    a, b = _inputs(r, n, 83), _inputs(r, n, 84)
+    ab, bb = _pack(a), _pack(b)
+    cl = _client(field, logn)
+    words, big, one_word = _dev(bb), _dev(bytes(32 * 12)), _dev((7).to_bytes(32, "little"))
+    mark = bytes(range(1, 161))
+    out, s = _dev(mark), DeviceBuffer(0, 128)   # 5 words; the op in flight's own
+    V = BlzVecArg
+    B0, B1, W, R = V(None, 0, 0, 0), V(None, 1, 0, n), V(words.ptr, 0, 0, n), V(one_word.ptr, 0, 0, 1)
+    P4, BAD = V(words.ptr, 0, 0, 4), V(None, 2, 0, 0)
+    # two tables that overlap in part, and r in the words the second receives but not in the first's
+    LO, HI, R5 = V(big.ptr, 0, 0, 8), V(big.ptr + 32 * 4, 0, 0, 8), V(big.ptr + 32 * 5, 0, 0, 1)
+    o = out.ptr
+    ONE, AB = [(1, [0])], [(1, [0, 1])]
+    g1, g2, g0 = make_gate(1, ONE, None), make_gate(2, AB, None), make_gate(2, AB, None)
+    g0.ntables = 0
+
+    def step(gate, tables, rr, points, length, d_out):
+        return raw_gate(cl, gate, tables, rr, points, length, d_out)
+
+    def good():
+        cl.set_data(NTTInput(0, ab)); cl.set_data(NTTInput(1, bb)); out.upload(mark)
+        assert step(g2, [B0, B1], R, 3, n, o + 32) == 0, L.blz_last_error_message()
+        cl.wait_result()
+        fa, fb = fold_ref(a, r, 7, n), fold_ref(b, r, 7, n)
+        assert bytes(cl.result(0)) == _pack(fa) + ab[16 * n:] and bytes(cl.result(1)) == _pack(fb) + bb[16 * n:]
+        assert bytes(out.download()) == mark[:32] + _pack(sum_gate_ref([fa, fb], AB, None, r, n // 2, 3)) + mark[128:]
+
+    cases = [
+        ("ntables, points", (lambda: step(g0, [B0, B1], R, 7, n, o), "gate: ntables 0 is not in [1, 12]", False), (lambda: step(g1, [B0], R, 7, n, o), "points 7 is not in [0, 6]", False)),
+        ("points, null d_out", (lambda: step(g1, [B0], R, 7, n, None), "points 7 is not in [0, 6]", False), (lambda: step(g1, [B0], R, 3, n, None), "null d_out", False)),
+        ("points 0, r", (lambda: step(g1, [B0], B1, 0, n, o), "points 0 is a bind alone", False), (lambda: step(g1, [B0], B1, 2, n, o), "r.d_ptr != NULL, r.count == 1", False)),
+        ("null d_out, r", (lambda: step(g1, [B0], B1, 3, n, None), "null d_out", False), (lambda: step(g1, [B0], B1, 3, n, o), "r.d_ptr != NULL, r.count == 1", False)),
+        ("r, len", (lambda: step(g1, [B0], B1, 2, 12, o), "r.d_ptr != NULL, r.count == 1", False), (lambda: step(g1, [B0], R, 2, 12, o), "len 12: the live length is 2^m", False)),
+        ("len, len >= 4", (lambda: step(g1, [B0], R, 2, 3, o), "len 3: the live length is 2^m", False), (lambda: step(g1, [B0], R, 2, 2, o), "a bind and a round need len >= 4", False)),
+        ("len >= 4, in flight", (lambda: step(g1, [B0], R, 2, 2, o), "a bind and a round need len >= 4", True), (lambda: step(g1, [B0], R, 2, n, o), "already running", True)),
+        ("in flight, operand", (lambda: step(g1, [V(None, 0, 7, 0)], R, 2, n, o), "already running", True),
+         (lambda: step(g1, [V(None, 0, 7, 0)], R, 2, n, o), "operand tables[0]: reserved must be 0", False)),
+        ("operand, periodic", (lambda: step(g2, [P4, BAD], R, 3, 8, o), "operand tables[1]: buf must be 0 or 1", False),
+         (lambda: step(g2, [P4, B1], R, 3, 8, o), "operand tables[0]: 4 words, read periodically over len 8", False)),
+        ("periodic, overlap", (lambda: step(g2, [W, P4], R, 3, 8, o), "operand tables[1]: 4 words, read periodically over len 8", False),
+         (lambda: step(g2, [W, W], R, 3, 8, o), "tables[0] and tables[1] overlap", False)),
+        ("overlap, r in the words written", (lambda: step(g2, [LO, HI], R5, 3, 8, o), "tables[0] and tables[1] overlap", False),
+         (lambda: step(g2, [B0, HI], R5, 3, 8, o), "r lies in the words tables[1] receives", False)),
+    ]
+    check_order_of_checks(cl, cases, lambda: cl.vec_mle_round(words, out=s), good)
+    assert bytes(words.download()) == bb and bytes(big.download()) == bytes(32 * 12) and _word(one_word) == 7
+    cl.close()
+    for d in (words, big, one_word, out, s):
         d.free()
 
 

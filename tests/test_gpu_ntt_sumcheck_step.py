@@ -14,7 +14,8 @@ import blaze_amd
 from blaze_amd import DeviceBuffer, DriverClientError
 from blaze_amd._lib import BlzVecArg
 from blaze_amd.ingo_ntt import NTTClient, NTTInput
-from ntt_spmv_util import _inputs, _u32, row_ptr_of, spmv_ref
+from ntt_mle_util import challenges, check_order_of_checks, fill, fold_ref, interpolate
+from ntt_spmv_util import _inputs, _u32, sparse_rows, spmv_ref
 from ntt_vec_util import FIELDS, _client, _dev, _pack, _unpack, _word, _words
 from oracle import pyref
 
@@ -24,15 +25,6 @@ GATES = [(PRODUCT, 1), (PRODUCT, 2), (PRODUCT, 3), (R1CS, 4)]
 # (log n, len): one quad; less than a block; 256 quads, exactly one block: d_out written directly; two blocks: workspace and
 # finish; a live length below n
 SIZES = [(2, 4), (6, 64), (10, 1024), (11, 2048), (11, 512)]
-
-
-def _fill(nwords, seed):
-    return random.Random(seed).randbytes(32 * nwords)
-
-
-def fold_ref(a, r, rr, length):
-    half = length // 2
-    return [(a[p] + rr * (a[p + half] - a[p])) % r for p in range(half)]
 
 
 def gate_ref(tables, r, length, points, gate):
@@ -52,12 +44,6 @@ def gate_ref(tables, r, length, points, gate):
                 s += term
         out.append(s % r)
     return out
-
-
-def _challenges(r, seed):
-    """0, 1, r - 1, r + 1 and a random word >= r"""
-    big = next(v for v in _words(seed, 16) if v >= r)
-    return [0, 1, r - 1, r + 1, big]
 
 
 def _ref(v):
@@ -83,7 +69,7 @@ def test_bind_and_round_against_python_integers(gpu, field, logn, length):
     n = 1 << logn
     r = pyref.CURVES[field]["r"]
     cl = _client(field, logn)
-    rs = _challenges(r, logn)
+    rs = challenges(r, logn)
     drs = [cl.scalar(v) for v in rs]
     words = [DeviceBuffer(0, 32 * n) for _ in range(4)]
     guard = DeviceBuffer(0, 32 * 6)
@@ -97,7 +83,7 @@ def test_bind_and_round_against_python_integers(gpu, field, logn, length):
                 vals = [v[j:] + v[:j] for j, v in enumerate(vals)]
             before, tabs, w = [], [], 0
             for j, place in enumerate(places):
-                b = _pack(vals[j]) + _fill(n - length, turn * 4 + j)
+                b = _pack(vals[j]) + fill(n - length, turn * 4 + j)
                 before.append(b)
                 if place == "w":
                     words[w].upload(b)
@@ -106,7 +92,7 @@ def test_bind_and_round_against_python_integers(gpu, field, logn, length):
                 else:
                     cl.set_data(NTTInput(place, b))
                     tabs.append(place)
-            gfill = _fill(6, turn + 50)
+            gfill = fill(6, turn + 50)
             guard.upload(gfill)
             assert _raw_step(cl, gate, tabs, dr, points, length, guard.ptr + 32) == 0, blaze_amd.lib().blz_last_error_message()
             cl.wait_result()
@@ -144,7 +130,7 @@ def test_round_only(gpu, field, logn, length):
     guard = bytes(range(100, 132))
     for points in (1, 2, 3, 4):
         names = combos[points - 1]
-        out = _dev(_fill(points, points) + guard)
+        out = _dev(fill(points, points) + guard)
         got = cl.sumcheck_step([tab[x][0] for x in names], gate=R1CS, points=points, length=length, out=out)
         cl.wait_result()
         assert got is out
@@ -170,7 +156,7 @@ def test_bind_only(gpu, field):
     n = 1 << logn
     r = pyref.CURVES[field]["r"]
     cl = _client(field, logn)
-    rs = _challenges(r, 3)
+    rs = challenges(r, 3)
     for turn, length in enumerate((2, n, 2, n)):
         rr = rs[(turn + 3) % 5]
         dr = cl.scalar(rr)
@@ -366,6 +352,63 @@ def test_refusals(gpu):
         d.free()
 
 
+def test_order_of_checks(gpu):
+    """A call wrong in two ways reports the earlier check: gate, points, d_out, r's shape, the live length, len >= 4 for a bind
+    with a round, an op in flight, the operands, then per table a periodic one, an overlap, r in the words it receives.  Checks
+    that read the same argument cannot all meet in one call (points above 4 and points 0; points 0 and a NULL d_out with points):
+    each is set against the nearest check it can meet."""
+    field, logn = "BLS381", 3
+    n = 1 << logn
+    r = pyref.CURVES[field]["r"]
+    L = blaze_amd.lib()
+    a, b = _inputs(r, n, 81), _inputs(r, n, 82)
+    ab, bb = _pack(a), _pack(b)
+    cl = _client(field, logn)
+    words, big, one_word = _dev(bb), _dev(bytes(32 * 12)), _dev((7).to_bytes(32, "little"))
+    mark = bytes(range(1, 161))
+    out, s = _dev(mark), DeviceBuffer(0, 128)   # 5 words; the op in flight's own
+    V = BlzVecArg
+    B0, B1, W, R = V(None, 0, 0, 0), V(None, 1, 0, n), V(words.ptr, 0, 0, n), V(one_word.ptr, 0, 0, 1)
+    P4, BAD = V(words.ptr, 0, 0, 4), V(None, 2, 0, 0)
+    # two tables that overlap in part, and r in the words the second receives but not in the first's
+    LO, HI, R5 = V(big.ptr, 0, 0, 8), V(big.ptr + 32 * 4, 0, 0, 8), V(big.ptr + 32 * 5, 0, 0, 1)
+    o = out.ptr
+
+    def step(gate, x, y, rr, points, length, d_out):
+        return L.blz_ntt_sumcheck_step(cl._h, gate, _ref(x), _ref(y), None, None, _ref(rr), points, length, d_out)
+
+    def good():
+        cl.set_data(NTTInput(0, ab)); cl.set_data(NTTInput(1, bb)); out.upload(mark)
+        assert step(PRODUCT, B0, B1, R, 3, n, o + 32) == 0, L.blz_last_error_message()
+        cl.wait_result()
+        fa, fb = fold_ref(a, r, 7, n), fold_ref(b, r, 7, n)
+        assert bytes(cl.result(0)) == _pack(fa) + ab[16 * n:] and bytes(cl.result(1)) == _pack(fb) + bb[16 * n:]
+        assert bytes(out.download()) == mark[:32] + _pack(gate_ref([fa, fb], r, n // 2, 3, PRODUCT)) + mark[128:]
+
+    P = PRODUCT
+    cases = [
+        ("gate, points", (lambda: step(2, B0, None, R, 5, n, o), "unknown gate 2", False), (lambda: step(P, B0, None, R, 5, n, o), "points 5 is not in [0, 4]", False)),
+        ("points, null d_out", (lambda: step(P, B0, None, R, 5, n, None), "points 5 is not in [0, 4]", False), (lambda: step(P, B0, None, R, 3, n, None), "null d_out", False)),
+        ("points 0, r", (lambda: step(P, B0, None, B1, 0, n, o), "points 0 is a bind alone", False), (lambda: step(P, B0, None, B1, 2, n, o), "r.d_ptr != NULL, r.count == 1", False)),
+        ("null d_out, r", (lambda: step(P, B0, None, B1, 3, n, None), "null d_out", False), (lambda: step(P, B0, None, B1, 3, n, o), "r.d_ptr != NULL, r.count == 1", False)),
+        ("r, len", (lambda: step(P, B0, None, B1, 2, 12, o), "r.d_ptr != NULL, r.count == 1", False), (lambda: step(P, B0, None, R, 2, 12, o), "len 12: the live length is 2^m", False)),
+        ("len, len >= 4", (lambda: step(P, B0, None, R, 2, 3, o), "len 3: the live length is 2^m", False), (lambda: step(P, B0, None, R, 2, 2, o), "a bind and a round need len >= 4", False)),
+        ("len >= 4, in flight", (lambda: step(P, B0, None, R, 2, 2, o), "a bind and a round need len >= 4", True), (lambda: step(P, B0, None, R, 2, n, o), "already running", True)),
+        ("in flight, operand", (lambda: step(P, V(None, 0, 7, 0), None, R, 2, n, o), "already running", True),
+         (lambda: step(P, V(None, 0, 7, 0), None, R, 2, n, o), "operand a: reserved must be 0", False)),
+        ("operand, periodic", (lambda: step(P, P4, BAD, R, 3, 8, o), "operand b: buf must be 0 or 1", False),
+         (lambda: step(P, P4, B1, R, 3, 8, o), "operand a: 4 words, read periodically over len 8", False)),
+        ("periodic, overlap", (lambda: step(P, W, P4, R, 3, 8, o), "operand b: 4 words, read periodically over len 8", False), (lambda: step(P, W, W, R, 3, 8, o), "tables a and b overlap", False)),
+        ("overlap, r in the words written", (lambda: step(P, LO, HI, R5, 3, 8, o), "tables a and b overlap", False),
+         (lambda: step(P, B0, HI, R5, 3, 8, o), "r lies in the words table b receives", False)),
+    ]
+    check_order_of_checks(cl, cases, lambda: cl.vec_mle_round(words, out=s), good)
+    assert bytes(words.download()) == bb and bytes(big.download()) == bytes(32 * 12) and _word(one_word) == 7
+    cl.close()
+    for d in (words, big, one_word, out, s):
+        d.free()
+
+
 def test_in_flight_rules(gpu):
     """A step that writes BOTH buffers in flight: neither can be read, written or exchanged and nothing else starts.  A round alone
     writes none: both can be read, the ones it reads cannot be written.  reset drops the op."""
@@ -445,25 +488,6 @@ def test_in_flight_rules(gpu):
         d.free()
 
 
-def _sparse_rows(rng, r, rows, width, per_row=(1, 4)):
-    lengths = [rng.randint(*per_row) for _ in range(rows)]
-    rp = row_ptr_of(lengths)
-    return rp, [rng.randrange(width) for _ in range(rp[-1])], [rng.randrange(r) for _ in range(rp[-1])]
-
-
-def _interpolate(s, x, r):
-    """The polynomial through (t, s[t]), t < len(s), at x"""
-    acc = 0
-    for i, si in enumerate(s):
-        num = den = 1
-        for j in range(len(s)):
-            if j != i:
-                num = num * (x - j) % r
-                den = den * (i - j) % r
-        acc += si * num * pow(den, -1, r)
-    return acc % r
-
-
 @pytest.mark.parametrize("field", FIELDS)
 def test_sumcheck_end_to_end(gpu, field):
     """A satisfied random R1CS of 2^10 constraints through vec_spmv to Az, Bz, Cz, then the sumcheck for
@@ -476,7 +500,7 @@ def test_sumcheck_end_to_end(gpu, field):
     r = pyref.CURVES[field]["r"]
     rng = random.Random(len(field) + 90)
     z = [rng.randrange(r) for _ in range(n)]
-    A, B, Cf = (_sparse_rows(rng, r, n, n) for _ in range(3))
+    A, B, Cf = (sparse_rows(rng, r, n, n) for _ in range(3))
     az, bz, cf = (spmv_ref(z, r, n, mat[1], mat[0], mat[2]) for mat in (A, B, Cf))
     z += [(az[p] * bz[p] - cf[p]) % r for p in range(n)]
     rpC, colC, valC = [], [], []
@@ -522,7 +546,7 @@ def test_sumcheck_end_to_end(gpu, field):
         c = rng.getrandbits(256)
         challenges.append(c)
         dc = cl.scalar(c)
-        claim = _interpolate(s, c, r)
+        claim = interpolate(s, c, r)
     assert cl.sumcheck_step(fused, dc, gate=R1CS, points=0, length=2) is None
     cl.wait_result()
     for t in (u_eq, u_az, u_bz, u_cz):
@@ -532,13 +556,13 @@ def test_sumcheck_end_to_end(gpu, field):
     assert claim == finals[0] * (finals[1] * finals[2] - finals[3]) % r
     # each final word is the original table at the challenges (the top variable was bound first), in integers
 
-    def at_challenges(table):
+    def atchallenges(table):
         for c in challenges:
             h = len(table) // 2
             table = [(table[p] + c * (table[p + h] - table[p])) % r for p in range(h)]
         return table[0]
 
-    assert finals == [at_challenges(t) for t in (eq0, az, bz, cz)]
+    assert finals == [atchallenges(t) for t in (eq0, az, bz, cz)]
     cl.close()
     for d in arrays + [dz, d_cz, d_eq, point, u_eq, u_az, u_bz, u_cz, s_dev, s1, s2, dc]:
         d.free()

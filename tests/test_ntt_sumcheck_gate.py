@@ -10,7 +10,7 @@ import re
 import pytest
 
 import blaze_amd
-from isa_util import ROOT, _read, kernel_scratch, kernel_vgprs, tools_available
+from isa_util import ROOT, _read, function_body, kernel_scratch, kernel_vgprs, tools_available
 
 LIB = os.environ.get("BLAZE_HIP_LIB") or os.path.join(ROOT, "blaze_amd", "lib", "libblaze_hip.so")
 
@@ -109,18 +109,26 @@ def test_kernels_in_their_own_header_behind_one_slot():
     src = _read("blaze_amd", "csrc", "ntt_gate.hip.hpp")
     kernels = re.findall(r"template\s*<([^>]*)>\s*__global__[^\n;{]*?\bvoid\s+(\w+)\s*\(", src)
     assert kernels == [("class Fr, class Source", "k_gate_round")], kernels   # the gate is not a template parameter
-    # the bind alone, the block reduction and the finish are the existing step's, not copies
-    assert "ntt_vec_mle_fold_t<Fr>(" in src and "k_mle_round_fin<Fr>" in src and "sc_block_sums<Fr>(" in src and "fold_block_tree" not in src
+    # the bind alone, the block reduction, the launch plan and the finish are the existing step's, not copies: the launcher
+    # chooses between the two instantiations, launches, and calls ntt_sumcheck.hip.hpp for the rest
+    assert "sc_block_sums<Fr>(" in src and "fold_block_tree" not in src
+    launcher = function_body(re.sub(r"//[^\n]*", "", src), "int ntt_sumcheck_gate_t(")
+    assert all(launcher.count(f) == 1 for f in ("sc_plan(", "sc_bind_only<Fr>(", "sc_finish<Fr>(", "hipLaunchKernelGGL("))
+    assert "k_gate_round<Fr, ScQuads>" in launcher and "k_gate_round<Fr, ScPairs<false>>" in launcher
+    for elsewhere in ("k_mle_round_fin<Fr>", "ntt_vec_mle_fold_t<Fr>(", "VEC_MAX_BLOCKS", "hipGetLastError", "fold_log2"):
+        assert elsewhere not in src, elsewhere
     statements = re.sub(r"//[^\n]*", "", src)
     for banned in ("atomic", "alloc", "volatile", "__shared__ int", "__threadfence"):   # no atomics, no flags, no allocation
         assert banned not in statements, banned
     ntt = _read("blaze_amd", "csrc", "ntt.hip")
-    body = ntt[ntt.index(f"int {NAME}("):]
-    body = body[:body.index("\n}\n")]
-    # the protocol is the existing step's, by the same helpers: nothing about pointers is checked here
-    assert body.count("call.resolve(") == 1 and "call.begin()" in body and "call.live_length(" in body and "call.enqueue(" in body
-    assert "NttVecCall::words_meet(" in body and "hipPointerGetAttributes" not in body and "hipMemGetAddressRange" not in body
-    assert "h->ops->sumcheck_gate(" in body and body.index('"null handle"') < body.index("gate->")
+    # the protocol is the existing step's, by ONE call to the function the two share (tests/test_ntt_sumcheck_step.py pins what
+    # it holds): nothing about pointers, overlaps or what is in flight is checked here
+    body = function_body(ntt, f"int {NAME}(")
+    assert body.count("ntt_step_protocol(") == 1 and "h->ops->sumcheck_gate(" in body
+    for elsewhere in ("hipPointerGetAttributes", "hipMemGetAddressRange", "call.resolve(", "words_meet(", "call.begin()", "call.enqueue("):
+        assert elsewhere not in body, elsewhere
+    assert body.index('"null handle"') < body.index("gate->") < body.index("ntt_step_protocol(")
+    assert ntt.index("int ntt_step_protocol(") < ntt.index("int blz_ntt_sumcheck_step(")
 
 
 def test_documented_where_the_other_ops_are():

@@ -11,7 +11,7 @@ import re
 import pytest
 
 import blaze_amd
-from isa_util import ROOT, _read, count, disassemble_library, function_instructions, kernel_scratch, kernel_vgprs, tools_available
+from isa_util import ROOT, _read, count, disassemble_library, function_body, function_instructions, kernel_scratch, kernel_vgprs, tools_available
 
 LIB = os.environ.get("BLAZE_HIP_LIB") or os.path.join(ROOT, "blaze_amd", "lib", "libblaze_hip.so")
 
@@ -68,25 +68,41 @@ def test_kernels_in_their_own_header_behind_the_field_ops():
     assert "o.sumcheck_step = " in impl and re.search(r"\(\*sumcheck_step\)\s*\(\s*hipStream_t\s+st\s*,", eng)
     src = _read("blaze_amd", "csrc", "ntt_sumcheck.hip.hpp")
     # a bind alone is vec_mle_fold's launcher, not a second copy; every round polynomial - vec_mle_round's too - is ONE kernel over
-    # a pair source and a gate, and the block reduction of its accumulators is written once
-    assert "ntt_vec_mle_fold_t<Fr>(" in src and "k_mle_round_fin<Fr>" in src
+    # a pair source and a gate, and the block reduction of its accumulators is written once.  The launch plan, the bind alone and
+    # the finish are written once too, for this launcher and the caller-defined gate's: one launch of k_mle_round_fin, one cap
+    statements = re.sub(r"//[^\n]*", "", src)
+    assert statements.count("ntt_vec_mle_fold_t<Fr>(") == 1 and statements.count("k_mle_round_fin<Fr>") == 1
+    assert "hipLaunchKernelGGL(k_mle_round_fin<Fr>," in function_body(statements, "int sc_finish(")
+    assert statements.count("VEC_MAX_BLOCKS") == 1 and "VEC_MAX_BLOCKS" in function_body(statements, "inline ScPlan sc_plan(")
+    launcher = function_body(statements, "int ntt_sumcheck_step_t(")
+    assert all(launcher.count(f) == 1 for f in ("sc_plan(", "sc_bind_only<Fr>(", "sc_finish<Fr>(", "hipLaunchKernelGGL("))
+    assert "hipGetLastError" not in launcher and "fold_log2" not in launcher
     both = _read("blaze_amd", "csrc", "ntt_mle.hip.hpp") + src
     kernels = re.findall(r"template\s*<([^>]*)>\s*__global__[^\n;{]*?\bvoid\s+(\w+)\s*\(", both)
     assert sorted(k for _, k in kernels) == ["k_mle_eq", "k_mle_fold", "k_mle_round_fin", "k_sc_round"], kernels
     assert [k for params, k in kernels if "GATE" in params] == ["k_sc_round"], kernels
     assert both.count("fold_block_tree<Fr>(x, acc[t]") == 1
     assert "o.vec_mle_round" not in impl and "(*vec_mle_round)" not in eng
-    statements = re.sub(r"//[^\n]*", "", src)
     for banned in ("atomic", "alloc", "volatile"):   # no atomics, no flags, no allocation
         assert banned not in statements, banned
     ntt = _read("blaze_amd", "csrc", "ntt.hip")
     assert ntt.index("int blz_ntt_stream(") < ntt.index(f"int {NAME}(")
     assert ntt.count("hipMemGetAddressRange(") == 1 and ntt.count("is not a power of two") == 1
     assert ntt.count("hipPointerGetAttributes(&at") == 1
-    body = ntt[ntt.index(f"int {NAME}("):]
-    body = body[:body.index("\n}\n")]
-    assert body.count("call.resolve(") == 1 and "call.begin()" in body and "call.live_length(" in body
-    assert "hipPointerGetAttributes" not in body and "h->ops->sumcheck_step(" in body
+    # the entry point checks its gate and its tables' order, then makes ONE call to the protocol it shares with
+    # blz_ntt_sumcheck_gate; the in-place and in-flight rules live there and nowhere else
+    body = function_body(ntt, f"int {NAME}(")
+    assert body.count("ntt_step_protocol(") == 1 and "h->ops->sumcheck_step(" in body
+    for elsewhere in ("hipPointerGetAttributes", "hipMemGetAddressRange", "call.resolve(", "words_meet(", "call.begin()", "call.enqueue("):
+        assert elsewhere not in body, elsewhere
+    shared = function_body(ntt, "int ntt_step_protocol(")
+    assert shared.count("resolve(") == 1 and "call.begin()" in shared and "call.live_length(" in shared and shared.count("call.enqueue(") == 1
+    assert shared.index("call.live_length(") < shared.index("call.begin()") < shared.index("call.resolve(") < shared.index("call.enqueue(")
+    assert shared.count("NttVecCall::words_meet(") == 3 and "hipPointerGetAttributes" not in shared and "hipMemGetAddressRange" not in shared
+    for stem in ('"points 0 is a bind alone', "a bind and a round need len", "a periodic table cannot be folded in place", "overlap in their first len words",
+                 '"r lies in the words %s%s receives"', '"d_out lies in the live words of %s%s"', "a sumcheck step takes the challenge as one device word"):
+        assert ntt.count(stem) == 1 and stem in shared, stem
+    assert "tab(" not in ntt and '"tables[0]"' not in ntt
     # the handle records a second written buffer beside the one the existing ops record
     assert "in_flight_buf2" in ntt and "int in_flight_buf = -1;" in ntt
 
