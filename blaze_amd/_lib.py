@@ -63,6 +63,11 @@ class BlzVecCsr(C.Structure):
     _fields_ = [("d_row_ptr", C.c_void_p), ("d_col", C.c_void_p), ("d_val", C.c_void_p), ("rows", C.c_uint64), ("nnz", C.c_uint64)]
 
 
+class BlzVecScatter(C.Structure):
+    """struct blz_vec_scatter (include/blaze_hip.h): the nonzeros blz_ntt_vec_scatter adds up, index arrays in device memory."""
+    _fields_ = [("d_idx", C.c_void_p), ("d_src", C.c_void_p), ("d_val", C.c_void_p), ("nnz", C.c_uint64), ("reserved", C.c_uint64)]
+
+
 # every exported symbol of include/blaze_hip.h: name -> (restype, argtypes)
 _u8p = C.c_void_p
 _SIGS = {
@@ -139,6 +144,7 @@ _SIGS = {
     "blz_ntt_vec_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_horner": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_gather": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecView)]),
+    "blz_ntt_vec_scatter": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecScatter)]),
     "blz_ntt_vec_spmv": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecCsr)]),
     "blz_ntt_vec_mle_fold": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_uint64]),
     "blz_ntt_vec_mle_round": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_uint32,

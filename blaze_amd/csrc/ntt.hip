@@ -644,8 +644,8 @@ int blz_ntt_reset(blz_ntt* h) {
     return BLZ_OK;
 }
 
-// Ops on the transform buffers (include/blaze_hip.h: blz_ntt_vec_op, _reduce, _scan, _horner, _gather, _spmv, _mle_*; kernels and their workspace:
-// ntt_vec.hip.hpp, ntt_fold.hip.hpp, ntt_horner.hip.hpp, ntt_gather.hip.hpp, ntt_spmv.hip.hpp, ntt_mle.hip.hpp).  An op runs like a transform: compute stream, ev0 .. ev1, finished by
+// Ops on the transform buffers (include/blaze_hip.h: blz_ntt_vec_op, _reduce, _scan, _horner, _gather, _scatter, _spmv, _mle_*; kernels and their workspace:
+// ntt_vec.hip.hpp, ntt_fold.hip.hpp, ntt_horner.hip.hpp, ntt_gather.hip.hpp, ntt_scatter.hip.hpp, ntt_spmv.hip.hpp, ntt_mle.hip.hpp).  An op runs like a transform: compute stream, ev0 .. ev1, finished by
 // blz_ntt_wait_result.  Everything is checked before anything is enqueued and nothing waits for the device.  The workspace is
 // `scratch`, n x 32 bytes that only a transform or an op of this handle uses - and none can be in flight.  An entry point
 // checks its own arguments, then walks this protocol: begin, resolve, enqueue.
@@ -933,6 +933,36 @@ int blz_ntt_vec_spmv(blz_ntt* h, size_t buf_dst, const blz_vec_arg* x, const blz
         if (csr || m->nnz == 0) BLZ_HIP(hipMemsetAsync(dst, 0, ntt_bytes(h), h->stream), BLZ_ERR_UNKNOWN);
         if (m->nnz == 0 || m->rows == 0) return BLZ_OK;
         return h->ops->vec_spmv(h->stream, dst, vx, m->d_row_ptr, m->d_col, (const uint32_t*)m->d_val, m->rows, m->nnz, call.n, call.ws);
+    });
+}
+
+// The other way round: a nonzero names the position it is added to (ntt_scatter.hip.hpp).  The arrays are the caller's device
+// memory, checked as pointers like the matrix above; the destination is the accumulator and `scratch` its upper half, so x may
+// not name buf_dst.  The kernels' dispatch zeroes what its mode accumulates into; without a nonzero the zeros are the result.
+int blz_ntt_vec_scatter(blz_ntt* h, size_t buf_dst, const blz_vec_arg* x, const blz_vec_scatter* s) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (!s) return fail(BLZ_ERR_INVALID_PARAM, "a scatter-add takes a scatter s");
+    if (buf_dst > 1) return fail(BLZ_ERR_INVALID_PARAM, "buf_dst must be 0 or 1");
+    if (s->reserved != 0) return fail(BLZ_ERR_INVALID_PARAM, "scatter s: reserved must be 0");
+    if (s->nnz > (1ull << 31)) return fail(BLZ_ERR_INVALID_PARAM, "scatter s: nnz %llu is above 2^31", (unsigned long long)s->nnz);
+    if (!s->d_idx && s->nnz > 0) return fail(BLZ_ERR_INVALID_PARAM, "scatter s: d_idx is NULL with nnz %llu", (unsigned long long)s->nnz);
+    if (s->d_src && !x) return fail(BLZ_ERR_INVALID_PARAM, "scatter s: d_src is given without operand x, whose words it selects");
+    NttVecCall call{h};
+    BLZ_TRY(call.begin());
+    NttVecArg vx{};
+    BLZ_TRY(call.resolve({{"x", x, &vx, 1ull << NTT_MAX_LOG}}));
+    const uint32_t* const dst_words = h->buf[buf_dst].as<uint32_t>();
+    if (x && vx.p < dst_words + call.n * 8 && dst_words < vx.p + (vx.mask + 1) * 8)
+        return fail(BLZ_ERR_INVALID_PARAM, "operand x names or overlaps buffer %zu, the destination: a scatter-add cannot run in place", buf_dst);
+    if (s->nnz > 0) BLZ_TRY(call.device_range("scatter s", "d_idx", s->d_idx, s->nnz * 4, 4, s->nnz, "entries"));
+    if (s->d_src && s->nnz > 0) BLZ_TRY(call.device_range("scatter s", "d_src", s->d_src, s->nnz * 4, 4, s->nnz, "entries"));
+    if (s->d_val && s->nnz > 0) BLZ_TRY(call.device_range("scatter s", "d_val", s->d_val, s->nnz * 32, 16, s->nnz, "elements"));
+    return call.enqueue((int)buf_dst, [&](uint32_t* dst) -> int {
+        if (s->nnz == 0) {
+            BLZ_HIP(hipMemsetAsync(dst, 0, ntt_bytes(h), h->stream), BLZ_ERR_UNKNOWN);
+            return BLZ_OK;
+        }
+        return h->ops->vec_scatter(h->stream, dst, vx, s->d_idx, s->d_src, (const uint32_t*)s->d_val, s->nnz, call.n, call.ws);
     });
 }
 

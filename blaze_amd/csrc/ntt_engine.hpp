@@ -137,6 +137,12 @@ struct NttFieldOps {
     // val == nullptr: coefficients 1.  dst must NOT overlap x's words
     int (*vec_spmv)(hipStream_t st, uint32_t* dst, NttVecArg x, const uint32_t* row_ptr, const uint32_t* col, const uint32_t* val,
                     uint64_t rows, uint64_t nnz, uint64_t n, uint32_t* ws);
+    // Scatter-add (blz_ntt_vec_scatter; kernels, the accumulators' layout and the workspace: ntt_scatter.hip.hpp): dst[t] = sum
+    // over k < nnz with (idx[k] & (n - 1)) == t of val[k] x[(src ? src[k] : k) & x.mask], 0 where no nonzero points; every
+    // position of dst is written.  x.p == nullptr: every x word is 1 (and src is nullptr); val == nullptr: coefficients 1;
+    // both: the histogram of idx.  1 <= nnz <= 2^31.  dst must NOT overlap x's words
+    int (*vec_scatter)(hipStream_t st, uint32_t* dst, NttVecArg x, const uint32_t* idx, const uint32_t* src, const uint32_t* val,
+                       uint64_t nnz, uint64_t n, uint32_t* ws);
     // Multilinear tables (blz_ntt_vec_mle_fold / _eq; kernels and the workspace's layout: ntt_mle.hip.hpp).  len = 2^m, 2 <= len,
     // is the live length; flags: BLZ_MLE_LOW.  None of them writes past the words named here.  blz_ntt_vec_mle_round has no entry
     // of its own: it is sumcheck_step below with BLZ_GATE_PRODUCT, no r and its flags.

@@ -9,6 +9,7 @@
 #include "ntt_horner.hip.hpp"
 #include "ntt_gather.hip.hpp"
 #include "ntt_spmv.hip.hpp"
+#include "ntt_scatter.hip.hpp"
 #include "ntt_mle.hip.hpp"
 #include "ntt_sumcheck.hip.hpp"
 #include "ntt_gate.hip.hpp"
@@ -525,6 +526,7 @@ NttFieldOps make_ntt_ops() {
     o.vec_horner = &ntt_vec_horner_t<Fr>;
     o.vec_gather = &ntt_vec_gather_t<Fr>;
     o.vec_spmv = &ntt_vec_spmv_t<Fr>;
+    o.vec_scatter = &ntt_vec_scatter_t<Fr>;
     o.vec_mle_fold = &ntt_vec_mle_fold_t<Fr>;
     o.vec_mle_eq = &ntt_vec_mle_eq_t<Fr>;
     o.sumcheck_step = &ntt_sumcheck_step_t<Fr>;

@@ -6,7 +6,7 @@ import enum
 from dataclasses import dataclass
 from typing import Optional
 
-from ._lib import GATE_MAX_FACTORS, GATE_MAX_TABLES, GATE_MAX_TERMS, BlzSumGate, BlzVecArg, BlzVecCsr, BlzVecView, DeviceBuffer, buf_ptr, check, lib
+from ._lib import GATE_MAX_FACTORS, GATE_MAX_TABLES, GATE_MAX_TERMS, BlzSumGate, BlzVecArg, BlzVecCsr, BlzVecScatter, BlzVecView, DeviceBuffer, buf_ptr, check, lib
 from .driver_client import DriverClient, DriverPrimitive
 
 NTT_LOG_SIZE = 27  # ntt_data.rs:65: NTT_SIZE = 2^27
@@ -228,6 +228,29 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         zeros above them - n coefficients into a 4n client.  A vec_gather with length = m."""
         self.vec_gather(dst, a, offset=0, stride=1, length=a.nbytes // NTT_WORD_SIZE)
         self._vec_keep = (a,)
+
+    def vec_scatter(self, dst: int, idx: DeviceBuffer, x=None, val: Optional[DeviceBuffer] = None, src: Optional[DeviceBuffer] = None,
+                    nnz: Optional[int] = None) -> None:
+        """Scatter-add (blz_ntt_vec_scatter): transform buffer `dst`[t] = sum over k < nnz with idx[k] mod n == t of
+        val[k] x[src(k) mod count], src(k) = src[k] or, without `src`, k; a position no nonzero names becomes 0.  `idx` and `src`
+        are uint32 DeviceBuffers (nnz = idx.nbytes / 4 entries unless `nnz` says less), `val` 32-byte words (None: every
+        coefficient is 1).  `x` is the other transform buffer or a DeviceBuffer of count = nbytes / 32 words (a power of two up
+        to 2^27; one word: a scalar), None: every x word is 1 - and then `src` must be None; it may not name `dst`.  Without x
+        and val it is the histogram of idx (vec_count).  With idx = col, src = the row of each nonzero and x = y it is the
+        transposed sparse product A^T y.  Exact in the field: two runs give the same bytes.  Finished by wait_result()."""
+        vx = self._vec_arg(x)
+        if nnz is None:
+            nnz = idx.nbytes // 4 if idx is not None else 0
+        s = BlzVecScatter(None if idx is None else idx.ptr, None if src is None else src.ptr, None if val is None else val.ptr, int(nnz), 0)
+        check(lib().blz_ntt_vec_scatter(self._h, dst, None if vx is None else C.byref(vx), C.byref(s)))
+        self._vec_keep = (x, idx, src, val)
+
+    def vec_count(self, dst: int, idx: DeviceBuffer, nnz: Optional[int] = None) -> None:
+        """Multiplicities: transform buffer `dst`[t] = the number of entries k < nnz of the uint32 DeviceBuffer `idx` with
+        idx[k] mod n == t, as a field element - the column m of a lookup argument beside the looked-up column vec_index makes
+        from the same indices.  A vec_scatter without x and val."""
+        self.vec_scatter(dst, idx, nnz=nnz)
+        self._vec_keep = (idx,)
 
     def vec_spmv(self, dst: int, x, col: DeviceBuffer, row_ptr: Optional[DeviceBuffer] = None, val: Optional[DeviceBuffer] = None,
                  rows: Optional[int] = None, nnz: Optional[int] = None, row0: int = 0) -> None:

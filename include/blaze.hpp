@@ -287,6 +287,15 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
         const blz_vec_arg a = words(d_ptr, count);
         vec_gather(dst, &a, view(0, 1, count));
     }
+    // scatter-add (blz_ntt_vec_scatter): buffer dst[t] = sum over k < nnz with d_idx[k] mod n == t of val[k] x[src(k) mod count],
+    // src(k) = d_src ? d_src[k] : k; x null: ones (d_src null too), d_val null: coefficients 1; x may not name dst.  With
+    // d_idx = col, d_src = the row of each nonzero and x = y: the transposed sparse product.  vec_count: dst[t] = the number of
+    // entries of d_idx that name t, the multiplicities of a lookup argument
+    static blz_vec_scatter scatter(const uint32_t* d_idx, const uint32_t* d_src, const void* d_val, uint64_t nnz) {
+        return blz_vec_scatter{d_idx, d_src, d_val, nnz, 0};
+    }
+    void vec_scatter(size_t dst, const blz_vec_arg* x, const blz_vec_scatter& s) { check(blz_ntt_vec_scatter(h_, dst, x, &s)); }
+    void vec_count(size_t dst, const uint32_t* d_idx, uint64_t nnz) { vec_scatter(dst, nullptr, scatter(d_idx, nullptr, nullptr, nnz)); }
     // sparse matrix times vector (blz_ntt_vec_spmv): buffer dst[p] = sum over the nonzeros k of row p of val[k] x[col[k] mod count],
     // 0 for an empty row and above rows; x may not name dst.  csr(row_ptr, col, val, rows, nnz) builds the struct from device
     // pointers (val null: coefficients 1).  vec_index: dst[p] = x[col[p] mod count] (times val[p]), the data-dependent gather

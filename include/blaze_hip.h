@@ -431,7 +431,7 @@ typedef struct blz_vec_arg {
     uint32_t buf;        /* 0 | 1, read only when d_ptr == NULL */
     uint32_t reserved;   /* must be 0 */
     uint64_t count;      /* d_ptr != NULL: number of 32-byte elements, a power of two, 1 <= count <= n (the source of
-                            blz_ntt_vec_gather and blz_ntt_vec_spmv: <= 2^27); position p of the op reads element p & (count - 1).
+                            blz_ntt_vec_gather, _scatter and _spmv: <= 2^27); position p of the op reads element p & (count - 1).
                             d_ptr == NULL: 0 or n */
 } blz_vec_arg;
 int blz_ntt_vec_op(blz_ntt* h, int op, size_t buf_dst, const blz_vec_arg* a, const blz_vec_arg* b, const blz_vec_arg* c);
@@ -529,6 +529,49 @@ typedef struct blz_vec_view {
     uint64_t len;      /* positions p < len read the source, positions len <= p < n become 0; len <= n */
 } blz_vec_view;
 int blz_ntt_vec_gather(blz_ntt* h, size_t buf_dst, const blz_vec_arg* a, const blz_vec_view* v);
+/* Scatter-add on resident buffers: the one op in which a nonzero names the position it is ADDED TO - every other op computes a
+ * destination word from the sources that word names.  Not injective and data-dependent, so no inverse table turns it into a
+ * gather: the multiplicity column m[t] = #{p : idx[p] = t} of a lookup argument (logUp, Lasso-style memory checking; the
+ * indices depend on the witness), and the transposed sparse product A^T y of Spartan's second sumcheck, A(r_x, .) = A^T eq(r_x, .):
+ * dst[col[k]] += val[k] * y[row(k)].  Over the handle's field, by buffer POSITION (the BLZ_NTT_BITREV_* flags and the coset shift
+ * play no part), with n = 2^log_size:
+ *   dst[t] = sum over k < nnz with (idx[k] mod n) == t of val[k] * x[src(k) mod count]   for every t < n
+ *   src(k) = d_src ? d_src[k] : k
+ *   Without d_val every coefficient is 1; without x every x word is 1; without both it is the histogram: dst[t] is the number
+ *   of nonzeros that name t, as a field element.  A position no nonzero names becomes 0.
+ *   Values: every word of x and of val is any 256-bit value and counts as its residue; every output word is canonical,
+ *   little-endian.  The result is exact in the field and does not depend on the order in which the device adds: two runs give
+ *   the same bytes.
+ *   x: NULL - ones, and then d_src must be NULL too - or a transform buffer (d_ptr == NULL) or `count` device words, checked as
+ *   for blz_ntt_vec_gather: count is a power of two up to 2^27 and may be below or above n; it is read at src(k) & (count - 1), so
+ *   a one-word x is a scalar.  x may NOT name buf_dst (nor may its device words overlap that buffer): the destination is the
+ *   accumulator.
+ *   Indices: idx[k] is taken modulo n and src[k] modulo count (an AND each).  The host never reads the arrays: whatever bytes
+ *   they hold, no memory outside the arrays, the destination buffer and the handle's scratch is touched.
+ *   Bounds: nnz <= 2^31; nnz = 0 is valid and writes zeros.  The workspace is the handle's scratch (n x 32 bytes); nothing is
+ *   allocated.
+ *   Pointers: d_idx and d_src are 4-byte aligned device memory of the handle's device with nnz * 4 bytes inside one allocation;
+ *   d_val is 16-byte aligned with nnz * 32 bytes.
+ *   Cost: the limbs of a term are added into 64-bit integer accumulators with the device's atomic adds, two 64-byte requests at
+ *   the memory side per nonzero (one 4-byte add for the histogram); a destination of n <= 1024 (histogram: n <= 16384) is
+ *   accumulated in on-chip memory first ("Scatter-add").
+ *   Protocol: that of blz_ntt_vec_spmv.  Everything is checked before anything is enqueued; the op runs on the compute stream
+ *   and the call returns without waiting for the device; blz_ntt_wait_result finishes it, blz_ntt_last_kernel_ms then reports
+ *   it, blz_ntt_reset drops it.  While it is in flight buf_dst may not be read, written or exchanged, a buffer that is only read
+ *   may be read, and every transform, blz_ntt_set_coset and op on the buffers is refused (as blz_ntt_vec_scatter is while any of
+ *   those is in flight).  Memory behind the pointers stays valid and unwritten until blz_ntt_wait_result returns.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing: null handle (before any other argument is looked at), null s, buf_dst > 1,
+ *   reserved != 0, nnz > 2^31, null d_idx with nnz > 0, d_src given without x, a bad pointer (alignment, not device memory of the
+ *   handle's device, the array running past its allocation), x naming or overlapping buf_dst, an op in flight, and any operand
+ *   error of blz_ntt_vec_op with the count bound raised to 2^27. */
+typedef struct blz_vec_scatter {
+    const uint32_t* d_idx;     /* nnz entries: nonzero k is added to position idx[k] mod n (an AND) */
+    const uint32_t* d_src;     /* NULL: nonzero k reads x[k mod count]; else nnz entries, x[src[k] mod count] */
+    const void*     d_val;     /* NULL: every coefficient is 1; else nnz 32-byte words */
+    uint64_t        nnz;       /* <= 2^31; 0 is valid and writes zeros */
+    uint64_t        reserved;  /* must be 0 */
+} blz_vec_scatter;             /* 40 bytes */
+int blz_ntt_vec_scatter(blz_ntt* h, size_t buf_dst, const blz_vec_arg* x, const blz_vec_scatter* s);
 /* Sparse matrix-vector products on resident buffers: a sparse matrix in CSR form times a resident vector, into a transform
  * buffer - the first step of a prover, which turns a witness w into vectors on the evaluation domain: A w, B w, C w of an R1CS
  * (one row per constraint, a few nonzeros per row, a tail of very long rows), the wire columns a[p] = w[ia[p]] of PLONK, the

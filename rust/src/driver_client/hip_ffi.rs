@@ -36,6 +36,17 @@ pub struct BlzVecView {
     pub stride: u64,
     pub len: u64,
 }
+/// `struct blz_vec_scatter`: the nonzeros `blz_ntt_vec_scatter` adds up, index arrays in device memory.  `d_src` null: nonzero k
+/// reads x\[k mod count\]; `d_val` null: every coefficient is 1; `reserved` must be 0.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct BlzVecScatter {
+    pub d_idx: *const u32,
+    pub d_src: *const u32,
+    pub d_val: *const c_void,
+    pub nnz: u64,
+    pub reserved: u64,
+}
 /// `struct blz_vec_csr`: the sparse matrix `blz_ntt_vec_spmv` multiplies by, CSR arrays in device memory.  `d_row_ptr` null: row p
 /// holds nonzero p alone (`rows` == `nnz`); `d_val` null: every coefficient is 1.
 #[repr(C)]
@@ -165,6 +176,7 @@ extern "C" {
     pub fn blz_ntt_vec_scan(h: *mut BlzNtt, op: c_int, flags: u32, buf_dst: usize, a: *const BlzVecArg, d_total: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_horner(h: *mut BlzNtt, flags: u32, buf_dst: usize, a: *const BlzVecArg, z: *const BlzVecArg, d_total: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_gather(h: *mut BlzNtt, buf_dst: usize, a: *const BlzVecArg, v: *const BlzVecView) -> c_int;
+    pub fn blz_ntt_vec_scatter(h: *mut BlzNtt, buf_dst: usize, x: *const BlzVecArg, s: *const BlzVecScatter) -> c_int;
     pub fn blz_ntt_vec_spmv(h: *mut BlzNtt, buf_dst: usize, x: *const BlzVecArg, m: *const BlzVecCsr) -> c_int;
     pub fn blz_ntt_vec_mle_fold(h: *mut BlzNtt, flags: u32, dst: *const BlzVecArg, a: *const BlzVecArg, r: *const BlzVecArg, len: u64) -> c_int;
     pub fn blz_ntt_vec_mle_round(h: *mut BlzNtt, flags: u32, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg, points: u32,

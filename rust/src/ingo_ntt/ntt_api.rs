@@ -218,6 +218,30 @@ impl NTTClient {
         self.vec_gather(dst, VecOperand::Words { d_ptr, count }, 0, 1, count)
     }
 
+    /// Scatter-add (blz_ntt_vec_scatter): transform buffer `dst`\[t\] = the sum over k < `nnz` with `d_idx`\[k\] mod n == t of
+    /// val\[k\] x\[src(k) mod count\], src(k) = `d_src`\[k\] or, with a null `d_src`, k; a position no nonzero names becomes 0.
+    /// `x` None: every x word is 1 (and `d_src` must be null); a null `d_val`: every coefficient is 1; both: the histogram of
+    /// `d_idx` (`vec_count`).  With `d_idx` the columns, `d_src` the row of each nonzero and `x` = y it is the transposed
+    /// sparse product.  `x` may not name `dst`.  Exact in the field: two runs give the same bytes.
+    ///
+    /// # Safety
+    /// As for `vec_op`; the three arrays are device memory of the client's device that stays valid and unwritten until
+    /// `wait_result` returns.
+    pub unsafe fn vec_scatter(&self, dst: usize, x: Option<VecOperand>, d_idx: *const u32, d_src: *const u32,
+                              d_val: *const std::os::raw::c_void, nnz: u64) -> Result<()> {
+        let (rx, s) = (x.map(|v| v.raw()), BlzVecScatter { d_idx, d_src, d_val, nnz, reserved: 0 });
+        check(blz_ntt_vec_scatter(self.h, dst, rx.as_ref().map_or(std::ptr::null(), |r| r as *const BlzVecArg), &s))
+    }
+
+    /// Multiplicities: transform buffer `dst`\[t\] = the number of entries k < `nnz` of `d_idx` with `d_idx`\[k\] mod n == t, as a
+    /// field element.  A `vec_scatter` without x and coefficients.
+    ///
+    /// # Safety
+    /// As for `vec_scatter`.
+    pub unsafe fn vec_count(&self, dst: usize, d_idx: *const u32, nnz: u64) -> Result<()> {
+        self.vec_scatter(dst, None, d_idx, std::ptr::null(), std::ptr::null(), nnz)
+    }
+
     /// Sparse matrix times vector (blz_ntt_vec_spmv): transform buffer `dst`\[p\] = the sum over the nonzeros k of row p
     /// (`d_row_ptr`\[p\] <= k < `d_row_ptr`\[p + 1\]) of val\[k\] x\[col\[k\] mod count\] for p < `rows`, 0 for an empty row and
     /// for `rows` <= p < n.  `x` is the other transform buffer or `count` device words (a power of two up to 2^27); it may not
