@@ -197,6 +197,8 @@ _AUX_SIGS = {
     "blz_test_ec_op": (C.c_int, [C.c_int, C.c_int, C.c_int, _u8p, _u8p, _u8p, _u8p, _u8p, C.c_size_t]),
     "blz_test_msm_tail_plan": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8),
                                          C.c_char_p, C.c_size_t]),
+    "blz_test_msm_sort_plan": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_char_p, C.c_size_t]),
     "blz_test_law_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     "blz_test_law_op": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _u8p, _u8p, C.c_size_t]),
     "blz_test_rr_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint32)]),

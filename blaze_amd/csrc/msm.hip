@@ -2,10 +2,9 @@
 // bitstream behind src/ingo_msm/msm_hw_code.rs:6-54 computes; kernels are new design).
 //
 // Pipeline (main stream, then the tail stream from the second reduce level on):
-//   msm_sort.hip   signed window digits of every scalar, two-level LDS counting sort ->
-//                  count[] per bucket, then (point index | sign) entries grouped by bucket
-//   k_scan_*       exclusive scan: bucket offsets + accumulate-unit offsets (runs split at L)
-//   k_fill_units   unit -> bucket map;  k_unit_* order the units by run length (descending)
+//   msm_sort_stage.hip   the sort stage, by one of three sorts (plan_sort()): signed window digits of every scalar ->
+//                  count[] per bucket, (point index | sign) entries grouped by bucket, bucket offsets + accumulate-unit
+//                  offsets (runs split at L), unit -> bucket map, the units ordered by run length (descending)
 //   k_accumulate   one lane per unit: gathers its run of points, XYZZ mixed adds   [phase 1]
 //   k_combine_units   only when a bucket needed more than one unit
 //   k_reduce_level Sum_b b*S_b per virtual window by segmented running sums        [phase 2]
@@ -332,24 +331,6 @@ std::string describe(const TailPlan& T) {
     return s + (T.finish_row ? " finish_row" : " finish");
 }
 
-// zero-fill (hipMemsetAsync's fill kernel took 0.7 ms for the 71 MB bucket-count array: ~100 GB/s)
-__global__ __launch_bounds__(256) void k_zero(uint4* __restrict__ p, size_t n16) {
-    __builtin_amdgcn_s_setprio(3);   // sort-stage kernel: may run underneath another task's accumulation (msm_sort3.hip)
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = z;
-}
-
-// scalar-range tasks: dst = words [w0, w0 + nw) of every 8-word scalar, zero-extended to 8 words
-__global__ __launch_bounds__(256) void k_extract_range(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint64_t n, uint32_t w0,
-                                                       uint32_t nw) {
-    __builtin_amdgcn_s_setprio(3);   // sort-stage kernel
-    const uint64_t total = n * 8;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256) {
-        const uint32_t j = (uint32_t)(i & 7u);
-        dst[i] = j < nw ? src[(i & ~(uint64_t)7) + w0 + j] : 0u;
-    }
-}
-
 __global__ __launch_bounds__(64) void k_words_to_pinned(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, uint32_t n) {
     __builtin_amdgcn_s_setprio(3);
     if (threadIdx.x < n) __hip_atomic_store(dst + threadIdx.x, src[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -364,241 +345,6 @@ int copy_words_to_pinned(void* host_pinned, const void* d_src, uint32_t dwords, 
 // p[i] = i: the "every bucket has exactly one sum, at its own index" unit_off of piecewise tasks (begin() / end())
 __global__ __launch_bounds__(256) void k_iota(uint32_t* __restrict__ p, uint64_t n) {
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) p[i] = (uint32_t)i;
-}
-
-// ------------------------------------------------------------------------------------------------
-// exclusive scan of (count, units(count)) packed in one u64: low = entries, high = units
-// ------------------------------------------------------------------------------------------------
-constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_TILE = 256 * SCAN_ITEMS;
-
-__device__ __forceinline__ uint64_t pack_cu(uint32_t cnt, uint32_t L) {
-    return (uint64_t)cnt | ((uint64_t)((cnt + L - 1) / L) << 32);
-}
-__device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* sh) {
-    // wave reduce then across 4 waves
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) sh[wv] = v;
-    __syncthreads();
-    uint64_t t = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return t;
-}
-
-__global__ __launch_bounds__(256) void k_scan_reduce(const uint32_t* __restrict__ count, uint64_t G, uint32_t L,
-                                                     uint64_t* __restrict__ blocksums, uint32_t* __restrict__ stats) {
-    __builtin_amdgcn_s_setprio(3);   // sort-stage kernel: may run underneath another task's accumulation (msm_sort3.hip)
-    __shared__ uint64_t sh[4];
-    uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE;
-    uint64_t acc = 0;
-    uint32_t mx = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        uint64_t i = base + (uint64_t)k * 256 + threadIdx.x;
-        if (i < G) {
-            uint32_t cn = count[i];
-            acc += pack_cu(cn, L);
-            mx = cn > mx ? cn : mx;
-        }
-    }
-    uint64_t tot = block_sum_u64(acc, sh);
-    for (int o = 32; o > 0; o >>= 1) { uint32_t t = __shfl_down(mx, o, 64); mx = t > mx ? t : mx; }
-    // (guarded: 5 x 10^4 unconditional atomics on one address cost 0.5 ms; the value only grows)
-    if ((threadIdx.x & 63) == 0 && mx > *(volatile uint32_t*)&stats[1]) atomicMax(&stats[1], mx);
-    if (threadIdx.x == 0) blocksums[blockIdx.x] = tot;
-}
-
-// single block: exclusive scan of blocksums in place; totals -> stats[0] (units), stats[2] (entries)
-// (256 threads: the kernel belongs to the sort stage, which may have to fit beside another task's accumulation -
-// a 1024-thread block needs four waves per SIMD at once and 4 x its registers of the ~100 VGPRs the accumulation leaves)
-constexpr int SCAN_SUMS_THREADS = 256;
-__global__ __launch_bounds__(SCAN_SUMS_THREADS) void k_scan_sums(uint64_t* __restrict__ blocksums, uint32_t nblocks,
-                                                                 uint32_t* __restrict__ stats) {
-    __builtin_amdgcn_s_setprio(3);   // sort-stage kernel: may run underneath another task's accumulation (msm_sort3.hip)
-    __shared__ uint64_t sh[SCAN_SUMS_THREADS];
-    __shared__ uint64_t carry_sh;
-    if (threadIdx.x == 0) carry_sh = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < nblocks; base += SCAN_SUMS_THREADS) {
-        uint32_t i = base + threadIdx.x;
-        uint64_t v = i < nblocks ? blocksums[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < SCAN_SUMS_THREADS; o <<= 1) {
-            uint64_t t = threadIdx.x >= (uint32_t)o ? sh[threadIdx.x - o] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += t;
-            __syncthreads();
-        }
-        uint64_t incl = sh[threadIdx.x];
-        uint64_t carry = carry_sh;
-        if (i < nblocks) blocksums[i] = carry + incl - v;
-        __syncthreads();
-        if (threadIdx.x == SCAN_SUMS_THREADS - 1) carry_sh = carry + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        stats[0] = (uint32_t)(carry_sh >> 32);
-        stats[2] = (uint32_t)(carry_sh & 0xffffffffu);
-    }
-}
-
-// per-block exclusive scan with the block's base; writes off[], unit_off[] and turns count[] into
-// the scatter cursor (count[g] = off[g]).  Element G (one past the end) receives the totals.
-__global__ __launch_bounds__(256) void k_scan_final(uint32_t* __restrict__ count, uint64_t G, uint32_t L,
-                                                    const uint64_t* __restrict__ blocksums,
-                                                    uint32_t* __restrict__ off, uint32_t* __restrict__ unit_off) {
-    __builtin_amdgcn_s_setprio(3);   // sort-stage kernel: may run underneath another task's accumulation (msm_sort3.hip)
-    __shared__ uint64_t sh[256];
-    uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t v[SCAN_ITEMS];
-    uint64_t tsum = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        uint64_t i = base + k;
-        v[k] = i < G ? pack_cu(count[i], L) : 0;
-        tsum += v[k];
-    }
-    sh[threadIdx.x] = tsum;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        uint64_t t = threadIdx.x >= (uint32_t)o ? sh[threadIdx.x - o] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += t;
-        __syncthreads();
-    }
-    uint64_t run = blocksums[blockIdx.x] + sh[threadIdx.x] - tsum;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        uint64_t i = base + k;
-        if (i <= G) {
-            off[i] = (uint32_t)(run & 0xffffffffu);
-            unit_off[i] = (uint32_t)(run >> 32);
-            if (i < G) count[i] = (uint32_t)(run & 0xffffffffu);
-        }
-        run += v[k];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Units ordered by run length (descending), so the 64 lanes of a wave walk runs of equal length:
-// with uniform scalars the runs are Poisson (mean n/2^(c-1)), and bucket order costs ~30% of the
-// lanes to divergence.  Counting sort over <= 1025 length bins, LDS-privatised; both kernels walk the
-// buckets in order (coalesced reads of off / unit_off), one lane per bucket.
-// ------------------------------------------------------------------------------------------------
-constexpr int MAX_L = 1024;
-constexpr uint32_t UNITS_INLINE = 8;   // buckets with more units than this are filled by the whole block
-
-// unit -> bucket map + histogram of unit lengths.  Grid-stride over chunks of 256 buckets: the LDS
-// histogram is flushed once per block (one block per chunk meant 10^5 blocks x 257 global atomics on
-// the same 257 addresses: 1.3 ms at 2^26, all of it atomic serialisation).
-constexpr uint32_t UNIT_GRID = 2048;
-
-__global__ __launch_bounds__(256) void k_fill_units(const uint32_t* __restrict__ off, const uint32_t* __restrict__ unit_off,
-                                                    uint64_t G, uint32_t L, uint32_t* __restrict__ unit_bucket,
-                                                    uint32_t* __restrict__ hist) {
-    __builtin_amdgcn_s_setprio(3);   // sort-stage kernel: may run underneath another task's accumulation (msm_sort3.hip)
-    __shared__ uint32_t sh[MAX_L + 1];
-    __shared__ uint32_t big[256], nbig;
-    for (uint32_t i = threadIdx.x; i <= L; i += 256) sh[i] = 0;
-    const uint64_t nchunks = (G + 255) / 256;
-    for (uint64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        if (threadIdx.x == 0) nbig = 0;
-        __syncthreads();
-        // a bucket of cnt entries has cnt / L full units and one unit of cnt % L entries
-        const uint64_t g0 = chunk * 256;
-        uint64_t g = g0 + threadIdx.x;
-        if (g < G) {
-            uint32_t u0 = unit_off[g], u1 = unit_off[g + 1];
-            uint32_t cnt = off[g + 1] - off[g];
-            uint32_t nfull = cnt / L, rem = cnt - nfull * L;
-            if (nfull) atomicAdd(&sh[L], nfull);
-            if (rem) atomicAdd(&sh[rem], 1u);
-            if (u1 - u0 > UNITS_INLINE) big[atomicAdd(&nbig, 1u)] = threadIdx.x;   // hot bucket: the block fills it together
-            else for (uint32_t u = u0; u < u1; ++u) unit_bucket[u] = (uint32_t)g;
-        }
-        __syncthreads();
-        for (uint32_t b = 0; b < nbig; ++b) {
-            uint64_t gb = g0 + big[b];
-            uint32_t u0 = unit_off[gb], u1 = unit_off[gb + 1];
-            for (uint32_t u = u0 + threadIdx.x; u < u1; u += 256) unit_bucket[u] = (uint32_t)gb;
-        }
-        __syncthreads();
-    }
-    for (uint32_t i = threadIdx.x; i <= L; i += 256)
-        if (sh[i]) atomicAdd(&hist[i], sh[i]);
-}
-
-// cursor[len] = number of units strictly longer than len (descending order); one block
-__global__ __launch_bounds__(256) void k_unit_len_scan(const uint32_t* __restrict__ hist, uint32_t L,
-                                                       uint32_t* __restrict__ cursor) {
-    __builtin_amdgcn_s_setprio(3);   // sort-stage kernel: may run underneath another task's accumulation (msm_sort3.hip)
-    if (threadIdx.x != 0) return;
-    uint32_t run = 0;
-    for (int len = (int)L; len >= 0; --len) {
-        cursor[len] = run;
-        run += hist[len];
-    }
-}
-
-__global__ __launch_bounds__(256) void k_unit_order(const uint32_t* __restrict__ off, const uint32_t* __restrict__ unit_off,
-                                                    uint64_t G, uint32_t L, uint32_t* __restrict__ cursor,
-                                                    uint32_t* __restrict__ unit_order) {
-    __builtin_amdgcn_s_setprio(3);   // sort-stage kernel: may run underneath another task's accumulation (msm_sort3.hip)
-    __shared__ uint32_t sh_cnt[MAX_L + 1];
-    __shared__ uint32_t sh_base[MAX_L + 1];
-    __shared__ uint32_t big[256], big_pos[256], nbig;
-    for (uint32_t i = threadIdx.x; i <= L; i += 256) sh_cnt[i] = 0;
-    __syncthreads();
-    const uint64_t nchunks = (G + 255) / 256;
-    // pass 1 over this block's chunks: how many units of each length
-    for (uint64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        uint64_t g = chunk * 256 + threadIdx.x;
-        if (g < G) {
-            uint32_t cnt = off[g + 1] - off[g];
-            uint32_t nfull = cnt / L, rem = cnt - nfull * L;
-            if (nfull) atomicAdd(&sh_cnt[L], nfull);
-            if (rem) atomicAdd(&sh_cnt[rem], 1u);
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i <= L; i += 256) {
-        uint32_t v = sh_cnt[i];
-        sh_base[i] = v ? atomicAdd(&cursor[i], v) : 0u;
-        sh_cnt[i] = 0;
-    }
-    // pass 2: place
-    for (uint64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        if (threadIdx.x == 0) nbig = 0;
-        __syncthreads();
-        const uint64_t g0 = chunk * 256;
-        uint64_t g = g0 + threadIdx.x;
-        if (g < G) {
-            uint32_t u0 = unit_off[g];
-            uint32_t cnt = off[g + 1] - off[g];
-            uint32_t nfull = cnt / L, rem = cnt - nfull * L;
-            if (nfull) {
-                uint32_t pos = sh_base[L] + atomicAdd(&sh_cnt[L], nfull);
-                if (nfull > UNITS_INLINE) {
-                    uint32_t q = atomicAdd(&nbig, 1u);
-                    big[q] = threadIdx.x;
-                    big_pos[q] = pos;
-                } else {
-                    for (uint32_t k = 0; k < nfull; ++k) unit_order[pos + k] = u0 + k;
-                }
-            }
-            if (rem) unit_order[sh_base[rem] + atomicAdd(&sh_cnt[rem], 1u)] = u0 + nfull;
-        }
-        __syncthreads();
-        for (uint32_t b = 0; b < nbig; ++b) {
-            uint64_t gb = g0 + big[b];
-            uint32_t ub = unit_off[gb];
-            uint32_t nf = (off[gb + 1] - off[gb]) / L, pos = big_pos[b];
-            for (uint32_t k = threadIdx.x; k < nf; k += 256) unit_order[pos + k] = ub + k;
-        }
-        __syncthreads();
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -623,26 +369,6 @@ int msm_points_all_canonical(int format_id, const void* d_raw, uint64_t npts, ui
     const MsmCurveOps* ops = msm_ops_for(format_id & 0xff, (format_id >> 8) & 0xff);
     if (!ops) return fail(BLZ_ERR_UNKNOWN, "unknown Montgomery format 0x%x", format_id);
     return ops->points_all_canonical(d_raw, npts, flag, st);
-}
-
-int launch_fill_units(const MsmStep& C, uint32_t U /* upper bound of the unit count */) {
-    const uint64_t G = C.P.G;
-    const uint32_t L = C.P.L;
-    hipStream_t st = C.sort_stream;
-    MsmEngine::SortBufs& B = C.B;
-    BLZ_TRY(B.unit_bucket.reserve(((size_t)U + 1) * 4));
-    BLZ_TRY(B.unit_order.reserve(((size_t)U + 1) * 4));
-    BLZ_TRY(B.lenhist.reserve(2 * (MAX_L + 1) * 4));
-    uint32_t* hist = B.lenhist.as<uint32_t>();
-    uint32_t* cursor = hist + (MAX_L + 1);
-    BLZ_HIP(hipMemsetAsync(hist, 0, 2 * (MAX_L + 1) * 4, st), BLZ_ERR_UNKNOWN);
-    uint64_t nchunks = (G + 255) / 256;
-    dim3 gg((uint32_t)(nchunks < UNIT_GRID ? nchunks : UNIT_GRID)), b(256);
-    hipLaunchKernelGGL(k_fill_units, gg, b, 0, st, B.off.as<uint32_t>(), B.unit_off.as<uint32_t>(), G, L, B.unit_bucket.as<uint32_t>(), hist);
-    hipLaunchKernelGGL(k_unit_len_scan, dim3(1), b, 0, st, hist, L, cursor);
-    hipLaunchKernelGGL(k_unit_order, gg, b, 0, st, B.off.as<uint32_t>(), B.unit_off.as<uint32_t>(), G, L, cursor, B.unit_order.as<uint32_t>());
-    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
-    return BLZ_OK;
 }
 
 int MsmEngine::init(int device_id, int curve_id, int precompute_factor) {
@@ -748,23 +474,6 @@ int MsmEngine::build_table(const void* d_raw, void* d_table, uint32_t npts, int 
 }
 size_t MsmEngine::table_scratch_bytes(int W) const { return msm_ops_for(curve, repr)->table_scratch_bytes(W); }
 
-// do the hidden sort's waves (sv VGPRs) fit on a SIMD beside the accumulation's (av VGPRs each, as many as fit)?  Measured: the
-// sort runs beside 2 x 200 + 72 = 472 registers and waits for the accumulation to END behind 2 x 208 + 72 = 488.
-// LDS (reasoned from the allocation rules, not measured like the register bound): the accumulation's blocks are 128 lanes, so `waves` of its waves per SIMD are 2 x waves blocks per CU; one block of the
-// sort has to fit in what they leave of the CU's 160 KiB (allocations taken in steps of 1 KiB).  A sort block that does not
-// fit is not an error either: it waits until the accumulation's blocks drain from a CU, that is for its end.
-bool msm_sort_fits_beside(int av, int sv, int al, int sl) {
-    if (av <= 0 || sv <= 0) return true;
-    const int a = (av + 7) & ~7, s = (sv + 7) & ~7;
-    int waves = 512 / a;
-    if (waves > 4) waves = 4;
-    if (waves < 1) waves = 1;
-    if (waves * a + s > 512 - 32) return false;
-    if (al <= 0 || sl <= 0) return true;   // no LDS on one side (or not known): nothing to share
-    const int ak = (al + 1023) >> 10, sk = (sl + 1023) >> 10;
-    return 2 * waves * ak + sk <= 160;
-}
-
 static const int kScalarFieldBits[3] = {253, 255, 254};  // bit length of r (BLS12-377 / 381 / BN254)
 
 MsmPlan MsmEngine::plan_for(uint32_t npts, int sbits) const {
@@ -841,8 +550,8 @@ int MsmEngine::step(int slot, int piece, bool curve_kernels, std::optional<MsmSt
     if (curve_kernels && S.repr != repr) return fail(BLZ_ERR_INVALID_PARAM, "the handle's arithmetic changed while task %d was being enqueued", slot);
     if (S.slices == 1) piece = -1;
     // a ping-pong task's pieces alternate between the slot's own set and the other slot's; end() reads the slot's own
-    const int set = S.pingpong && piece >= 0 ? (slot + piece) % MSM_QUEUE_DEPTH : slot;
-    out.emplace(MsmStep{slot, S, piece, S.plan, sbuf[set], stream, S.sort_hidden ? sort_stream : stream});
+    const int set = S.sort.where == SortPlan::PINGPONG && piece >= 0 ? (slot + piece) % MSM_QUEUE_DEPTH : slot;
+    out.emplace(MsmStep{slot, S, piece, S.plan, sbuf[set], stream, S.sort.where != SortPlan::OPEN ? sort_stream : stream});
     return BLZ_OK;
 }
 
@@ -861,52 +570,17 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
     uint32_t per = npts;
     nslices = msm_task_pieces(P, nslices, phased, &per);
     BLZ_TRY(plan_tail(P, ops->tail, nslices > 1, S.tail));   // (a refusal leaves the slot free)
-    BLZ_LOG(2, "msm plan: npts=%u sbits=%d c=%d W=%d Bw=%u G=%llu L=%u pieces=%d tail: %s", npts, sbits, P.c, P.W, P.Bw,
-            (unsigned long long)G, P.L, nslices, describe(S.tail).c_str());
+    // The sort stage's outputs are per slot (SortBufs); the scratch the sorts share is protected by chaining every sort stage
+    // behind the one before (last_sort_done).
+    // (fits: a build whose register and LDS counts cannot be read is taken to fit; k_accumulate_cont shares k_accumulate's register cap)
+    const SortInputs sort_in = {env_int("BLAZE_SORT_HIDE", 1), slots[(slot + 1) % MSM_QUEUE_DEPTH].busy, recent_hot[0] || recent_hot[1],
+                                msm_sort_fits_beside(ops->accumulate_vgprs(), msm_sort3_max_vgprs(P.table), ops->accumulate_lds(), msm_sort3_max_lds(P.table))};
+    const SortPlan sort = plan_sort(P, npts, sbits, nslices, sort_in);
+    BLZ_LOG(2, "msm plan: npts=%u sbits=%d c=%d W=%d Bw=%u G=%llu L=%u pieces=%d sort: %s tail: %s", npts, sbits, P.c, P.W, P.Bw,
+            (unsigned long long)G, P.L, nslices, describe(sort).c_str(), describe(S.tail).c_str());
     const uint64_t max_entries = (uint64_t)per * P.W;
     const uint64_t max_units = G + max_entries / P.L + 1;
     if (max_units >= (1ull << 32)) return fail(BLZ_ERR_INVALID_PARAM, "unit bound %llu exceeds 32 bits", (unsigned long long)max_units);
-
-    // The sort stage (digit sort, bucket / unit scans, unit lists) of a one-piece task.  When the handle's other task is
-    // still in flight - its accumulation is running or about to - the stage goes to sort_stream with the small-footprint
-    // three-level sort (msm_sort3.hip) and runs UNDERNEATH that accumulation; the accumulation of this task then starts
-    // with its sort already done.  Its outputs are per slot (SortBufs); the scratch the sorts share is protected by
-    // chaining every sort stage behind the one before (last_sort_done).  BLAZE_SORT_HIDE: 0 never, 1 when the other slot
-    // is busy (default), 2 the three-level sort always (on the main stream when there is nothing to hide under: tests).
-    const int hide_env = env_int("BLAZE_SORT_HIDE", 1);
-    const MsmSlot& O = slots[(slot + 1) % MSM_QUEUE_DEPTH];
-    bool s3 = P.table || (hide_env != 0 && nslices == 1 && msm_sort3_ok(P, sbits));   // (a table task has no other sort)
-    bool fits = true;
-    // (a build whose register and LDS counts cannot be read is taken to fit; k_accumulate_cont shares k_accumulate's register cap)
-    auto sort_fits = [&](bool table) {
-        return msm_sort_fits_beside(ops->accumulate_vgprs(), msm_sort3_max_vgprs(table), ops->accumulate_lds(), msm_sort3_max_lds(table));
-    };
-    if (s3 && hide_env == 1 && !P.table) {
-        // the three-level sort gives one block a whole level-2 bin: fine for the near-uniform digits of real scalars, a
-        // cliff for inputs that pile entries into a few buckets (the reference harness repeats a 256-point tile).  The
-        // handle's last two COLLECTED tasks say which kind it is being fed (finish(): their largest bucket against their own
-        // mean - judged when the host has waited for the task, never read from a copy that may still be in flight)
-        if (recent_hot[0] || recent_hot[1]) s3 = false;
-    }
-    if (s3 && hide_env == 1) {
-        // ... and the sort only hides if its waves fit BESIDE the accumulation's: two of those per SIMD (registers are
-        // allocated in eights) plus one of the sort's.  Measured: the sort runs beside 2 x 194..199 (-> 2 x 200) + 72 = 472
-        // registers, and waits for the accumulation to END behind 2 x 206 (-> 208) + 72 = 488 and 2 x 211 (-> 216) + 72 = 504 -
-        // the SIMD does not hand out all 512.  A build whose k_accumulate grew past that still works, it just sorts in
-        // the open (round 3 saw 211 VGPRs cost 4 ms per step before this check existed).
-        // (the SIMD runs as many accumulation waves as their allocation admits: two of the reduced-radix kernels', three of
-        // the 32-bit-limb kernel's, whose allocation is padded to 136 for exactly this purpose)
-        // A table plan's largest kernel (k3t_l3<true>: 78 VGPRs, allocated as 80) fits with nothing to spare: 2 x 200 + 80 = 480.
-        // The same goes for LDS: the BLS accumulation's four blocks per CU hold 4 x 16 KiB, the sort's largest block 83 KiB.
-        fits = sort_fits(P.table);
-        if (!fits && !P.table) s3 = false;   // (a table task has no other sort: it then sorts in the open)
-    }
-    bool hide = s3 && O.busy && hide_env != 0 && fits;
-    // pieces of a task on an otherwise idle handle: piece k + 1 sorts underneath the accumulation of piece k (ping-pong over
-    // the two slots' sort buffers); same conditions as hiding a task's sort
-    const bool pingpong = nslices > 1 && hide_env != 0 && !O.busy && !P.table && msm_sort3_ok(P, sbits) && !(recent_hot[0] || recent_hot[1]) &&
-                          sort_fits(false);
-    if (pingpong) { s3 = true; hide = true; }
 
     rr_cursor = slot;
     if (slot_out) *slot_out = slot;
@@ -920,16 +594,14 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
     S.slices = nslices;
     S.pts_per_slice = per;
     S.max_units = max_units;
-    S.use_s3 = s3 && (hide || hide_env == 2 || P.table);
-    S.sort_hidden = hide;
-    S.pingpong = pingpong;
+    S.sort = sort;
     S.acc_pp_recorded[0] = S.acc_pp_recorded[1] = false;
     S.phased = phased;
     S.task_inputs_event = inputs_event;
     S.accum_timed = false;
     BLZ_HIP(hipEventRecord(S.ev[0], st), BLZ_ERR_UNKNOWN);
     for (int b = 0; b < MSM_QUEUE_DEPTH; ++b) {
-        if (b != slot && !pingpong) continue;
+        if (b != slot && sort.where != SortPlan::PINGPONG) continue;   // (a ping-pong task's pieces use both slots' sets)
         BLZ_TRY(sbuf[b].count.reserve((G + 1) * 4 + 16));
         BLZ_TRY(sbuf[b].off.reserve((G + 2) * 4));
         BLZ_TRY(sbuf[b].unit_off.reserve((G + 2) * 4));
@@ -940,7 +612,7 @@ int MsmEngine::begin(uint32_t npts, int sbits, int* slot_out, int table_c, int b
         const size_t sum_bytes = (size_t)ops->tail.partial_dwords * 4;
         BLZ_TRY(bucket_sums.reserve((G + 1) * sum_bytes));
         BLZ_TRY(bucket_ident.reserve((G + 2) * 4));
-        hipLaunchKernelGGL(k_zero, dim3(2048), dim3(256), 0, st, (uint4*)bucket_sums.p, ((G + 1) * sum_bytes + 15) / 16);   // all-zero = infinity
+        launch_zero(bucket_sums.p, ((G + 1) * sum_bytes + 15) / 16, st);   // all-zero = infinity
         BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
     }
     S.open = true;
@@ -955,64 +627,24 @@ int MsmEngine::sort_slice(int slot, int sl, const void* d_scalars, uint32_t np) 
     MsmSlot& S = C->S;
     if (sl < 0 || sl >= S.slices || np == 0 || np > S.pts_per_slice) return fail(BLZ_ERR_INVALID_PARAM, "piece %d of %d with %u points", sl, S.slices, np);
     rr_cursor = slot;
-    const MsmPlan& P = C->P;
-    const uint64_t G = P.G;
-    const uint32_t nscan = (uint32_t)((G + 1 + SCAN_TILE - 1) / SCAN_TILE);
     MsmSlot& O = slots[(slot + 1) % MSM_QUEUE_DEPTH];
-    SortBufs& B = C->B;
-    const bool hide = S.sort_hidden;
+    const bool hide = S.sort.where != SortPlan::OPEN, pingpong = S.sort.where == SortPlan::PINGPONG;
     hipStream_t ss = C->sort_stream;
     if (last_sort_done) BLZ_HIP(hipStreamWaitEvent(ss, last_sort_done, 0), BLZ_ERR_UNKNOWN);
     if (hide) {
         // whoever read this buffer set last must have let go of it: the accumulation two pieces back (ping-pong), else the
         // slot's previous task (its level-0 reduce read unit_off last) - and the OTHER slot's last task too if that was a
         // ping-pong task, which borrowed this slot's set
-        if (S.pingpong && S.acc_pp_recorded[sl & 1]) {
+        if (pingpong && S.acc_pp_recorded[sl & 1]) {
             BLZ_HIP(hipStreamWaitEvent(ss, S.ev_acc_pp[sl & 1], 0), BLZ_ERR_UNKNOWN);
         } else {
             if (S.l0_recorded) BLZ_HIP(hipStreamWaitEvent(ss, S.ev_l0, 0), BLZ_ERR_UNKNOWN);
-            if (O.pingpong && O.l0_recorded) BLZ_HIP(hipStreamWaitEvent(ss, O.ev_l0, 0), BLZ_ERR_UNKNOWN);
+            if (O.sort.where == SortPlan::PINGPONG && O.l0_recorded) BLZ_HIP(hipStreamWaitEvent(ss, O.ev_l0, 0), BLZ_ERR_UNKNOWN);
         }
     }
     BLZ_HIP(hipEventRecord(S.ev_s0, ss), BLZ_ERR_UNKNOWN);   // ev_s0 .. ev_s1: the sort stage, whichever stream it is on
-    dim3 b256(256);
-    const char* sc_s = (const char*)d_scalars;
-    if (S.ranged) {
-        // the range of every scalar as a scalar of its own (zero-extended): everything downstream reads 32-byte scalars and
-        // walks the plan's windows from bit 0; k_finish puts the 2^bit_lo back (FinishPlan offsets)
-        BLZ_TRY(B.range_scalars.reserve((size_t)np * 32 + 16));
-        hipLaunchKernelGGL(k_extract_range, dim3(2048), dim3(256), 0, ss, (const uint32_t*)sc_s, B.range_scalars.as<uint32_t>(),
-                           (uint64_t)np, (uint32_t)(S.bit_lo >> 5), (uint32_t)((S.bit_hi - S.bit_lo) >> 5));
-        sc_s = (const char*)B.range_scalars.p;
-    }
-    BLZ_HIP(hipMemsetAsync(B.stats.p, 0, 64, ss), BLZ_ERR_UNKNOWN);
-    // a small task's whole sort stage - digits, bucket scan, entries, unit lists - is one block's work (msm_sort_tiny.hip)
-    const bool tiny = !S.use_s3 && S.slices == 1 && msm_sort_tiny_ok(P, np, S.sbits);
-    LdsSortPass lds_pass;
-    if (S.use_s3) {
-        BLZ_TRY(msm_sort3(*this, *C, sc_s, np, S.sbits));   // count[] and entries[] in one go
-    } else if (tiny) {
-        BLZ_TRY(msm_sort_tiny(*this, *C, sc_s, np, S.sbits, (uint32_t)S.max_units));
-    } else {
-        const size_t n16 = ((G + 1) * 4 + 15) / 16;   // the reserve of begin() rounds the allocation up
-        hipLaunchKernelGGL(k_zero, dim3(2048), dim3(256), 0, ss, (uint4*)B.count.p, n16);
-        BLZ_TRY(msm_sort_lds(*this, *C, sc_s, np, S.sbits, lds_pass));
-    }
-    if (!tiny) {
-        hipLaunchKernelGGL(k_scan_reduce, dim3(nscan), b256, 0, ss, B.count.as<uint32_t>(), G, P.L, blocksums.as<uint64_t>(),
-                           B.stats.as<uint32_t>());
-        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_SUMS_THREADS), 0, ss, blocksums.as<uint64_t>(), nscan, B.stats.as<uint32_t>());
-        hipLaunchKernelGGL(k_scan_final, dim3(nscan), b256, 0, ss, B.count.as<uint32_t>(), G, P.L, blocksums.as<uint64_t>(),
-                           B.off.as<uint32_t>(), B.unit_off.as<uint32_t>());
-        if (!S.use_s3) BLZ_TRY(msm_sort_lds_scatter(*this, *C, lds_pass));
-    }
-    BLZ_HIP(hipGetLastError(), BLZ_ERR_UNKNOWN);
-    // No host round trip: the unit count stays on the device.  Buffers and grids are sized by the bound
-    // (every bucket at most one short unit, plus entries / L full ones) and the kernels read the real count
-    // from `stats`; the host copy below is for the log line, the sanity check of finish() and the hot-bucket guard.
-    BLZ_TRY(copy_words_to_pinned(S.stats_h, B.stats.p, 4, ss));
-    if (!tiny) BLZ_TRY(launch_fill_units(*C, (uint32_t)S.max_units));
-    hipEvent_t sorted = S.pingpong ? S.ev_sorted_pp[sl & 1] : S.ev_sorted;
+    BLZ_TRY(msm_sort_stage(*this, *C, d_scalars, np));
+    hipEvent_t sorted = pingpong ? S.ev_sorted_pp[sl & 1] : S.ev_sorted;
     BLZ_HIP(hipEventRecord(sorted, ss), BLZ_ERR_UNKNOWN);
     last_sort_done = sorted;
     BLZ_HIP(hipEventRecord(S.ev_s1, ss), BLZ_ERR_UNKNOWN);
@@ -1036,10 +668,11 @@ int MsmEngine::accumulate_slice(int slot, int sl, const void* d_pts) {
     MsmSlot& S = C->S;
     const MsmCurveOps* ops = msm_ops_for(curve, repr);
     rr_cursor = slot;
-    if (S.sort_hidden) BLZ_HIP(hipStreamWaitEvent(stream, S.pingpong ? S.ev_sorted_pp[sl & 1] : S.ev_sorted, 0), BLZ_ERR_UNKNOWN);
+    const bool pingpong = S.sort.where == SortPlan::PINGPONG;
+    if (S.sort.where != SortPlan::OPEN) BLZ_HIP(hipStreamWaitEvent(stream, pingpong ? S.ev_sorted_pp[sl & 1] : S.ev_sorted, 0), BLZ_ERR_UNKNOWN);
     BLZ_TRY(ops->run_accumulate(*this, *C, d_pts, (uint32_t)S.max_units));
     if (S.slices > 1) BLZ_TRY(ops->merge_buckets(*this, *C));
-    if (S.pingpong) {
+    if (pingpong) {
         BLZ_HIP(hipEventRecord(S.ev_acc_pp[sl & 1], stream), BLZ_ERR_UNKNOWN);
         S.acc_pp_recorded[sl & 1] = true;
     }
@@ -1149,7 +782,7 @@ int MsmEngine::finish(int slot, uint8_t* out) {
             last_ms[1] = t;
         }
     }
-    last_sort_hidden = S.sort_hidden && S.plan.c != 0;
+    last_sort_hidden = S.sort.where != SortPlan::OPEN && S.plan.c != 0;
     if (S.plan.c) (void)hipEventElapsedTime(&t, S.ev_s0, S.ev_s1);   // the sort stage: on the main stream, or on sort_stream underneath the previous task
     else t = 0;
     last_ms[2] = t;

@@ -1,4 +1,4 @@
-// Host-side interface of the MSM device pipeline (implemented in msm.hip).
+// Host-side interface of the MSM device pipeline (implemented in msm.hip; the sort stage in msm_sort_stage.hip).
 #pragma once
 #include "common.hpp"
 #include <optional>
@@ -91,6 +91,23 @@ int plan_tail(const MsmPlan& P, TailTraits tr, bool piecewise, TailPlan& out);
 // one canonical line: "units2 hot_row fold_row_weak | L0row Lrow Lrow finish_row"
 std::string describe(const TailPlan& T);
 
+// ------------------------------------------------------------------------------------------------
+// The stage in front of k_accumulate - the digit sort, the bucket / unit scans, the unit lists - is served by three sorts.
+// Which one a task runs, and where, is decided ONCE, by plan_sort() in begin() (msm_sort_stage.hip, with the reasons);
+// msm_sort_stage() only enqueues what the plan names.
+// ------------------------------------------------------------------------------------------------
+struct SortPlan {
+    enum Kind { LDS, S3, TINY } kind;      // msm_sort.hip / msm_sort3.hip / msm_sort_tiny.hip
+    enum Where { OPEN, HIDDEN, PINGPONG } where;   // main stream / sort_stream under the other slot's accumulation / under this task's own previous piece
+};
+// everything begin() reads that is not the plan: BLAZE_SORT_HIDE; the handle's other slot holds a task; one of the last two
+// collected tasks piled its entries into a few buckets (MsmEngine::recent_hot); msm_sort_fits_beside for this kind of plan
+struct SortInputs { int hide_env; bool other_busy, recent_hot, fits; };
+SortPlan plan_sort(const MsmPlan& P, uint32_t npts, int sbits, int pieces, const SortInputs& in);   // host arithmetic: no HIP call
+std::string describe(const SortPlan&);   // "lds open" | "tiny open" | "s3 open" | "s3 hidden" | "s3 pingpong"
+constexpr int SCAN_TILE = 2048;   // buckets per block of the bucket scan (k_scan_*): sizes `blocksums`
+constexpr int MAX_L = 1024;       // longest accumulate unit (MsmPlan::L): the unit lists count run lengths in LDS
+
 // Task queue (msm_hw_code.rs:19-25: the device has a task queue and a result queue): up to
 // MSM_QUEUE_DEPTH tasks may be in flight.  The throughput-bound part of a task (sort, bucket
 // accumulation, first bucket-reduce level) runs on `stream`; its latency-bound tail (upper reduce
@@ -105,7 +122,6 @@ struct MsmSlot {
     hipEvent_t ev_l0 = nullptr;    // stream: level-0 reduce written -> tail may start (and this slot's sort outputs are free)
     hipEvent_t ev_sorted = nullptr;  // the sort stage (sort, scans, unit lists) of this slot's task is complete
     hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;  // timing of a hidden sort stage on sort_stream
-    bool sort_hidden = false;      // this task's sort ran on sort_stream
     bool l0_recorded = false;      // ev_l0 has been recorded at least once
     hipEvent_t ev_done = nullptr;  // tail_stream: result bytes are in result_h
     DevBuf lvlA[2], lvlC[2];
@@ -113,6 +129,11 @@ struct MsmSlot {
     uint32_t* stats_h = nullptr;   // pinned: [0] total units, [1] max bucket count, [2] total entries (read in finish())
     uint64_t max_units = 0;        // the bound the launches of this task were sized by
     MsmPlan plan;
+    // which sort runs in front of the accumulation, and where (begin()).  Not OPEN: the stage is on sort_stream.  PINGPONG: a
+    // piecewise task on an otherwise idle handle sorts piece k + 1 UNDERNEATH the accumulation of piece k, like a stream of
+    // tasks does: the pieces alternate between this slot's SortBufs and the other slot's (which nobody uses while that slot
+    // is idle), one pair of events per buffer set (ev_sorted_pp / ev_acc_pp).
+    SortPlan sort{};
     TailPlan tail;                 // what runs behind the accumulation (begin())
     // piecewise tasks (msm.hip begin()): one event pair per piece around its k_accumulate_cont launch; finish() sums them
     hipEvent_t slice_ev[2 * 64] = {};
@@ -122,15 +143,12 @@ struct MsmSlot {
     // state of a task between begin() and end() (msm.hip)
     bool open = false;             // begun, not every piece enqueued yet
     bool phased = false;           // the caller enqueues the pieces as their data lands (inputs_event is recorded by end())
-    bool use_s3 = false, ranged = false;
+    bool ranged = false;
     uint32_t npts = 0, pts_per_slice = 0;
     int sbits = 0, bit_lo = 0, bit_hi = 0;
     int repr = 0;                  // the arithmetic begin() sized the task for (bucket_sums): accumulate_slice / end refuse another
     hipEvent_t task_inputs_event = nullptr;   // the caller's inputs_event, until it has been recorded
-    // A piecewise task on an otherwise idle handle sorts piece k + 1 UNDERNEATH the accumulation of piece k, like a stream
-    // of tasks does: the pieces alternate between this slot's SortBufs and the other slot's (which nobody uses while that
-    // slot is idle), sorts on sort_stream, one pair of events per buffer set.
-    bool pingpong = false;
+    // ping-pong tasks (sort.where)
     hipEvent_t ev_sorted_pp[2] = {nullptr, nullptr};   // piece's sort stage complete (index: piece & 1)
     hipEvent_t ev_acc_pp[2] = {nullptr, nullptr};      // the accumulation that read the piece's sort outputs is through
     bool acc_pp_recorded[2] = {false, false};
@@ -251,29 +269,20 @@ int msm_points_all_canonical(int format_id, const void* d_raw, uint64_t npts, ui
 int copy_words_to_pinned(void* host_pinned, const void* d_src, uint32_t dwords, hipStream_t st);
 size_t fq_bytes(int curve);
 size_t mont_point_bytes(int curve);  // stride of the Montgomery point array the pipeline reads (msm_impl.hip.hpp MONT_STRIDE)
-// The sort stages enqueue on C.sort_stream and fill C.B for the plan C.P; the scratch they share is the engine's.  Two-level LDS-privatised digit
-// sort (msm_sort.hip): msm_sort_lds fills count[]; after the caller's scan msm_sort_lds_scatter fills entries[] from the intermediate described by `pass`
-struct LdsSortPass {
-    uint32_t slices = 0, nc = 0;           // fine-pass work items (upper bound), coarse bins
-    int cl = 0;                            // log2 of the buckets per coarse bin
-    const uint16_t* inter_fine = nullptr;  // u16 fine digits of the sort intermediate (second half of `inter`)
-};
-int msm_sort_lds(MsmEngine& E, const MsmStep& C, const void* d_scalars, uint32_t npts, int sbits, LdsSortPass& pass);
-int msm_sort_lds_scatter(MsmEngine& E, const MsmStep& C, const LdsSortPass& pass);
-// three-level, small-footprint digit sort built to run underneath another task's k_accumulate (msm_sort3.hip): fills count[] and
-// entries[].  One family of kernels for plain plans and for window-table plans (P.table: shared bucket set, entries = point * W +
-// window).  msm_sort3_ok: does the plan qualify
+// The sort stage of a piece of np points (msm_sort_stage.hip): enqueues on C.sort_stream what C.S.sort names and fills C.B for the
+// plan C.P - count / off / unit_off / entries, the unit lists, `stats` and its pinned copy; the scratch the sorts share is the engine's
+int msm_sort_stage(MsmEngine& E, const MsmStep& C, const void* d_scalars, uint32_t np);
+void launch_zero(void* p, size_t n16, hipStream_t st);   // the stage's zero-fill (k_zero: 2048 blocks of 256) over n16 x 16 bytes
+// what plan_sort() asks the sorts (msm_sort.hpp has their entry points).  msm_sort3_ok: does the plan qualify for the three-level,
+// small-footprint digit sort built to run underneath another task's k_accumulate (msm_sort3.hip; plain and window-table plans)
 bool msm_sort3_ok(const MsmPlan& P, int sbits);
 int msm_sort3_max_vgprs(bool table);   // the largest register count among the kernels of that kind of plan (0 if unknown)
 int msm_sort3_max_lds(bool table);     // ... and the largest LDS allocation of one block, in bytes (0 if unknown)
 // do the hidden sort's blocks (sv VGPRs per lane, sl bytes of LDS per block) fit on a CU beside the accumulation's (av VGPRs,
-// al bytes of LDS per block of 128 lanes)?  msm.hip; a count that is not known (<= 0) is taken to fit.
+// al bytes of LDS per block of 128 lanes)?  msm_sort_stage.hip; a count that is not known (<= 0) is taken to fit.
 bool msm_sort_fits_beside(int av, int sv, int al, int sl);
-int msm_sort3(MsmEngine& E, const MsmStep& C, const void* d_scalars, uint32_t npts, int sbits);
-// the whole sort stage of a small task (digits, bucket scan, entries, unit lists, stats) in one block (msm_sort_tiny.hip)
+// ... and for the whole sort stage of a small task in one block (msm_sort_tiny.hip)
 bool msm_sort_tiny_ok(const MsmPlan& P, uint32_t npts, int sbits);
-int msm_sort_tiny(MsmEngine& E, const MsmStep& C, const void* d_scalars, uint32_t npts, int sbits, uint32_t max_units);
-int launch_fill_units(const MsmStep& C, uint32_t units);  // unit->bucket map + length-ordered unit list (at most `units` units)
 
 // per-curve entry points (one translation unit per curve: msm_<curve>.hip)
 struct MsmCurveOps {

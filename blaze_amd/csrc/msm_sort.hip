@@ -12,11 +12,11 @@
 //                     (k_coarse_scatter: the unstaged form, BLAZE_SORT_STAGED=0)
 //   k_slice_map       device-built work list: every coarse bin cut into slices of <= 65536 entries
 //   k_fine_count      per (coarse bin, slice): LDS histogram over the 2^cl fine buckets -> count[]
-//   (k_scan_* of msm.hip: bucket offsets + unit offsets)
+//   (k_scan_* of msm_sort_stage.hip: bucket offsets + unit offsets)
 //   k_fine_scatter    per (coarse bin, slice): LDS rank, reservation per (block, bucket) on the
 //                     scatter cursor, bucket-major LDS stage, slot-major copy-out to the final runs
 // HBM traffic: scalars read twice (32 B each), 8 B/entry written + read twice, 4 B/entry written.
-#include "msm_engine.hpp"
+#include "msm_sort.hpp"
 #include "msm_digits.hip.hpp"
 
 namespace blz {

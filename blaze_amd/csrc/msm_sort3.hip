@@ -11,7 +11,7 @@
 // writes pieces of 24 - 32 entries, 256 threads per block, wave priority raised (at equal priority the accumulation's
 // older waves starve the sort's).  Registers as compiled for gfx950: the plain plan's kernels <= 72 VGPRs
 // (k3_l1_scatter 72, k3_l3 70), the table plan's <= 78 (k3t_l3<true> 78, k3_l1_scatter 72, k3t_l3<false> 54).  The sort
-// hides only while msm_sort_fits_beside (msm.hip) holds: 2 x 200 + 72 = 472 of the 480 registers a SIMD hands
+// hides only while msm_sort_fits_beside (msm_sort_stage.hip) holds: 2 x 200 + 72 = 472 of the 480 registers a SIMD hands
 // out, and 2 x 200 + 80 (78 is allocated as 80) = 480 with nothing to spare; tests/test_isa_counts.py holds these bounds.
 // And its largest block's LDS (k3_l1_scatter: 83 KiB) beside the accumulation's four blocks per CU: 64 + 83 of 160 KiB.
 //
@@ -23,14 +23,14 @@
 //                  (index | sign : u32, low 14 bits of the bucket : u16) grouped by level-1 bin
 //   k3_l2_count / k3_l2_scatter   per slice of 4096 entries of a level-1 bin: 128-way split by the middle 7 bits;
 //                  out: (index | sign : u32, low 7 bits : u8) grouped by level-2 bin (= 128 consecutive buckets)
-//   k3_l3          one block per level-2 bin: bucket counts (-> count[], the scans of msm.hip turn them into off[] /
+//   k3_l3          one block per level-2 bin: bucket counts (-> count[], the scans of msm_sort_stage.hip turn them into off[] /
 //                  unit_off[]) and the bin's entries in bucket order, staged in LDS and written as one contiguous run
 //                  - the bin's position in entries[] is already final, no global bucket scan is needed before it
 // HBM traffic ~26 GB at 2^26 (the two-level sort: 18 GB) - it is hidden, what counts is that it is coalesced.
 // Same digits, same buckets as msm_sort.hip; the order of a bucket's entries differs (the group law does not care).
-// Used when another task of the handle is in flight (msm.hip run()); a task with nothing to hide under keeps the
+// Used when another task of the handle is in flight (msm_sort_stage.hip plan_sort(): "s3 hidden", "s3 pingpong"); a task with nothing to hide under keeps the
 // two-level sort, which is faster when it has the chip to itself.  BLAZE_SORT_HIDE = 0 never / 2 always (tests).
-#include "msm_engine.hpp"
+#include "msm_sort.hpp"
 #include "msm_digits.hip.hpp"
 
 namespace blz {

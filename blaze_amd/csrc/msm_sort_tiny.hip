@@ -10,8 +10,8 @@
 //   D  unit -> bucket map and the units in order of descending run length (counting sort over the <= L + 1 lengths), the
 //      length histogram k_combine_units reads, stats (units, largest bucket, entries)
 // Same outputs, bit for bit the same buckets as the big path (the order of a bucket's entries differs; the group law does
-// not care).  Chosen by msm.hip run() when msm_sort_tiny_ok().
-#include "msm_engine.hpp"
+// not care).  Chosen by plan_sort() (msm_sort_stage.hip: "tiny open") for a one-piece task with nothing to hide under when msm_sort_tiny_ok().
+#include "msm_sort.hpp"
 #include "msm_digits.hip.hpp"
 
 namespace blz {
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(TINY_THREADS) void k_sort_tiny(const uint32_t* __re
         }
     }
     __syncthreads();
-    // ---- B: scan.  Thread t owns the buckets [t chunk, (t + 1) chunk); (entries, units) packed in a u64 as in msm.hip
+    // ---- B: scan.  Thread t owns the buckets [t chunk, (t + 1) chunk); (entries, units) packed in a u64 as in msm_sort_stage.hip
     const uint32_t chunk = (G + TINY_THREADS - 1) / TINY_THREADS;
     const uint32_t g0 = tid * chunk, g1 = g0 + chunk < G ? g0 + chunk : G;
     uint64_t mine = 0;

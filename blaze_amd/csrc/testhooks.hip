@@ -1343,6 +1343,21 @@ int blz_test_msm_tail_plan(int curve, int repr, uint32_t npts, int sbits, int pi
     return BLZ_OK;
 }
 
+int blz_test_msm_sort_plan(int curve, int repr, uint32_t npts, int sbits, int pieces, int table_c, int bit_lo, int bit_hi, int hide_env, int other_busy,
+                           int recent_hot, int fits, char* text, size_t cap) {
+    if (!text || cap == 0) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
+    if (!msm_ops_for(curve, repr) || npts == 0) return fail(BLZ_ERR_INVALID_PARAM, "unknown curve %d or empty task", curve);
+    // the steps of MsmEngine::begin()
+    MsmPlan P;
+    BLZ_TRY(msm_task_plan(curve, npts, sbits, table_c, bit_lo, bit_hi, P, nullptr));
+    uint32_t per = 0;
+    pieces = msm_task_pieces(P, pieces, false, &per);
+    const std::string line = describe(plan_sort(P, npts, sbits, pieces, SortInputs{hide_env, other_busy != 0, recent_hot != 0, fits != 0}));
+    if (line.size() >= cap) return fail(BLZ_ERR_INVALID_PARAM, "text buffer of %zu bytes for a line of %zu", cap, line.size());
+    memcpy(text, line.c_str(), line.size() + 1);
+    return BLZ_OK;
+}
+
 int blz_test_law_layout(int curve, int repr, int law, uint32_t out[32]) {
     if (!out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
     LawLayout L;

@@ -61,6 +61,12 @@ int blz_test_ec_op(int device_id, int curve, int op, const uint8_t* p, const uin
  * L0<w32|rr|quad|row> L<..> ... finish[_row]".  A plan the kernels cannot serve is an error, as it is for the task. */
 int blz_test_msm_tail_plan(int curve, int repr, uint32_t npts, int sbits, int pieces, int table_c, int bit_lo, int bit_hi, uint32_t plan_out[8],
                            uint8_t* widths, char* text, size_t cap);
+/* The sort stage the same task gets in front of its accumulation (plan_sort()), from what begin() reads besides the plan: hide_env
+ * (BLAZE_SORT_HIDE, passed in - the environment is not read), other_busy (the handle's other slot holds a task), recent_hot (one of
+ * the last two collected tasks piled its entries into a few buckets), fits (the three-level sort's blocks fit beside the
+ * accumulation's), each 0 / 1.  Host only, no device.  text: "lds open" | "tiny open" | "s3 open" | "s3 hidden" | "s3 pingpong". */
+int blz_test_msm_sort_plan(int curve, int repr, uint32_t npts, int sbits, int pieces, int table_c, int bit_lo, int bit_hi, int hide_env, int other_busy,
+                           int recent_hot, int fits, char* text, size_t cap);
 
 /* The group laws of the MSM tail (ec_law.hip.hpp), element by element on RAW point images: what a law loads and stores, limb for limb.
  * law: 0 lane, 1 quad (a DPP quad per point), 2 row (a wave per point); repr as above.  A (curve, repr, law) the product does not

@@ -1327,7 +1327,7 @@ def test_dma_pieces_host_buffers(gpu, orc, curve, pf, n, monkeypatch):
 
 def test_lone_piecewise_task_sorts_under_its_own_accumulation(gpu, orc, monkeypatch):
     """A piecewise task on an otherwise idle handle sorts piece k + 1 on the sort stream underneath the accumulation of piece
-    k, its pieces alternating between its own slot's sort buffers and the other slot's (msm.hip begin(): ping-pong; which
+    k, its pieces alternating between its own slot's sort buffers and the other slot's (msm_sort_stage.hip plan_sort(): "s3 pingpong"; which
     buffer set and which stream a piece gets is MsmEngine::step()'s decision).  That path needs a plan the three-level sort
     accepts - every window of 15 bits or more - which default plans reach only from about 2^19 points up, so the small
     piecewise tests never take it.  Forced here at an oracle-checkable size: c=15 gives 5000 points 18 uniform windows and

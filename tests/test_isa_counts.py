@@ -81,7 +81,7 @@ def test_table_check_doubling_multiply_adds(disasm):
 
 def test_three_level_sort_register_counts():
     """The hidden digit sort (msm_sort3.hip) only runs BESIDE the accumulation while its kernels' registers fit next to
-    2 x 200 of k_accumulate's (MsmEngine::begin() sort_fits_beside: 400 + 72 = 472 for a plain plan, 400 + 80 = 480 - the limit
+    2 x 200 of k_accumulate's (plan_sort()'s `fits`, msm_sort_fits_beside: 400 + 72 = 472 for a plain plan, 400 + 80 = 480 - the limit
     - for a window-table plan, whose 78 are allocated as 80).  begin() degrades silently to sorting in the open when a kernel
     grows, so the shipped code object is held to the counts the hiding was measured with: plain-plan kernels <= 72 VGPRs,
     window-table kernels <= 78."""

@@ -1,5 +1,5 @@
 """Which kernels an MSM task launches, shape by shape: runs the shapes of tests/test_gpu_msm.py::test_every_tail_schedule_is_served
-and a few more (STEP_SHAPES) once each (one task at a time, an empty task - k_emit_infinity - in front of every shape as a separator) so that a kernel trace of
+and a few more (STEP_SHAPES; BURST_SHAPES, two tasks in flight) once each (one task at a time otherwise, an empty task - k_emit_infinity - in front of every shape as a separator) so that a kernel trace of
 the run can be cut into per-shape launch sequences and two builds of the library (BLAZE_HIP_LIB) compared:
 
     rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 tools/msm_tail_trace.py          (a run of its own, no counters)
@@ -38,7 +38,12 @@ STEP_SHAPES = [
     ("BLS381", 1, 5000, "c=15", "3"),
     ("BLS381", 1, 16, None, None),
 ]
-ALL_SHAPES = SHAPES + STEP_SHAPES
+# ... and a shape run as TWO tasks in flight: the second one's sort stage goes to the sort stream, underneath the first one's
+# accumulation ("s3 hidden" of plan_sort(); the first sorts in the open).  c = 15: the smallest forced plan the three-level sort accepts
+BURST_SHAPES = [
+    ("BLS381", 1, 5000, "c=15", None),
+]
+ALL_SHAPES = SHAPES + STEP_SHAPES + BURST_SHAPES
 MARKER = "k_emit_infinity"
 
 
@@ -52,15 +57,18 @@ def run_shapes():
     dc = DriverClient(0)
     rng = np.random.default_rng(2024)
 
-    def task(cl, pts, sc, n):
+    def submit(cl, pts, sc, n):
         p = MSMParams(n, None)
         cl.initialize(p)
         cl.start_process()
         cl.set_data(MSMInput(pts, sc, p))
-        cl.wait_result()
-        return cl.result().result
 
-    for curve, pf, n, plan, pieces in ALL_SHAPES:
+    def collect(cl):
+        cl.wait_result()
+        return bytes(cl.result().result)
+
+    for k, (curve, pf, n, plan, pieces) in enumerate(ALL_SHAPES):
+        in_flight = 2 if k >= len(SHAPES) + len(STEP_SHAPES) else 1
         for key, val in (("BLAZE_MSM_PLAN", plan), ("BLAZE_MSM_PIECES", pieces)):
             os.environ.pop(key, None)
             if val:
@@ -70,9 +78,12 @@ def run_shapes():
         sc = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
         sc[:, 31] &= 0x0F                                   # < 2^252: canonical in all three scalar fields
         cl = MSMClient(MSMInit(PointMemoryType.DMA, pf == 8, Curve[curve]), dc)
-        task(cl, b"", b"", 0)                               # the separator
-        res = task(cl, g * (n * pf), sc.tobytes(), n)
-        print(f"{curve} pf={pf} n={n} plan={plan} pieces={pieces}: result sha256 {hashlib.sha256(bytes(res)).hexdigest()[:16]}", flush=True)
+        submit(cl, b"", b"", 0)                             # the separator
+        collect(cl)
+        for _ in range(in_flight):
+            submit(cl, g * (n * pf), sc.tobytes(), n)
+        res = b"".join(collect(cl) for _ in range(in_flight))
+        print(f"{curve} pf={pf} n={n} plan={plan} pieces={pieces}: result sha256 {hashlib.sha256(res).hexdigest()[:16]}", flush=True)
         cl.close()
 
 
