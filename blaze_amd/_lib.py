@@ -139,6 +139,7 @@ _SIGS = {
     "blz_ntt_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     "blz_ntt_reset": (C.c_int, [C.c_void_p]),
     "blz_ntt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "blz_ntt_gate_eval": (C.c_int, [C.c_void_p, C.POINTER(BlzSumGate), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(C.c_uint64), C.c_uint64]),
     "blz_ntt_vec_op": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg)]),
     "blz_ntt_vec_reduce": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.c_void_p]),

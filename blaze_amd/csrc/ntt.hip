@@ -1066,20 +1066,17 @@ int blz_ntt_sumcheck_step(blz_ntt* h, uint32_t gate, const blz_vec_arg* a, const
     });
 }
 
-// The step for a caller-defined gate (ntt_gate.hip.hpp).  The description is checked and packed here - the longest term's
-// length F, each term's deficit F - nfactors, the close power - and travels to the kernel by value; the tables then walk
-// blz_ntt_sumcheck_step's protocol as tables[0 .. ntables).
-int blz_ntt_sumcheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* tables, const blz_vec_arg* r, uint32_t points, uint64_t len,
-                          void* d_out) {
-    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
-    if (!gate || !tables) return fail(BLZ_ERR_INVALID_PARAM, "a gate step takes %s", !gate ? "a gate: gate is NULL" : "the gate's tables: tables is NULL");
+// A caller-defined gate's description (blz_sum_gate), checked and packed for the kernels - the longest term's length F, each
+// term's deficit F - nfactors, the close power - for both entry points that take one: blz_ntt_sumcheck_gate and
+// blz_ntt_gate_eval.  g's tables are the caller's to resolve.
+extern "C++" {
+static int ntt_gate_describe(const blz_sum_gate* gate, NttGate& g) {
     if (gate->ntables < 1 || gate->ntables > BLZ_GATE_MAX_TABLES) return fail(BLZ_ERR_INVALID_PARAM, "gate: ntables %u is not in [1, %d]", gate->ntables, BLZ_GATE_MAX_TABLES);
     if (gate->nterms < 1 || gate->nterms > BLZ_GATE_MAX_TERMS) return fail(BLZ_ERR_INVALID_PARAM, "gate: nterms %u is not in [1, %d]", gate->nterms, BLZ_GATE_MAX_TERMS);
     if (gate->common < -1 || gate->common >= (int32_t)gate->ntables)
         return fail(BLZ_ERR_INVALID_PARAM, "gate: common %d is neither -1 nor a table index below ntables %u", gate->common, gate->ntables);
     if (gate->reserved != 0) return fail(BLZ_ERR_INVALID_PARAM, "gate: reserved must be 0");
-    const int nt = (int)gate->ntables;
-    NttGate g{};
+    g = NttGate{};
     g.ntables = gate->ntables;
     g.nterms = gate->nterms;
     g.common = gate->common;
@@ -1100,16 +1097,69 @@ int blz_ntt_sumcheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_ar
         for (uint32_t j = 0; j < t.nfactors; ++j) g.term[m] |= (uint32_t)t.factor[j] << (8 + 4 * j);
     }
     g.close_k = longest + (gate->common >= 0 ? 1u : 0u);
+    return BLZ_OK;
+}
+// the gate's tables as operands "tables[j]" that resolve into g.t[j]
+struct NttGateTables {
     char name[BLZ_GATE_MAX_TABLES][16];
     NttVecCall::Operand ops[BLZ_GATE_MAX_TABLES];
-    for (int j = 0; j < nt; ++j) {
-        snprintf(name[j], sizeof name[j], "tables[%d]", j);
-        ops[j] = {name[j], tables + j, &g.t[j]};
+    NttGateTables(NttGate& g, const blz_vec_arg* tables) {
+        for (uint32_t j = 0; j < g.ntables; ++j) {
+            snprintf(name[j], sizeof name[j], "tables[%u]", j);
+            ops[j] = {name[j], tables + j, &g.t[j]};
+        }
     }
+};
+}  // extern "C++"
+
+// The step for a caller-defined gate (ntt_gate.hip.hpp).  The description travels to the kernel by value; the tables then walk
+// blz_ntt_sumcheck_step's protocol as tables[0 .. ntables).
+int blz_ntt_sumcheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* tables, const blz_vec_arg* r, uint32_t points, uint64_t len,
+                          void* d_out) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (!gate || !tables) return fail(BLZ_ERR_INVALID_PARAM, "a gate step takes %s", !gate ? "a gate: gate is NULL" : "the gate's tables: tables is NULL");
+    NttGate g;
+    BLZ_TRY(ntt_gate_describe(gate, g));
+    const int nt = (int)gate->ntables;
+    NttGateTables t(g, tables);
     NttVecCall call{h};
-    return ntt_step_protocol(call, ops, nt, "", "", r, points, BLZ_GATE_MAX_POINTS, len, d_out, [&](const uint32_t* rw) {
+    return ntt_step_protocol(call, t.ops, nt, "", "", r, points, BLZ_GATE_MAX_POINTS, len, d_out, [&](const uint32_t* rw) {
         return h->ops->sumcheck_gate(h->stream, g, rw, points, len, (uint32_t*)d_out, call.ws);
     });
+}
+
+// The same description evaluated at every position (ntt_geval.hip.hpp): the first op that writes a destination from up to twelve
+// operands.  dst follows blz_ntt_vec_mle_fold's destination rule and may be one of the tables where a lane reads only the
+// position it writes: the table starts where dst starts, holds the len words and is not rotated.
+int blz_ntt_gate_eval(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* dst, const blz_vec_arg* tables, const uint64_t* rot, uint64_t len) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (!gate || !dst || !tables)
+        return fail(BLZ_ERR_INVALID_PARAM, "a gate evaluation takes %s", !gate ? "a gate: gate is NULL" : !dst ? "a destination: dst is NULL" : "the gate's tables: tables is NULL");
+    NttGate g;
+    BLZ_TRY(ntt_gate_describe(gate, g));
+    NttGateTables t(g, tables);
+    NttVecCall call{h};
+    if (len < 1 || len > call.n)
+        return fail(BLZ_ERR_INVALID_PARAM, "len %llu: a gate evaluation writes 1 <= len <= %llu words", (unsigned long long)len, (unsigned long long)call.n);
+    BLZ_TRY(call.begin());
+    BLZ_TRY(call.resolve(t.ops, g.ntables));
+    uint32_t* d = nullptr;
+    int buf = -1;
+    BLZ_TRY(call.destination(dst, len, d, buf));
+    uint64_t rots[BLZ_GATE_MAX_TABLES] = {};
+    for (uint32_t j = 0; j < g.ntables; ++j) {
+        if (rot) rots[j] = rot[j];
+        const uint64_t count = g.t[j].mask + 1;
+        if (!NttVecCall::words_meet(d, len, g.t[j].p, count)) continue;
+        if (g.t[j].p != d) return fail(BLZ_ERR_INVALID_PARAM, "dst overlaps the words of %s without starting where they start", t.name[j]);
+        if (count < len)
+            return fail(BLZ_ERR_INVALID_PARAM, "dst names the %llu words of %s, read periodically over len %llu: a periodic table cannot be written in place",
+                        (unsigned long long)count, t.name[j], (unsigned long long)len);
+        if (rots[j] != 0)
+            return fail(BLZ_ERR_INVALID_PARAM, "dst names the words of %s, which is rotated by %llu: a table written in place has rot 0", t.name[j],
+                        (unsigned long long)rots[j]);
+    }
+    return call.enqueue(buf, [&](uint32_t*) { return h->ops->gate_eval(h->stream, d, g, rots, len); });
 }
 
 int blz_ntt_last_kernel_ms(blz_ntt* h, float* out) {

@@ -162,6 +162,10 @@ struct NttFieldOps {
     // The same step for a caller-defined gate (blz_ntt_sumcheck_gate; kernels: ntt_gate.hip.hpp): g's tables take the place of
     // t[0 .. k) under the same rules, EVERY table of g is folded with r, points <= NTT_GATE_MAX_POINTS
     int (*sumcheck_gate)(hipStream_t st, const NttGate& g, const uint32_t* r, uint32_t points, uint64_t len, uint32_t* out, uint32_t* ws);
+    // The same description evaluated position by position (blz_ntt_gate_eval; kernel: ntt_geval.hip.hpp): dst[p] = G over table i
+    // read at (p + rot[i]) & g.t[i].mask, p < len; rot: g.ntables values; exactly len words are written.  A table may be dst
+    // itself where it starts at dst, holds at least len words and has rot 0; no other table word may lie in dst's len words
+    int (*gate_eval)(hipStream_t st, uint32_t* dst, const NttGate& g, const uint64_t* rot, uint64_t len);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

@@ -13,6 +13,7 @@
 #include "ntt_mle.hip.hpp"
 #include "ntt_sumcheck.hip.hpp"
 #include "ntt_gate.hip.hpp"
+#include "ntt_geval.hip.hpp"
 
 namespace blz {
 
@@ -531,6 +532,7 @@ NttFieldOps make_ntt_ops() {
     o.vec_mle_eq = &ntt_vec_mle_eq_t<Fr>;
     o.sumcheck_step = &ntt_sumcheck_step_t<Fr>;
     o.sumcheck_gate = &ntt_sumcheck_gate_t<Fr>;
+    o.gate_eval = &ntt_gate_eval_t<Fr>;
     return o;
 }
 

@@ -353,17 +353,10 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         self._vec_keep = (*tables, r, out)
         return out if points > 0 else None
 
-    def sumcheck_gate(self, tables, terms, common: Optional[int] = None, r: Optional[DeviceBuffer] = None, points: Optional[int] = None,
-                      length: Optional[int] = None, out: Optional[DeviceBuffer] = None) -> Optional[DeviceBuffer]:
-        """sumcheck_step for a caller-defined gate (blz_ntt_sumcheck_gate): G = tables[common] x sum of the signed products
-        `terms`, a list of (sign, [table indices]) - sign +1 / -1, 1 to 4 indices into `tables` (at most 12 ints / DeviceBuffers),
-        an index may repeat, `common` (None: no common factor) may also be a factor.  A vanilla PLONK zerocheck over
-        [eq, qL, qR, qM, qO, qC, a, b, c] is common=0, terms=[(1, [1, 6]), (1, [2, 7]), (1, [3, 6, 7]), (-1, [4, 8]), (1, [5])].
-        With `r` EVERY table is folded in place - named by a term or not - and out[t], t < points, is the round polynomial of
-        the folded tables; without `r` the round alone (nothing is written; periodic tables allowed, a constant selector is a
-        one-word DeviceBuffer).  points defaults to the gate's degree + 1 and is at most 6; points=0 (with r) binds only and
-        returns None.  length=None means the longest table named."""
-        tables, terms = list(tables), list(terms)
+    @staticmethod
+    def _sum_gate(tables, terms, common):
+        """The blz_sum_gate of (tables, terms, common) - sumcheck_gate's conventions, gate_eval's too - and its longest term's length"""
+        terms = list(terms)
         if len(tables) > GATE_MAX_TABLES or len(terms) > GATE_MAX_TERMS:
             raise ValueError(f"a gate takes at most {GATE_MAX_TABLES} tables and {GATE_MAX_TERMS} terms, {len(tables)} and {len(terms)} given")
         gate = BlzSumGate(len(tables), len(terms), -1 if common is None else int(common), 0)
@@ -376,6 +369,20 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
             for j, f in enumerate(factors[:GATE_MAX_FACTORS]):   # (a longer term is the library's to refuse: nfactors says so)
                 gate.term[m].factor[j] = f
             degree = max(degree, len(factors))
+        return gate, degree
+
+    def sumcheck_gate(self, tables, terms, common: Optional[int] = None, r: Optional[DeviceBuffer] = None, points: Optional[int] = None,
+                      length: Optional[int] = None, out: Optional[DeviceBuffer] = None) -> Optional[DeviceBuffer]:
+        """sumcheck_step for a caller-defined gate (blz_ntt_sumcheck_gate): G = tables[common] x sum of the signed products
+        `terms`, a list of (sign, [table indices]) - sign +1 / -1, 1 to 4 indices into `tables` (at most 12 ints / DeviceBuffers),
+        an index may repeat, `common` (None: no common factor) may also be a factor.  A vanilla PLONK zerocheck over
+        [eq, qL, qR, qM, qO, qC, a, b, c] is common=0, terms=[(1, [1, 6]), (1, [2, 7]), (1, [3, 6, 7]), (-1, [4, 8]), (1, [5])].
+        With `r` EVERY table is folded in place - named by a term or not - and out[t], t < points, is the round polynomial of
+        the folded tables; without `r` the round alone (nothing is written; periodic tables allowed, a constant selector is a
+        one-word DeviceBuffer).  points defaults to the gate's degree + 1 and is at most 6; points=0 (with r) binds only and
+        returns None.  length=None means the longest table named."""
+        tables = list(tables)
+        gate, degree = self._sum_gate(tables, terms, common)
         if points is None:
             points = degree + (common is not None) + 1
         points = int(points)
@@ -390,6 +397,30 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
                                           None if out is None else out.ptr))
         self._vec_keep = (*tables, r, out)
         return out if points > 0 else None
+
+    def gate_eval(self, dst, tables, terms, common: Optional[int] = None, rot=None, length: Optional[int] = None) -> None:
+        """A caller-defined gate evaluated position by position (blz_ntt_gate_eval): dst[p] = tables[common][p_c] x sum of the
+        signed products `terms`, for p < length, with table i read at p_i = (p + rot[i]) mod its count.  `tables` and `terms`
+        follow sumcheck_gate's conventions - ints (transform buffers) or DeviceBuffers of a power of two of words up to n, read
+        periodically (one word: a scalar); terms a list of (sign, [table indices]).  The PLONK quotient numerator over
+        [qL, qR, qM, qO, qC, a, b, c] is terms=[(1, [0, 5]), (1, [1, 6]), (1, [2, 5, 6]), (-1, [3, 7]), (1, [4])].  `rot` is one
+        integer per table (None: all zero), taken modulo 2^64: -1 reads the previous row.  `dst` is an int or a DeviceBuffer;
+        exactly `length` words of it (None: n) are written, every other byte keeps its value.  `dst` may be one of the tables -
+        dst <- dst + alpha a b is one op - if that table is not rotated.  Finished by wait_result()."""
+        tables = list(tables)
+        gate, _ = self._sum_gate(tables, terms, common)
+        args = (BlzVecArg * max(len(tables), 1))(*[self._vec_arg(x) for x in tables])
+        vd = self._vec_arg(dst)
+        rots = None
+        if rot is not None:
+            rot = [int(k) for k in rot]
+            if len(rot) != len(tables):
+                raise ValueError(f"rot holds one rotation per table: {len(rot)} for {len(tables)} tables")
+            rots = (C.c_uint64 * max(len(rot), 1))(*[k & 0xFFFFFFFFFFFFFFFF for k in rot])
+        if length is None:
+            length = 1 << self.log_size
+        check(lib().blz_ntt_gate_eval(self._h, C.byref(gate), None if vd is None else C.byref(vd), args, rots, int(length)))
+        self._vec_keep = (dst, *tables)
 
     def scalar(self, value: int) -> DeviceBuffer:
         """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""

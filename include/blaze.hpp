@@ -338,6 +338,13 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
         degree += gate.common >= 0 ? 1u : 0u;
         check(blz_ntt_sumcheck_gate(h_, &gate, tables, r, bind_only ? 0u : points ? points : degree + 1u, len, d_out));
     }
+    // the same description evaluated position by position (blz_ntt_gate_eval): dst[p] = the gate over table i read at
+    // (p + rot[i]) mod its count, p < len (1 .. n, any value); rot: gate.ntables host values or nullptr for all zero.  dst is
+    // buffer(i) or words(p, count) and may be a table that starts where it starts, holds len words and is not rotated; exactly
+    // len words are written
+    void gate_eval(const blz_sum_gate& gate, const blz_vec_arg* dst, const blz_vec_arg* tables, uint64_t len, const uint64_t* rot = nullptr) {
+        check(blz_ntt_gate_eval(h_, &gate, dst, tables, rot, len));
+    }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

@@ -768,6 +768,44 @@ typedef struct blz_sum_gate {
 } blz_sum_gate;
 int blz_ntt_sumcheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* tables, const blz_vec_arg* r, uint32_t points,
                           uint64_t len, void* d_out);
+/* The same description evaluated POSITION BY POSITION - the element-wise counterpart of the step above: for p < len
+ *     dst[p] = T[common][p_c] x sum_{m < nterms} (+/-) prod_{j < nfactors_m} T[factor_mj][p_mj]   (common == -1: the sum alone)
+ * with table i read at p_i = (p + rot[i]) & (count_i - 1).  One op where a chain of blz_ntt_vec_op calls - one product or sum
+ * each, every intermediate through a buffer - stood: the quotient numerator qL a + qR b + qM a b - qO c + qC on the 4n coset, a
+ * custom gate that reads the next row, the random linear combination sum_j gamma^j f_j in front of an opening, the table
+ * eq (Az Bz - Cz).  Arithmetic is over the handle's field and BY BUFFER POSITION: the bit-reversal flags and the coset shift play
+ * no part, as for every op on the buffers.
+ *   gate    blz_sum_gate as above: same layout, same limits, checked by the same code with the same messages.  A table index may
+ *           repeat within a term and across terms, common may also be a factor, a table no term names is not read.
+ *   tables  tables[0 .. ntables): operands as for blz_ntt_vec_op - a transform buffer, or `count` device words, a power of two
+ *           with 1 <= count <= n, read periodically.  A one-word table is a scalar (a challenge power, a constant selector);
+ *           four words carry 1 / Z_H on a 4x domain.  Messages name them tables[i].
+ *   rot     ntables host values, copied by the call, or NULL for all zero.  Any 64-bit value: the index is taken modulo count_i
+ *           in 64-bit arithmetic.  n - 1 reads the previous row, 4 on a 4n coset the next row of the n domain; the same words
+ *           under two table indices with two rotations are Z and Z(wX) in one gate.
+ *   dst     blz_ntt_vec_mle_fold's destination rule: a transform buffer, or the caller's device words (count a power of two,
+ *           len <= count <= n).  1 <= len <= n, any value, not only powers of two.  EXACTLY len words are written; every other
+ *           byte keeps its value (no zero fill).
+ *   In place: dst may be a table, if that table starts where dst starts, holds at least len words and has rot[i] == 0 - a lane
+ *           reads the position it owns before it writes it.  Every other meeting of a table's words with dst's len words is
+ *           refused.  So dst <- dst + alpha a b is one op, dst a one-factor term of its own gate.
+ *   Values: any 256-bit input word counts as its residue; every word written is canonical, little-endian.
+ *   Cost ("Gate evaluation"; derived from the code): per position a table's word is read once per time a
+ *   term or common names it (32 bytes from memory the first time, from cache after; a periodic table's from cache throughout)
+ *   and 32 bytes are written.  Montgomery products per position: f for every term of f >= 2 factors (f - 1 for the product, 1
+ *   for the constant R^f that takes the Montgomery powers off), none for a one-factor term, 2 for a common factor.  The PLONK
+ *   gate above, five terms of 2, 2, 3, 2, 1 factors and no common factor: 9 products, 8 x 32 bytes read, 32 written; a linear
+ *   combination of six: 12.
+ *   Protocol: enqueued on the compute stream, the call returns; blz_ntt_wait_result finishes it, blz_ntt_last_kernel_ms reports
+ *   it, blz_ntt_reset drops it.  While it is in flight the buffer written may not be read, written or exchanged, a buffer that is
+ *   only read may be read, and every transform, blz_ntt_set_coset and op on the buffers is refused.  Memory behind every device
+ *   pointer stays valid, and operands unwritten, until blz_ntt_wait_result returns; the description and rot are copied.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing and enqueueing nothing: a null handle (refused before any other argument is looked
+ *   at), a null gate, dst or tables, every description error of blz_ntt_sumcheck_gate, len of 0 or above n, an op in flight, any
+ *   operand error of blz_ntt_vec_op in a table or in dst, len above dst's count, a table that meets dst's len words without
+ *   starting where dst starts, or that starts there with count < len or with a nonzero rotation. */
+int blz_ntt_gate_eval(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* dst, const blz_vec_arg* tables, const uint64_t* rot,
+                      uint64_t len);
 
 /* ------------------------------------------------------------------ Poseidon octal Merkle tree (src/ingo_hash/poseidon_api.rs)
  *

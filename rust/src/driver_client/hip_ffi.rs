@@ -171,6 +171,8 @@ extern "C" {
     pub fn blz_ntt_result(h: *mut BlzNtt, buf: usize, out: *mut u8, out_cap: usize) -> c_int;
     pub fn blz_ntt_reset(h: *mut BlzNtt) -> c_int;
     pub fn blz_ntt_last_kernel_ms(h: *mut BlzNtt, out: *mut f32) -> c_int;
+    pub fn blz_ntt_gate_eval(h: *mut BlzNtt, gate: *const BlzSumGate, dst: *const BlzVecArg, tables: *const BlzVecArg, rot: *const u64,
+                             len: u64) -> c_int;
     pub fn blz_ntt_vec_op(h: *mut BlzNtt, op: c_int, buf_dst: usize, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg) -> c_int;
     pub fn blz_ntt_vec_reduce(h: *mut BlzNtt, op: c_int, a: *const BlzVecArg, b: *const BlzVecArg, d_out: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_scan(h: *mut BlzNtt, op: c_int, flags: u32, buf_dst: usize, a: *const BlzVecArg, d_total: *mut c_void) -> c_int;

@@ -333,7 +333,16 @@ impl NTTClient {
     /// As for `sumcheck_step`.
     pub unsafe fn sumcheck_gate(&self, tables: &[VecOperand], terms: &[(bool, &[u8])], common: Option<u8>, r: Option<VecOperand>, points: u32,
                                 len: u64, d_out: *mut std::os::raw::c_void) -> Result<()> {
-        let mut gate = BlzSumGate { ntables: tables.len() as u32, nterms: terms.len() as u32, common: common.map_or(-1, |c| c as i32), reserved: 0,
+        let gate = Self::sum_gate(tables.len(), terms, common);
+        let raw: Vec<BlzVecArg> = tables.iter().map(|x| x.raw()).collect();
+        let rr = r.map(|v| v.raw());
+        check(blz_ntt_sumcheck_gate(self.h, &gate, if raw.is_empty() { std::ptr::null() } else { raw.as_ptr() },
+                                    rr.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg), points, len, d_out))
+    }
+
+    /// The `blz_sum_gate` of `ntables` tables, `terms` and `common`, for `sumcheck_gate` and `gate_eval` alike
+    fn sum_gate(ntables: usize, terms: &[(bool, &[u8])], common: Option<u8>) -> BlzSumGate {
+        let mut gate = BlzSumGate { ntables: ntables as u32, nterms: terms.len() as u32, common: common.map_or(-1, |c| c as i32), reserved: 0,
                                     term: [BlzGateTerm::default(); BLZ_GATE_MAX_TERMS] };
         for (slot, (negate, factors)) in gate.term.iter_mut().zip(terms.iter()) {
             // a count the library refuses stays refusable: it is passed on, the indices that fit are copied
@@ -343,10 +352,30 @@ impl NTTClient {
                 *f = *t;
             }
         }
+        gate
+    }
+
+    /// The same description evaluated position by position (blz_ntt_gate_eval): `dst`\[p\] = T\[common\]\[p_c\] x the signed sum
+    /// of `terms` for p < `len` (1 ..= n, any value), table i read at p_i = (p + `rot`\[i\]) mod its count.  `tables` and `terms`
+    /// as for `sumcheck_gate`; a table is a transform buffer or a power of two of device words up to n, read periodically (one
+    /// word: a scalar).  `rot` holds one rotation per table (`None`: all zero; any u64, `u64::MAX` reads the previous row).
+    /// `dst` as for `vec_mle_fold`; exactly `len` words are written.  `dst` may be one of the tables if that table starts where
+    /// `dst` starts, holds `len` words and is not rotated: dst <- dst + alpha a b is one op.
+    ///
+    /// # Safety
+    /// As for `vec_mle_fold`: device words named by `dst` are WRITTEN, those named by `tables` read, until `wait_result` returns.
+    pub unsafe fn gate_eval(&self, dst: VecOperand, tables: &[VecOperand], terms: &[(bool, &[u8])], common: Option<u8>, rot: Option<&[u64]>,
+                            len: u64) -> Result<()> {
+        if let Some(k) = rot {
+            if k.len() != tables.len() {
+                return Err(DriverClientError::InvalidPrimitiveParam);
+            }
+        }
+        let gate = Self::sum_gate(tables.len(), terms, common);
         let raw: Vec<BlzVecArg> = tables.iter().map(|x| x.raw()).collect();
-        let rr = r.map(|v| v.raw());
-        check(blz_ntt_sumcheck_gate(self.h, &gate, if raw.is_empty() { std::ptr::null() } else { raw.as_ptr() },
-                                    rr.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg), points, len, d_out))
+        let rd = dst.raw();
+        check(blz_ntt_gate_eval(self.h, &gate, &rd, if raw.is_empty() { std::ptr::null() } else { raw.as_ptr() },
+                                rot.map_or(std::ptr::null(), |k| k.as_ptr()), len))
     }
 
     pub fn reset_engine(&self) -> Result<()> {
