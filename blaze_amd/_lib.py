@@ -58,6 +58,26 @@ class BlzSumGate(C.Structure):
                 ("term", BlzGateTerm * GATE_MAX_TERMS)]
 
 
+LIN_MAX_TABLES, LIN_MAX_FORMS, LIN_MAX_SUMMANDS, LIN_FORM, LIN_NO_COEF = 16, 8, 4, 0x80, 0xFF   # BLZ_LIN_* (include/blaze_hip.h)
+
+
+class BlzLinSummand(C.Structure):
+    """struct blz_lin_summand (include/blaze_hip.h), 4 bytes: (+/-) [T[coef] x] T[table]; coef LIN_NO_COEF is the coefficient 1."""
+    _fields_ = [("coef", C.c_uint8), ("table", C.c_uint8), ("negate", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+class BlzLinForm(C.Structure):
+    """struct blz_lin_form (include/blaze_hip.h), 20 bytes: a linear form over the tables, 1 to 4 summands."""
+    _fields_ = [("nsummands", C.c_uint8), ("reserved", C.c_uint8 * 3), ("summand", BlzLinSummand * LIN_MAX_SUMMANDS)]
+
+
+class BlzLinGate(C.Structure):
+    """struct blz_lin_gate (include/blaze_hip.h), 240 bytes: the gate blz_ntt_gate_eval_lin takes - blz_sum_gate whose factors and
+    common may be LIN_FORM | k, form k."""
+    _fields_ = [("ntables", C.c_uint32), ("nterms", C.c_uint32), ("common", C.c_int32), ("nforms", C.c_uint32),
+                ("term", BlzGateTerm * GATE_MAX_TERMS), ("form", BlzLinForm * LIN_MAX_FORMS)]
+
+
 class BlzVecCsr(C.Structure):
     """struct blz_vec_csr (include/blaze_hip.h): the sparse matrix blz_ntt_vec_spmv multiplies by, CSR arrays in device memory."""
     _fields_ = [("d_row_ptr", C.c_void_p), ("d_col", C.c_void_p), ("d_val", C.c_void_p), ("rows", C.c_uint64), ("nnz", C.c_uint64)]
@@ -140,6 +160,7 @@ _SIGS = {
     "blz_ntt_reset": (C.c_int, [C.c_void_p]),
     "blz_ntt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blz_ntt_gate_eval": (C.c_int, [C.c_void_p, C.POINTER(BlzSumGate), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(C.c_uint64), C.c_uint64]),
+    "blz_ntt_gate_eval_lin": (C.c_int, [C.c_void_p, C.POINTER(BlzLinGate), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(C.c_uint64), C.c_uint64]),
     "blz_ntt_vec_op": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg)]),
     "blz_ntt_vec_reduce": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.c_void_p]),

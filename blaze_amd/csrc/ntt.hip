@@ -1101,15 +1101,89 @@ static int ntt_gate_describe(const blz_sum_gate* gate, NttGate& g) {
 }
 // the gate's tables as operands "tables[j]" that resolve into g.t[j]
 struct NttGateTables {
-    char name[BLZ_GATE_MAX_TABLES][16];
-    NttVecCall::Operand ops[BLZ_GATE_MAX_TABLES];
-    NttGateTables(NttGate& g, const blz_vec_arg* tables) {
-        for (uint32_t j = 0; j < g.ntables; ++j) {
+    char name[BLZ_LIN_MAX_TABLES][16];
+    NttVecCall::Operand ops[BLZ_LIN_MAX_TABLES];
+    NttGateTables(NttGate& g, const blz_vec_arg* tables) : NttGateTables(g.t, g.ntables, tables) {}
+    NttGateTables(NttVecArg* t, uint32_t ntables, const blz_vec_arg* tables) {
+        for (uint32_t j = 0; j < ntables; ++j) {
             snprintf(name[j], sizeof name[j], "tables[%u]", j);
-            ops[j] = {name[j], tables + j, &g.t[j]};
+            ops[j] = {name[j], tables + j, &t[j]};
         }
     }
 };
+// An evaluated gate's in-place rule, for blz_ntt_gate_eval and blz_ntt_gate_eval_lin: rots[j] = rot[j] (rot NULL: 0), and a table
+// that meets the len words at d starts there, holds them all and is not rotated
+static int ntt_gate_in_place(const uint32_t* d, uint64_t len, const NttVecArg* t, const NttGateTables& names, uint32_t ntables, const uint64_t* rot,
+                             uint64_t* rots) {
+    for (uint32_t j = 0; j < ntables; ++j) {
+        rots[j] = rot ? rot[j] : 0;
+        const uint64_t count = t[j].mask + 1;
+        if (!NttVecCall::words_meet(d, len, t[j].p, count)) continue;
+        if (t[j].p != d) return fail(BLZ_ERR_INVALID_PARAM, "dst overlaps the words of %s without starting where they start", names.name[j]);
+        if (count < len)
+            return fail(BLZ_ERR_INVALID_PARAM, "dst names the %llu words of %s, read periodically over len %llu: a periodic table cannot be written in place",
+                        (unsigned long long)count, names.name[j], (unsigned long long)len);
+        if (rots[j] != 0)
+            return fail(BLZ_ERR_INVALID_PARAM, "dst names the words of %s, which is rotated by %llu: a table written in place has rot 0", names.name[j],
+                        (unsigned long long)rots[j]);
+    }
+    return BLZ_OK;
+}
+
+// A gate with linear-form factors (blz_lin_gate), checked and packed for k_lineval (NttLinGate).  Every form is checked, named
+// by a term or not; coef_tables gathers the coefficients of the forms that are named.  g's tables are the caller's to resolve.
+static int ntt_lin_gate_describe(const blz_lin_gate* gate, NttLinGate& g) {
+    if (gate->ntables < 1 || gate->ntables > BLZ_LIN_MAX_TABLES)
+        return fail(BLZ_ERR_INVALID_PARAM, "lin gate: ntables %u is outside [1, %d]", gate->ntables, BLZ_LIN_MAX_TABLES);
+    if (gate->nterms < 1 || gate->nterms > BLZ_GATE_MAX_TERMS)
+        return fail(BLZ_ERR_INVALID_PARAM, "lin gate: nterms %u is outside [1, %d]", gate->nterms, BLZ_GATE_MAX_TERMS);
+    if (gate->nforms > BLZ_LIN_MAX_FORMS) return fail(BLZ_ERR_INVALID_PARAM, "lin gate: nforms %u is above %d", gate->nforms, BLZ_LIN_MAX_FORMS);
+    // a factor byte or common: a table index below ntables, or BLZ_LIN_FORM | k with k below nforms
+    auto names = [&](uint32_t f) { return f < BLZ_LIN_FORM ? f < gate->ntables : f - BLZ_LIN_FORM < gate->nforms; };
+    if (gate->common != -1 && (gate->common < 0 || gate->common > 0xFF || !names((uint32_t)gate->common)))
+        return fail(BLZ_ERR_INVALID_PARAM, "lin gate: common %d is not -1, a table index below ntables %u or BLZ_LIN_FORM | k with k below nforms %u",
+                    gate->common, gate->ntables, gate->nforms);
+    g = NttLinGate{};
+    g.ntables = gate->ntables;
+    g.nterms = gate->nterms;
+    g.common = gate->common;
+    uint32_t used = gate->common >= (int32_t)BLZ_LIN_FORM ? 1u << (gate->common - BLZ_LIN_FORM) : 0u;   // the forms that are evaluated
+    for (uint32_t m = 0; m < gate->nterms; ++m) {
+        const blz_gate_term& t = gate->term[m];
+        if (t.nfactors < 1 || t.nfactors > BLZ_GATE_MAX_FACTORS)
+            return fail(BLZ_ERR_INVALID_PARAM, "lin gate: term[%u]: nfactors %u is outside [1, %d]", m, t.nfactors, BLZ_GATE_MAX_FACTORS);
+        if (t.negate > 1) return fail(BLZ_ERR_INVALID_PARAM, "lin gate: term[%u]: negate %u is neither 0 nor 1", m, t.negate);
+        if (t.reserved[0] != 0 || t.reserved[1] != 0) return fail(BLZ_ERR_INVALID_PARAM, "lin gate: term[%u]: a reserved byte is not 0", m);
+        g.term_hdr[m] = t.nfactors | (uint32_t)t.negate << 3;
+        for (uint32_t j = 0; j < t.nfactors; ++j) {
+            const uint32_t f = t.factor[j];
+            if (!names(f))
+                return f < BLZ_LIN_FORM ? fail(BLZ_ERR_INVALID_PARAM, "lin gate: term[%u]: factor %u names tables[%u], ntables is %u", m, j, f, gate->ntables)
+                                        : fail(BLZ_ERR_INVALID_PARAM, "lin gate: term[%u]: factor %u names form[%u], nforms is %u", m, j, f - BLZ_LIN_FORM, gate->nforms);
+            if (f >= BLZ_LIN_FORM) used |= 1u << (f - BLZ_LIN_FORM);
+            g.term_fac[m] |= f << (8 * j);
+        }
+    }
+    for (uint32_t k = 0; k < gate->nforms; ++k) {
+        const blz_lin_form& l = gate->form[k];
+        if (l.nsummands < 1 || l.nsummands > BLZ_LIN_MAX_SUMMANDS)
+            return fail(BLZ_ERR_INVALID_PARAM, "lin gate: form[%u]: nsummands %u is outside [1, %d]", k, l.nsummands, BLZ_LIN_MAX_SUMMANDS);
+        if (l.reserved[0] != 0 || l.reserved[1] != 0 || l.reserved[2] != 0) return fail(BLZ_ERR_INVALID_PARAM, "lin gate: form[%u]: a reserved byte is not 0", k);
+        g.form_n[k] = l.nsummands;
+        for (uint32_t s = 0; s < l.nsummands; ++s) {
+            const blz_lin_summand& x = l.summand[s];
+            if (x.table >= gate->ntables)
+                return fail(BLZ_ERR_INVALID_PARAM, "lin gate: form[%u]: summand %u names tables[%u], ntables is %u", k, s, x.table, gate->ntables);
+            if (x.coef != BLZ_LIN_NO_COEF && x.coef >= gate->ntables)
+                return fail(BLZ_ERR_INVALID_PARAM, "lin gate: form[%u]: summand %u takes its coefficient from tables[%u], ntables is %u", k, s, x.coef, gate->ntables);
+            if (x.negate > 1) return fail(BLZ_ERR_INVALID_PARAM, "lin gate: form[%u]: summand %u: negate %u is neither 0 nor 1", k, s, x.negate);
+            if (x.reserved != 0) return fail(BLZ_ERR_INVALID_PARAM, "lin gate: form[%u]: summand %u: the reserved byte is not 0", k, s);
+            g.form[k][s] = x.table | (uint32_t)x.coef << 8 | (uint32_t)x.negate << 16;
+            if (x.coef != BLZ_LIN_NO_COEF && ((used >> k) & 1u)) g.coef_tables |= 1u << x.coef;
+        }
+    }
+    return BLZ_OK;
+}
 }  // extern "C++"
 
 // The step for a caller-defined gate (ntt_gate.hip.hpp).  The description travels to the kernel by value; the tables then walk
@@ -1147,19 +1221,32 @@ int blz_ntt_gate_eval(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* d
     int buf = -1;
     BLZ_TRY(call.destination(dst, len, d, buf));
     uint64_t rots[BLZ_GATE_MAX_TABLES] = {};
-    for (uint32_t j = 0; j < g.ntables; ++j) {
-        if (rot) rots[j] = rot[j];
-        const uint64_t count = g.t[j].mask + 1;
-        if (!NttVecCall::words_meet(d, len, g.t[j].p, count)) continue;
-        if (g.t[j].p != d) return fail(BLZ_ERR_INVALID_PARAM, "dst overlaps the words of %s without starting where they start", t.name[j]);
-        if (count < len)
-            return fail(BLZ_ERR_INVALID_PARAM, "dst names the %llu words of %s, read periodically over len %llu: a periodic table cannot be written in place",
-                        (unsigned long long)count, t.name[j], (unsigned long long)len);
-        if (rots[j] != 0)
-            return fail(BLZ_ERR_INVALID_PARAM, "dst names the words of %s, which is rotated by %llu: a table written in place has rot 0", t.name[j],
-                        (unsigned long long)rots[j]);
-    }
+    BLZ_TRY(ntt_gate_in_place(d, len, g.t, t, g.ntables, rot, rots));
     return call.enqueue(buf, [&](uint32_t*) { return h->ops->gate_eval(h->stream, d, g, rots, len); });
+}
+
+// A gate whose factors may be linear forms, evaluated at every position (ntt_lineval.hip.hpp): blz_ntt_gate_eval's walk over
+// blz_lin_gate and up to sixteen tables.  The in-place rule looks at every table, whatever names it.
+int blz_ntt_gate_eval_lin(blz_ntt* h, const blz_lin_gate* gate, const blz_vec_arg* dst, const blz_vec_arg* tables, const uint64_t* rot, uint64_t len) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (!gate || !dst || !tables)
+        return fail(BLZ_ERR_INVALID_PARAM, "a gate evaluation with linear forms takes %s",
+                    !gate ? "a gate: gate is NULL" : !dst ? "a destination: dst is NULL" : "the gate's tables: tables is NULL");
+    NttLinGate g;
+    BLZ_TRY(ntt_lin_gate_describe(gate, g));
+    NttGateTables t(g.t, g.ntables, tables);
+    NttVecCall call{h};
+    if (len < 1 || len > call.n)
+        return fail(BLZ_ERR_INVALID_PARAM, "len %llu: a gate evaluation with linear forms writes 1 <= len <= %llu words", (unsigned long long)len,
+                    (unsigned long long)call.n);
+    BLZ_TRY(call.begin());
+    BLZ_TRY(call.resolve(t.ops, g.ntables));
+    uint32_t* d = nullptr;
+    int buf = -1;
+    BLZ_TRY(call.destination(dst, len, d, buf));
+    uint64_t rots[BLZ_LIN_MAX_TABLES] = {};
+    BLZ_TRY(ntt_gate_in_place(d, len, g.t, t, g.ntables, rot, rots));
+    return call.enqueue(buf, [&](uint32_t*) { return h->ops->gate_eval_lin(h->stream, d, g, rots, len); });
 }
 
 int blz_ntt_last_kernel_ms(blz_ntt* h, float* out) {

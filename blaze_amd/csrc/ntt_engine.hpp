@@ -87,6 +87,22 @@ struct NttGate {
     uint32_t term[NTT_GATE_MAX_TERMS];
     NttVecArg t[NTT_GATE_MAX_TABLES];
 };
+// The same with linear-form factors (blz_lin_gate, checked and packed by ntt.hip; kernel: ntt_lineval.hip.hpp).  A factor byte
+// below NTT_LIN_FORM is a table index, NTT_LIN_FORM | k is form k; common likewise, < 0: none.
+//   term_hdr[m] = nfactors | negate << 3, term_fac[m] = factor j << 8 j
+//   form_n[k] = nsummands, form[k][s] = table | coef << 8 | negate << 16 (coef NTT_LIN_NO_COEF: 1)
+//   coef_tables: bit i is set where table i is the coefficient of a summand of a form that a term or common names
+constexpr int NTT_LIN_MAX_TABLES = 16, NTT_LIN_MAX_FORMS = 8, NTT_LIN_MAX_SUMMANDS = 4;   // BLZ_LIN_MAX_*
+constexpr uint32_t NTT_LIN_FORM = 0x80, NTT_LIN_NO_COEF = 0xFF;
+struct NttLinGate {
+    uint32_t ntables, nterms;
+    int32_t common;
+    uint32_t coef_tables;
+    uint32_t term_hdr[NTT_GATE_MAX_TERMS], term_fac[NTT_GATE_MAX_TERMS];
+    uint32_t form_n[NTT_LIN_MAX_FORMS];
+    uint32_t form[NTT_LIN_MAX_FORMS][NTT_LIN_MAX_SUMMANDS];
+    NttVecArg t[NTT_LIN_MAX_TABLES];
+};
 constexpr int NTT_VEC_OPS = 6;              // enum blz_vec_op: ADD SUB MUL MULADD MULSUB INV
 constexpr uint64_t NTT_VEC_INV_TILE = 1024;  // batch inversion: elements per block (256 lanes x 4); one 32-byte total per tile
 constexpr int NTT_FOLD_OPS = 3;              // enum blz_fold_op: SUM DOT EVAL
@@ -166,6 +182,9 @@ struct NttFieldOps {
     // read at (p + rot[i]) & g.t[i].mask, p < len; rot: g.ntables values; exactly len words are written.  A table may be dst
     // itself where it starts at dst, holds at least len words and has rot 0; no other table word may lie in dst's len words
     int (*gate_eval)(hipStream_t st, uint32_t* dst, const NttGate& g, const uint64_t* rot, uint64_t len);
+    // A gate with linear-form factors evaluated position by position (blz_ntt_gate_eval_lin; kernel: ntt_lineval.hip.hpp):
+    // gate_eval's rules over NttLinGate; a table may be dst itself under the same rule whatever names it
+    int (*gate_eval_lin)(hipStream_t st, uint32_t* dst, const NttLinGate& g, const uint64_t* rot, uint64_t len);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

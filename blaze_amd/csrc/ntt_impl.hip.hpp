@@ -14,6 +14,7 @@
 #include "ntt_sumcheck.hip.hpp"
 #include "ntt_gate.hip.hpp"
 #include "ntt_geval.hip.hpp"
+#include "ntt_lineval.hip.hpp"
 
 namespace blz {
 
@@ -533,6 +534,7 @@ NttFieldOps make_ntt_ops() {
     o.sumcheck_step = &ntt_sumcheck_step_t<Fr>;
     o.sumcheck_gate = &ntt_sumcheck_gate_t<Fr>;
     o.gate_eval = &ntt_gate_eval_t<Fr>;
+    o.gate_eval_lin = &ntt_gate_eval_lin_t<Fr>;
     return o;
 }
 

@@ -6,11 +6,12 @@ import enum
 from dataclasses import dataclass
 from typing import Optional
 
-from ._lib import GATE_MAX_FACTORS, GATE_MAX_TABLES, GATE_MAX_TERMS, BlzSumGate, BlzVecArg, BlzVecCsr, BlzVecScatter, BlzVecView, DeviceBuffer, buf_ptr, check, lib
+from ._lib import GATE_MAX_FACTORS, GATE_MAX_TABLES, GATE_MAX_TERMS, LIN_FORM, LIN_MAX_FORMS, LIN_MAX_SUMMANDS, LIN_MAX_TABLES, LIN_NO_COEF, BlzLinGate, BlzSumGate, BlzVecArg, BlzVecCsr, BlzVecScatter, BlzVecView, DeviceBuffer, buf_ptr, check, lib
 from .driver_client import DriverClient, DriverPrimitive
 
 NTT_LOG_SIZE = 27  # ntt_data.rs:65: NTT_SIZE = 2^27
 NTT_WORD_SIZE = 32  # ntt_data.rs:66
+FORM = LIN_FORM  # BLZ_LIN_FORM: FORM + k as a factor or as common of NTTClient.gate_eval_lin names forms[k]
 VEC_INV_TILE = 1024  # csrc/ntt_engine.hpp NTT_VEC_INV_TILE: elements per block of NTTClient.vec_op(NTTClient.INV, ...)
 
 
@@ -354,11 +355,12 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         return out if points > 0 else None
 
     @staticmethod
-    def _sum_gate(tables, terms, common):
-        """The blz_sum_gate of (tables, terms, common) - sumcheck_gate's conventions, gate_eval's too - and its longest term's length"""
+    def _sum_gate(tables, terms, common, max_tables=GATE_MAX_TABLES):
+        """The blz_sum_gate of (tables, terms, common) - sumcheck_gate's conventions, gate_eval's too, and the terms of
+        gate_eval_lin, which allows more tables - and its longest term's length"""
         terms = list(terms)
-        if len(tables) > GATE_MAX_TABLES or len(terms) > GATE_MAX_TERMS:
-            raise ValueError(f"a gate takes at most {GATE_MAX_TABLES} tables and {GATE_MAX_TERMS} terms, {len(tables)} and {len(terms)} given")
+        if len(tables) > max_tables or len(terms) > GATE_MAX_TERMS:
+            raise ValueError(f"a gate takes at most {max_tables} tables and {GATE_MAX_TERMS} terms, {len(tables)} and {len(terms)} given")
         gate = BlzSumGate(len(tables), len(terms), -1 if common is None else int(common), 0)
         degree = 0
         for m, (sign, factors) in enumerate(terms):
@@ -398,6 +400,16 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         self._vec_keep = (*tables, r, out)
         return out if points > 0 else None
 
+    @staticmethod
+    def _rotations(rot, ntables):
+        """`rot` of gate_eval / gate_eval_lin as the C array: one integer per table, taken modulo 2^64; None stays None (all zero)"""
+        if rot is None:
+            return None
+        rot = [int(k) for k in rot]
+        if len(rot) != ntables:
+            raise ValueError(f"rot holds one rotation per table: {len(rot)} for {ntables} tables")
+        return (C.c_uint64 * max(len(rot), 1))(*[k & 0xFFFFFFFFFFFFFFFF for k in rot])
+
     def gate_eval(self, dst, tables, terms, common: Optional[int] = None, rot=None, length: Optional[int] = None) -> None:
         """A caller-defined gate evaluated position by position (blz_ntt_gate_eval): dst[p] = tables[common][p_c] x sum of the
         signed products `terms`, for p < length, with table i read at p_i = (p + rot[i]) mod its count.  `tables` and `terms`
@@ -411,15 +423,41 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         gate, _ = self._sum_gate(tables, terms, common)
         args = (BlzVecArg * max(len(tables), 1))(*[self._vec_arg(x) for x in tables])
         vd = self._vec_arg(dst)
-        rots = None
-        if rot is not None:
-            rot = [int(k) for k in rot]
-            if len(rot) != len(tables):
-                raise ValueError(f"rot holds one rotation per table: {len(rot)} for {len(tables)} tables")
-            rots = (C.c_uint64 * max(len(rot), 1))(*[k & 0xFFFFFFFFFFFFFFFF for k in rot])
+        rots = self._rotations(rot, len(tables))
         if length is None:
             length = 1 << self.log_size
         check(lib().blz_ntt_gate_eval(self._h, C.byref(gate), None if vd is None else C.byref(vd), args, rots, int(length)))
+        self._vec_keep = (dst, *tables)
+
+    def gate_eval_lin(self, dst, tables, forms, terms, common: Optional[int] = None, rot=None, length: Optional[int] = None) -> None:
+        """gate_eval with linear-form factors (blz_ntt_gate_eval_lin) - products of sums: dst[p] = C(p) x sum of the signed
+        products `terms`, where a factor, and `common`, is a table index or FORM + k, the value of forms[k].  `forms` is a list
+        of at most 8 forms; a form is a list of 1 to 4 summands (sign, coef, table): sign +1 / -1, `table` an index into
+        `tables`, `coef` the index of the table whose word multiplies it or None for 1.  `tables` holds at most 16 ints
+        (transform buffers) / DeviceBuffers, read periodically, with one rotation each in `rot` (None: all zero) whatever names
+        the index; a one-word coefficient (beta, gamma) costs one product per position, a longer one two; a constant is a
+        one-word table with coef None.  The numerator column prod_j (w_j + beta id_j + gamma) over [a, b, c, id1, id2, id3, beta,
+        gamma] is forms=[[(1, None, j), (1, 6, 3 + j), (1, None, 7)] for j in range(3)], terms=[(1, [FORM, FORM + 1, FORM + 2])].
+        `dst`, `length` and in place as for gate_eval: exactly `length` words (None: n) are written, and `dst` may be an
+        unrotated table that a factor, a summand or a coefficient names.  Finished by wait_result()."""
+        tables, forms = list(tables), [list(f) for f in forms]
+        if len(forms) > LIN_MAX_FORMS:
+            raise ValueError(f"a gate takes at most {LIN_MAX_FORMS} forms, {len(forms)} given")
+        sums, _ = self._sum_gate(tables, terms, common, LIN_MAX_TABLES)   # a factor FORM + k is a byte like any other
+        gate = BlzLinGate(sums.ntables, sums.nterms, sums.common, len(forms), sums.term)
+        for k, form in enumerate(forms):
+            gate.form[k].nsummands = min(len(form), 255)   # (a longer form is the library's to refuse)
+            for s, (sign, coef, table) in enumerate(form[:LIN_MAX_SUMMANDS]):
+                if sign not in (1, -1) or not 0 <= int(table) < 256 or not (coef is None or 0 <= int(coef) < LIN_NO_COEF):
+                    raise ValueError(f"form {k}, summand {s}: (sign, coef, table) with sign +1 or -1, coef None or a table index, table a table index")
+                x = gate.form[k].summand[s]
+                x.coef, x.table, x.negate = LIN_NO_COEF if coef is None else int(coef), int(table), int(sign < 0)
+        args = (BlzVecArg * max(len(tables), 1))(*[self._vec_arg(x) for x in tables])
+        vd = self._vec_arg(dst)
+        rots = self._rotations(rot, len(tables))
+        if length is None:
+            length = 1 << self.log_size
+        check(lib().blz_ntt_gate_eval_lin(self._h, C.byref(gate), None if vd is None else C.byref(vd), args, rots, int(length)))
         self._vec_keep = (dst, *tables)
 
     def scalar(self, value: int) -> DeviceBuffer:

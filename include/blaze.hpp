@@ -345,6 +345,12 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
     void gate_eval(const blz_sum_gate& gate, const blz_vec_arg* dst, const blz_vec_arg* tables, uint64_t len, const uint64_t* rot = nullptr) {
         check(blz_ntt_gate_eval(h_, &gate, dst, tables, rot, len));
     }
+    // gate_eval with linear-form factors (blz_ntt_gate_eval_lin) - products of sums: a factor byte of a term, and common, is a
+    // table index or BLZ_LIN_FORM | k, the value of gate.form[k] = sum of (+/-) [T[coef] x] T[table].  Up to 16 tables, one
+    // rotation per table index whatever names it; dst, len and in place as for gate_eval
+    void gate_eval_lin(const blz_lin_gate& gate, const blz_vec_arg* dst, const blz_vec_arg* tables, uint64_t len, const uint64_t* rot = nullptr) {
+        check(blz_ntt_gate_eval_lin(h_, &gate, dst, tables, rot, len));
+    }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

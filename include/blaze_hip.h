@@ -806,6 +806,90 @@ int blz_ntt_sumcheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_ar
  *   starting where dst starts, or that starts there with count < len or with a nonzero rotation. */
 int blz_ntt_gate_eval(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* dst, const blz_vec_arg* tables, const uint64_t* rot,
                       uint64_t len);
+/* Gate evaluation with LINEAR-FORM FACTORS - products of sums: a factor of a term, or the common factor, may be a linear form
+ * over the tables instead of a table word.  For p < len
+ *     dst[p] = C(p) x sum_{m < nterms} (+/-) prod_{j < nfactors_m} F_mj(p)                        (common == -1: the sum alone)
+ *     F, C   = a table word T[i][p_i], p_i = (p + rot[i]) & (count_i - 1), or the value of a form
+ *     L_k(p) = sum_{s < nsummands_k} (+/-) [ T[coef_s][p_coef] x ] T[table_s][p_table]
+ * One op and no temporaries where blz_ntt_gate_eval needs one call per factor w + beta sigma + gamma into caller memory and one
+ * more over the temporaries: the permutation argument's quotient term Z(wX) prod_j (w_j + beta sigma_j + gamma) -
+ * Z prod_j (w_j + beta k_j X + gamma), the numerator and denominator columns behind Z, the logUp denominator
+ * beta + sum_j gamma^j f_j, (Z - 1) L_1, a GKR layer add (x + y).  Arithmetic is over the handle's field and BY BUFFER POSITION:
+ * the bit-reversal flags and the coset shift play no part, as for every op on the buffers.
+ *   Layout (fixed; all fields little-endian, no padding):
+ *     blz_lin_summand, 4 bytes:  0 coef (BLZ_LIN_NO_COEF = 0xFF: coefficient 1; else a table index) | 1 table (a table index) |
+ *       2 negate (0: added, 1: subtracted) | 3 reserved, must be 0.
+ *     blz_lin_form, 20 bytes:  0 nsummands (1 .. BLZ_LIN_MAX_SUMMANDS = 4) | 1 reserved[3], must be 0 | 4 summand[4], the first
+ *       nsummands are read.
+ *     terms are blz_gate_term unchanged: a factor byte below BLZ_LIN_FORM (0x80) is a table index, BLZ_LIN_FORM | k is form k.
+ *     blz_lin_gate, 240 bytes:  0 ntables (1 .. BLZ_LIN_MAX_TABLES = 16) | 4 nterms (1 .. 8) | 8 common (-1, a table index, or
+ *       BLZ_LIN_FORM | k) | 12 nforms (0 .. BLZ_LIN_MAX_FORMS = 8) | 16 term[8], the first nterms are read | 80 form[8], the
+ *       first nforms are read.
+ *   An index may repeat anywhere: within a term and across terms, within a form and across forms; a coefficient may be the table
+ *   it multiplies (a square); a form may be named by several terms and as common; common may also be a factor.  A form that no
+ *   term names is still checked but not evaluated; a table that nothing evaluated names is not read.  A constant is a one-word
+ *   table with coef = BLZ_LIN_NO_COEF.  With nforms == 0 and ntables <= 12 the op writes the bytes blz_ntt_gate_eval writes.
+ *   The three-wire permutation term takes 13 tables - Z twice (two rotations), a, b, c, sigma1 .. sigma3, X, beta, beta k1,
+ *   beta k2, gamma -, six forms of three summands and two terms of four factors.
+ *   tables  tables[0 .. ntables): operands as for blz_ntt_vec_op - a transform buffer, or `count` device words, a power of two
+ *           with 1 <= count <= n, read periodically.  A one-word table is a scalar (a challenge power, a constant selector);
+ *           four words carry 1 / Z_H on a 4x domain.  Messages name them tables[i].
+ *   rot     ntables host values, copied by the call, or NULL for all zero: ONE rotation per table index, whatever names the
+ *           index - a factor, a summand's table, a summand's coefficient.  Any 64-bit value: the index is taken modulo count_i
+ *           in 64-bit arithmetic.  n - 1 reads the previous row, 4 on a 4n coset the next row of the n domain; the same words
+ *           under two table indices with two rotations are Z and Z(wX) in one gate.
+ *   dst     blz_ntt_vec_mle_fold's destination rule: a transform buffer, or the caller's device words (count a power of two,
+ *           len <= count <= n).  1 <= len <= n, any value, not only powers of two.  EXACTLY len words are written; every other
+ *           byte keeps its value (no zero fill).
+ *   In place: dst may be a table, if that table starts where dst starts, holds at least len words and has rot[i] == 0 - a lane
+ *           reads the position it owns before it writes it - whether the table is named as a factor, as a summand's table or
+ *           as a summand's coefficient.  Every other meeting of a table's words with dst's len words is refused.
+ *   Values: any 256-bit input word counts as its residue; every word written is canonical, little-endian.
+ *   Cost ("Gate evaluation with linear forms"; derived from the code): per position a table's word is read
+ *   once per time a term, a summand or common names it (32 bytes from memory the first time, from cache after; a periodic
+ *   table's from cache throughout; a ONE-WORD coefficient is read once per block, not per position), a form is evaluated once
+ *   per time it is named, and 32 bytes are written.  Montgomery products per position: per summand with a coefficient 1 if the
+ *   coefficient is a one-word table, 2 if it is longer, none without a coefficient; f for every term of f >= 2 factors, none
+ *   for a one-factor term; 2 for a common factor.  The permutation term above: 6 + 8 = 14 products, 9 x 32 bytes read (Z's second
+ *   reading comes from cache), 32 written; the logUp denominator beta + gamma f1 + gamma^2 f2 + gamma^3 f3: 3.
+ *   Protocol: enqueued on the compute stream, the call returns; blz_ntt_wait_result finishes it, blz_ntt_last_kernel_ms reports
+ *   it, blz_ntt_reset drops it.  While it is in flight the buffer written may not be read, written or exchanged, a buffer that is
+ *   only read may be read, and every transform, blz_ntt_set_coset and op on the buffers is refused.  Memory behind every device
+ *   pointer stays valid, and operands unwritten, until blz_ntt_wait_result returns; the description and rot are copied.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing and enqueueing nothing: a null handle (refused before any other argument is looked
+ *   at), a null gate, dst or tables, ntables outside 1 .. 16, nterms outside 1 .. 8, nforms above 8, common below -1 or neither
+ *   a table index below ntables nor BLZ_LIN_FORM | k with k below nforms, a term's nfactors outside 1 .. 4, a form's nsummands
+ *   outside 1 .. 4, negate above 1 in a term or a summand, a factor that is neither a table index below ntables nor a form
+ *   below nforms, a summand's table or coefficient (other than BLZ_LIN_NO_COEF) not below ntables, a nonzero reserved byte,
+ *   len of 0 or above n, an op in flight, any operand error of blz_ntt_vec_op in a table or in dst, len above dst's count, a
+ *   table that meets dst's len words without starting where dst starts, or that starts there with count < len or with a
+ *   nonzero rotation. */
+#define BLZ_LIN_MAX_TABLES   16
+#define BLZ_LIN_MAX_FORMS     8
+#define BLZ_LIN_MAX_SUMMANDS  4
+#define BLZ_LIN_FORM       0x80   /* in a factor byte or in common: BLZ_LIN_FORM | k names form k */
+#define BLZ_LIN_NO_COEF    0xFF   /* a summand's coef: the coefficient is 1 */
+typedef struct blz_lin_summand {
+    uint8_t coef;       /* BLZ_LIN_NO_COEF, or the table whose word multiplies the summand */
+    uint8_t table;      /* a table index */
+    uint8_t negate;     /* 0: the summand is added, 1: subtracted */
+    uint8_t reserved;   /* must be 0 */
+} blz_lin_summand;
+typedef struct blz_lin_form {
+    uint8_t nsummands;     /* 1 .. BLZ_LIN_MAX_SUMMANDS */
+    uint8_t reserved[3];   /* must be 0 */
+    blz_lin_summand summand[BLZ_LIN_MAX_SUMMANDS];   /* the first nsummands are read */
+} blz_lin_form;
+typedef struct blz_lin_gate {
+    uint32_t ntables;   /* 1 .. BLZ_LIN_MAX_TABLES */
+    uint32_t nterms;    /* 1 .. BLZ_GATE_MAX_TERMS */
+    int32_t common;     /* -1: none; a table index; or BLZ_LIN_FORM | k */
+    uint32_t nforms;    /* 0 .. BLZ_LIN_MAX_FORMS */
+    blz_gate_term term[BLZ_GATE_MAX_TERMS];   /* the first nterms are read */
+    blz_lin_form form[BLZ_LIN_MAX_FORMS];     /* the first nforms are read */
+} blz_lin_gate;
+int blz_ntt_gate_eval_lin(blz_ntt* h, const blz_lin_gate* gate, const blz_vec_arg* dst, const blz_vec_arg* tables,
+                          const uint64_t* rot, uint64_t len);
 
 /* ------------------------------------------------------------------ Poseidon octal Merkle tree (src/ingo_hash/poseidon_api.rs)
  *

@@ -88,6 +88,41 @@ pub struct BlzSumGate {
     pub reserved: u32,
     pub term: [BlzGateTerm; BLZ_GATE_MAX_TERMS],
 }
+/// The limits and marks of a gate with linear-form factors (`blz_ntt_gate_eval_lin`): tables, forms, summands per form; a factor
+/// byte (or `common`) `BLZ_LIN_FORM | k` names form k; a summand's `coef` `BLZ_LIN_NO_COEF` is the coefficient 1.
+pub const BLZ_LIN_MAX_TABLES: usize = 16;
+pub const BLZ_LIN_MAX_FORMS: usize = 8;
+pub const BLZ_LIN_MAX_SUMMANDS: usize = 4;
+pub const BLZ_LIN_FORM: u8 = 0x80;
+pub const BLZ_LIN_NO_COEF: u8 = 0xFF;
+/// `struct blz_lin_summand` (4 bytes): (+/-) \[T\[coef\] x\] T\[table\].
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct BlzLinSummand {
+    pub coef: u8,
+    pub table: u8,
+    pub negate: u8,
+    pub reserved: u8,
+}
+/// `struct blz_lin_form` (20 bytes): the signed sum of the first `nsummands` summands.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct BlzLinForm {
+    pub nsummands: u8,
+    pub reserved: [u8; 3],
+    pub summand: [BlzLinSummand; BLZ_LIN_MAX_SUMMANDS],
+}
+/// `struct blz_lin_gate` (240 bytes): `blz_sum_gate` whose factors and `common` may name one of the first `nforms` forms.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct BlzLinGate {
+    pub ntables: u32,
+    pub nterms: u32,
+    pub common: i32,
+    pub nforms: u32,
+    pub term: [BlzGateTerm; BLZ_GATE_MAX_TERMS],
+    pub form: [BlzLinForm; BLZ_LIN_MAX_FORMS],
+}
 
 pub const BLZ_COMM_ID_BYTES: usize = 128;
 
@@ -173,6 +208,8 @@ extern "C" {
     pub fn blz_ntt_last_kernel_ms(h: *mut BlzNtt, out: *mut f32) -> c_int;
     pub fn blz_ntt_gate_eval(h: *mut BlzNtt, gate: *const BlzSumGate, dst: *const BlzVecArg, tables: *const BlzVecArg, rot: *const u64,
                              len: u64) -> c_int;
+    pub fn blz_ntt_gate_eval_lin(h: *mut BlzNtt, gate: *const BlzLinGate, dst: *const BlzVecArg, tables: *const BlzVecArg, rot: *const u64,
+                                 len: u64) -> c_int;
     pub fn blz_ntt_vec_op(h: *mut BlzNtt, op: c_int, buf_dst: usize, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg) -> c_int;
     pub fn blz_ntt_vec_reduce(h: *mut BlzNtt, op: c_int, a: *const BlzVecArg, b: *const BlzVecArg, d_out: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_scan(h: *mut BlzNtt, op: c_int, flags: u32, buf_dst: usize, a: *const BlzVecArg, d_total: *mut c_void) -> c_int;

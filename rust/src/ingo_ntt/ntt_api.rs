@@ -378,6 +378,35 @@ impl NTTClient {
                                 rot.map_or(std::ptr::null(), |k| k.as_ptr()), len))
     }
 
+    /// `gate_eval` with linear-form factors (blz_ntt_gate_eval_lin) - products of sums.  A factor byte of `terms`, and `common`,
+    /// is a table index or `BLZ_LIN_FORM | k`, the value of `forms`\[k\]; a form is 1 to 4 summands `(negate, coef, table)`:
+    /// (+/-) \[T\[coef\] x\] T\[table\], `coef` `None` for 1.  At most 16 tables, 8 forms, 8 terms; `rot` holds one rotation per
+    /// table index, whatever names the index.  A one-word coefficient costs one product per position, a longer one two.
+    /// `dst`, `len` and in place as for `gate_eval`.
+    ///
+    /// # Safety
+    /// As for `gate_eval`.
+    pub unsafe fn gate_eval_lin(&self, dst: VecOperand, tables: &[VecOperand], forms: &[&[(bool, Option<u8>, u8)]], terms: &[(bool, &[u8])],
+                                common: Option<u8>, rot: Option<&[u64]>, len: u64) -> Result<()> {
+        if rot.map_or(false, |k| k.len() != tables.len()) || forms.len() > BLZ_LIN_MAX_FORMS || terms.len() > BLZ_GATE_MAX_TERMS {
+            return Err(DriverClientError::InvalidPrimitiveParam);
+        }
+        let sum = Self::sum_gate(tables.len(), terms, common);
+        let mut gate = BlzLinGate { ntables: sum.ntables, nterms: sum.nterms, common: sum.common, nforms: forms.len() as u32, term: sum.term,
+                                    form: [BlzLinForm::default(); BLZ_LIN_MAX_FORMS] };
+        for (slot, form) in gate.form.iter_mut().zip(forms.iter()) {
+            // a count the library refuses stays refusable: it is passed on, the summands that fit are copied
+            slot.nsummands = form.len().min(255) as u8;
+            for (x, (negate, coef, table)) in slot.summand.iter_mut().zip(form.iter()) {
+                *x = BlzLinSummand { coef: coef.unwrap_or(BLZ_LIN_NO_COEF), table: *table, negate: *negate as u8, reserved: 0 };
+            }
+        }
+        let raw: Vec<BlzVecArg> = tables.iter().map(|x| x.raw()).collect();
+        let rd = dst.raw();
+        check(blz_ntt_gate_eval_lin(self.h, &gate, &rd, if raw.is_empty() { std::ptr::null() } else { raw.as_ptr() },
+                                    rot.map_or(std::ptr::null(), |k| k.as_ptr()), len))
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
