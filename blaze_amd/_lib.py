@@ -161,6 +161,8 @@ _SIGS = {
     "blz_ntt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blz_ntt_gate_eval": (C.c_int, [C.c_void_p, C.POINTER(BlzSumGate), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(C.c_uint64), C.c_uint64]),
     "blz_ntt_gate_eval_lin": (C.c_int, [C.c_void_p, C.POINTER(BlzLinGate), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(C.c_uint64), C.c_uint64]),
+    "blz_ntt_zerocheck_gate": (C.c_int, [C.c_void_p, C.POINTER(BlzSumGate), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_uint32,
+                                         C.c_uint64, C.c_void_p]),
     "blz_ntt_vec_op": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg)]),
     "blz_ntt_vec_reduce": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.c_void_p]),

@@ -778,9 +778,15 @@ struct NttVecCall {
 // its name in a message ("a" / "tables[1]") and the slot it resolves to; one, two: what stands in front of one name and of a pair
 // ("table ", "tables " / nothing).  dispatch(r's word, or nullptr) launches.
 // blz_ntt_vec_mle_round does not come here: its points range, its flags and its operand rule are its own, and it binds nothing.
-template <class Dispatch>
+// extra: one more operand that is no table (blz_ntt_zerocheck_gate's weight), resolved behind r and kept off d_out as every
+// operand is, or NULL; after(r's word, or nullptr): its owner's rules, checked behind the tables' and before the enqueue.
+struct NttStepNoExtra {
+    int operator()(const uint32_t*) const { return BLZ_OK; }
+};
+template <class Dispatch, class After = NttStepNoExtra>
 int ntt_step_protocol(NttVecCall& call, const NttVecCall::Operand* tables, int k, const char* one, const char* two, const blz_vec_arg* r,
-                      uint32_t points, uint32_t max_points, uint64_t len, void* d_out, Dispatch&& dispatch) {
+                      uint32_t points, uint32_t max_points, uint64_t len, void* d_out, Dispatch&& dispatch, const NttVecCall::Operand* extra = nullptr,
+                      After&& after = After{}) {
     if (points > max_points) return fail(BLZ_ERR_INVALID_PARAM, "points %u is not in [0, %u]", points, max_points);
     if (points == 0 && (!r || d_out)) return fail(BLZ_ERR_INVALID_PARAM, "points 0 is a bind alone: it takes r and a NULL d_out");
     if (points > 0 && !d_out) return fail(BLZ_ERR_INVALID_PARAM, "null d_out");
@@ -789,11 +795,12 @@ int ntt_step_protocol(NttVecCall& call, const NttVecCall::Operand* tables, int k
     BLZ_TRY(call.live_length(len));
     if (r && points > 0 && len < 4) return fail(BLZ_ERR_INVALID_PARAM, "len %llu: a bind and a round need len >= 4", (unsigned long long)len);
     BLZ_TRY(call.begin());
-    NttVecCall::Operand ops[BLZ_GATE_MAX_TABLES + 1];   // the tables and r; blz_ntt_sumcheck_step's four fit
+    NttVecCall::Operand ops[BLZ_GATE_MAX_TABLES + 2];   // the tables, r and the extra operand; blz_ntt_sumcheck_step's four fit
     NttVecArg vr{};
     std::copy_n(tables, k, ops);
     ops[k] = {"r", r, &vr};
-    BLZ_TRY(call.resolve(ops, (size_t)k + 1, "d_out", d_out, points));
+    if (extra) ops[k + 1] = *extra;
+    BLZ_TRY(call.resolve(ops, (size_t)k + (extra ? 2 : 1), "d_out", d_out, points));
     int wbuf[2] = {-1, -1};
     if (r) {
         const uint64_t half = len >> 1;
@@ -811,6 +818,7 @@ int ntt_step_protocol(NttVecCall& call, const NttVecCall::Operand* tables, int k
             if (!ops[j].v->d_ptr) wbuf[wbuf[0] < 0 ? 0 : 1] = (int)ops[j].v->buf;
         }
     }
+    BLZ_TRY(after(r ? vr.p : nullptr));
     return call.enqueue(wbuf[0], [&](uint32_t*) { return dispatch(r ? vr.p : nullptr); }, wbuf[1]);
 }
 }  // extern "C++"
@@ -1099,6 +1107,9 @@ static int ntt_gate_describe(const blz_sum_gate* gate, NttGate& g) {
     g.close_k = longest + (gate->common >= 0 ? 1u : 0u);
     return BLZ_OK;
 }
+// blz_ntt_zerocheck_gate's gate is blz_ntt_sumcheck_gate's - same struct, same limits, same messages: the same function under the
+// name of the third entry point that takes one
+static constexpr auto ntt_zerocheck_describe = &ntt_gate_describe;
 // the gate's tables as operands "tables[j]" that resolve into g.t[j]
 struct NttGateTables {
     char name[BLZ_LIN_MAX_TABLES][16];
@@ -1200,6 +1211,42 @@ int blz_ntt_sumcheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_ar
     return ntt_step_protocol(call, t.ops, nt, "", "", r, points, BLZ_GATE_MAX_POINTS, len, d_out, [&](const uint32_t* rw) {
         return h->ops->sumcheck_gate(h->stream, g, rw, points, len, (uint32_t*)d_out, call.ws);
     });
+}
+
+// The gate step of a zerocheck (ntt_zerocheck.hip.hpp): blz_ntt_sumcheck_gate's walk with the weight as the protocol's extra
+// operand.  The weight is the caller's device words and no table: it is summed, not folded, so its rules are checked here, behind
+// the tables' - with r it holds the len / 2 words the step reads, they meet no table's first len words, and r is outside the
+// len / 4 it receives.  (d_out is off all its words in every mode: the protocol's d_ptr-operand rule.)
+int blz_ntt_zerocheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* tables, const blz_vec_arg* weight, const blz_vec_arg* r,
+                           uint32_t points, uint64_t len, void* d_out) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (!gate || !tables || !weight)
+        return fail(BLZ_ERR_INVALID_PARAM, "a zerocheck step takes %s",
+                    !gate ? "a gate: gate is NULL" : !tables ? "the gate's tables: tables is NULL" : "a weight table: weight is NULL");
+    NttGate g;
+    BLZ_TRY(ntt_zerocheck_describe(gate, g));
+    if (points == 0)
+        return fail(BLZ_ERR_INVALID_PARAM, "points 0: a zerocheck step takes a round; the bind alone has no weight and is blz_ntt_sumcheck_gate's");
+    if (!weight->d_ptr) return fail(BLZ_ERR_INVALID_PARAM, "operand weight: the weight is device words (d_ptr != NULL), not a transform buffer");
+    const int nt = (int)gate->ntables;
+    NttGateTables t(g, tables);
+    NttVecCall call{h};
+    NttVecArg vw{};
+    const NttVecCall::Operand w{"weight", weight, &vw};
+    return ntt_step_protocol(
+        call, t.ops, nt, "", "", r, points, BLZ_GATE_MAX_POINTS, len, d_out,
+        [&](const uint32_t* rw) { return h->ops->zerocheck_gate(h->stream, g, vw, rw, points, len, (uint32_t*)d_out, call.ws); }, &w,
+        [&](const uint32_t* rw) {
+            if (!rw) return (int)BLZ_OK;
+            if (vw.mask + 1 < len / 2)
+                return fail(BLZ_ERR_INVALID_PARAM, "operand weight: %llu words, a step with r sums len / 2 = %llu", (unsigned long long)(vw.mask + 1),
+                            (unsigned long long)(len / 2));
+            for (int j = 0; j < nt; ++j)
+                if (NttVecCall::words_meet(vw.p, len / 2, g.t[j].p, len))
+                    return fail(BLZ_ERR_INVALID_PARAM, "the weight's first len / 2 words meet the first len words of %s, which is folded in place", t.name[j]);
+            if (NttVecCall::words_meet(rw, 1, vw.p, len / 4)) return fail(BLZ_ERR_INVALID_PARAM, "r lies in the words the weight receives");
+            return (int)BLZ_OK;
+        });
 }
 
 // The same description evaluated at every position (ntt_geval.hip.hpp): the first op that writes a destination from up to twelve

@@ -185,6 +185,11 @@ struct NttFieldOps {
     // A gate with linear-form factors evaluated position by position (blz_ntt_gate_eval_lin; kernel: ntt_lineval.hip.hpp):
     // gate_eval's rules over NttLinGate; a table may be dst itself under the same rule whatever names it
     int (*gate_eval_lin)(hipStream_t st, uint32_t* dst, const NttLinGate& g, const uint64_t* rot, uint64_t len);
+    // sumcheck_gate's step with a summed weight table beside the gate (blz_ntt_zerocheck_gate; kernel: ntt_zerocheck.hip.hpp):
+    // 1 <= points; w: device words.  With r it holds at least len / 2 words clear of every table's first len, and its first
+    // len / 4 are written, W[q] += W[q + len / 4]; without r it is read at p & w.mask
+    int (*zerocheck_gate)(hipStream_t st, const NttGate& g, NttVecArg w, const uint32_t* r, uint32_t points, uint64_t len, uint32_t* out,
+                          uint32_t* ws);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

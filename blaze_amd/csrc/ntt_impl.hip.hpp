@@ -13,6 +13,7 @@
 #include "ntt_mle.hip.hpp"
 #include "ntt_sumcheck.hip.hpp"
 #include "ntt_gate.hip.hpp"
+#include "ntt_zerocheck.hip.hpp"
 #include "ntt_geval.hip.hpp"
 #include "ntt_lineval.hip.hpp"
 
@@ -535,6 +536,7 @@ NttFieldOps make_ntt_ops() {
     o.sumcheck_gate = &ntt_sumcheck_gate_t<Fr>;
     o.gate_eval = &ntt_gate_eval_t<Fr>;
     o.gate_eval_lin = &ntt_gate_eval_lin_t<Fr>;
+    o.zerocheck_gate = &ntt_zerocheck_gate_t<Fr>;
     return o;
 }
 

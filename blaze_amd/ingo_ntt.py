@@ -400,6 +400,35 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         self._vec_keep = (*tables, r, out)
         return out if points > 0 else None
 
+    def zerocheck_gate(self, tables, terms, weight: DeviceBuffer, common: Optional[int] = None, r: Optional[DeviceBuffer] = None,
+                       points: Optional[int] = None, length: Optional[int] = None, out: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """The gate step of a zerocheck sum_p eq(tau, p) G(p) (blz_ntt_zerocheck_gate): sumcheck_gate with the equality table out
+        of the gate and the summed weight table `weight` in its place.  `tables`, `terms`, `common` follow sumcheck_gate's
+        conventions and describe G alone.  `weight` is a DeviceBuffer of a power of two of words - for round 0 what
+        vec_mle_eq(weight, point, m - 1) writes, half the tables' length.  Without `r` out[t] = sum_p weight[p] G(pair p at t),
+        p < length / 2 (the weight may be periodic), and nothing else is written.  With `r` every table is folded in place, the
+        weight's first length / 4 words become weight[q] + weight[q + length / 4] - the next round's weight, no product - and
+        out[t] is the weighted round polynomial of the folded tables; the weight holds at least length / 2 words.  out is u_i of
+        s_i(X) = c_i eq(tau_{m-1-i}, X) u_i(X): the caller multiplies the linear factor back in.  points defaults to the gate's
+        degree + 1 - nothing is added for the weight - and is 1 to 6; a zerocheck's last op, the bind alone, is
+        sumcheck_gate(points=0).  length=None means the longest table named."""
+        tables = list(tables)
+        gate, degree = self._sum_gate(tables, terms, common)
+        if points is None:
+            points = degree + (common is not None) + 1
+        points = int(points)
+        if out is None:
+            out = DeviceBuffer(self.driver_client.id, NTT_WORD_SIZE * max(points, 1))
+        args = (BlzVecArg * max(len(tables), 1))(*[self._vec_arg(x) for x in tables])
+        vw, vr = self._vec_arg(weight), self._vec_arg(r)
+        if length is None:
+            n = 1 << self.log_size
+            length = max([x.nbytes // NTT_WORD_SIZE if isinstance(x, DeviceBuffer) else n for x in tables] or [0])
+        check(lib().blz_ntt_zerocheck_gate(self._h, C.byref(gate), args, None if vw is None else C.byref(vw), None if vr is None else C.byref(vr),
+                                           points, int(length), out.ptr))
+        self._vec_keep = (*tables, weight, r, out)
+        return out
+
     @staticmethod
     def _rotations(rot, ntables):
         """`rot` of gate_eval / gate_eval_lin as the C array: one integer per table, taken modulo 2^64; None stays None (all zero)"""

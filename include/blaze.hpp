@@ -338,6 +338,18 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
         degree += gate.common >= 0 ? 1u : 0u;
         check(blz_ntt_sumcheck_gate(h_, &gate, tables, r, bind_only ? 0u : points ? points : degree + 1u, len, d_out));
     }
+    // the gate step of a zerocheck (blz_ntt_zerocheck_gate): sumcheck_gate with eq out of the gate and the summed weight table
+    // `weight` - device words, for round 0 vec_mle_eq over m - 1 variables - in its place.  Without r: d_out[t] = sum_p W[p] G(pair
+    // p at t); with r every table is folded in place, W[q] += W[q + len / 4] for q < len / 4, and d_out is the weighted round of
+    // the folded tables: u_i of s_i(X) = c_i eq(tau_{m-1-i}, X) u_i(X).  points defaults to the gate's degree + 1, nothing added
+    // for the weight; there is no bind alone (that is sumcheck_gate's)
+    void zerocheck_gate(const blz_sum_gate& gate, const blz_vec_arg* tables, const blz_vec_arg& weight, const blz_vec_arg* r, uint64_t len, void* d_out,
+                        uint32_t points = 0) {
+        uint32_t degree = 0;
+        for (uint32_t m = 0; m < gate.nterms && m < BLZ_GATE_MAX_TERMS; ++m) degree = gate.term[m].nfactors > degree ? gate.term[m].nfactors : degree;
+        degree += gate.common >= 0 ? 1u : 0u;
+        check(blz_ntt_zerocheck_gate(h_, &gate, tables, &weight, r, points ? points : degree + 1u, len, d_out));
+    }
     // the same description evaluated position by position (blz_ntt_gate_eval): dst[p] = the gate over table i read at
     // (p + rot[i]) mod its count, p < len (1 .. n, any value); rot: gate.ntables host values or nullptr for all zero.  dst is
     // buffer(i) or words(p, count) and may be a table that starts where it starts, holds len words and is not rotated; exactly

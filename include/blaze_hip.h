@@ -890,6 +890,49 @@ typedef struct blz_lin_gate {
 } blz_lin_gate;
 int blz_ntt_gate_eval_lin(blz_ntt* h, const blz_lin_gate* gate, const blz_vec_arg* dst, const blz_vec_arg* tables,
                           const uint64_t* rot, uint64_t len);
+/* The gate step of a ZEROCHECK, sum_p eq(tau, p) G(p) = 0 - blz_ntt_sumcheck_gate with the equality table taken out of the gate
+ * and a SUMMED WEIGHT TABLE in its place (the eq-factor trick).  With top-variable pairing (p = sum x_i 2^i, round i binds
+ * x_{m-1-i}; tau_i pairs with bit i as in blz_ntt_vec_mle_eq) the round polynomial factors:
+ *     s_i(X) = c_i eq(tau_{m-1-i}, X) u_i(X),    u_i(X) = sum_p W_i[p] G(X, p),    eq(a, X) = a X + (1 - a)(1 - X),
+ *     W_i = eq(tau_0 .. tau_{m-2-i}, .), 2^{m-1-i} words, the same for every X;   c_0 = 1, c_{i+1} = c_i eq(tau_{m-1-i}, r_i).
+ * The op computes u_i: the degree of G, one below s_i, so one point fewer, and the weight multiplies the gate's sum once per
+ * point.  The next weight is a SUM, not a fold by r - W_{i+1}[q] = W_i[q] + W_i[q + len / 4], since eq(tau, 0) + eq(tau, 1) = 1 -
+ * and costs no product.  Reconstruction, on the host, O(points) per round: s_i(t) = c_i eq(tau_{m-1-i}, t) u_i(t) at the points
+ * t = 0 .. points - 1, one more value of u_i by extrapolation (u_i has degree below points), then c_{i+1} from r_i.
+ *   gate, tables   exactly blz_ntt_sumcheck_gate's: same struct, same limits, checked by the same code with the same messages.
+ *           common stays available and counts as before.
+ *   weight  required: the caller's device words, d_ptr != NULL, count a power of two in [1, n].  A transform buffer is refused.
+ *           W_0 is blz_ntt_vec_mle_eq(point, m - 1) on the point buffer of the whole zerocheck: half the table.
+ *   r == NULL - the first round: d_out[t] = sum_{p < len / 2} W[p & (count - 1)] G(.. lo_j + t (hi_j - lo_j) ..) for t < points,
+ *     over the pairs (T[p], T[p + len / 2]).  Nothing is written besides d_out; periodic tables and a periodic weight are
+ *     allowed.  len >= 2.
+ *   r != NULL - bind, then round: every table is folded in place exactly as by blz_ntt_sumcheck_gate; W[q] <- W[q] + W[q + len / 4]
+ *     for q < len / 4 - EXACTLY len / 4 weight words are written, every other byte of the weight keeps its value; then
+ *       d_out[t] = sum_{q < len / 4} W[q] G(.., T_j[q] + t (T_j[q + len / 4] - T_j[q]), ..) over the folded tables and the new W.
+ *     weight.count >= len / 2, len >= 4.
+ *   1 <= points <= BLZ_GATE_MAX_POINTS.  points == 0 is refused: a bind alone has no weight, so a zerocheck's last op is
+ *   blz_ntt_sumcheck_gate with points == 0.  An m-variable zerocheck is blz_ntt_vec_mle_eq(W, point, m - 1), one step without r at
+ *   len = n, m - 1 steps with r, then that bind: m + 2 ops.
+ *   Values: any 256-bit input word counts as its residue; every word written - table words, weight words and d_out - is
+ *   canonical, little-endian.
+ *   Cost ("Zerocheck step"; products derived from the code): blz_ntt_sumcheck_gate's count with `points`
+ *   products for the weight in place of the 2 + points of a common eq table, at one point fewer: W (Az Bz - Cz) at 3 points is
+ *   6 + 3 + 2 + 3 = 14 per quad where eq (Az Bz - Cz) at 4 is 18; the PLONK gate over its eight tables at 4 points 50 where nine
+ *   tables at 5 cost 58.  The weight's traffic is len / 2 words read and len / 4 written where eq's is len read, len / 2 written.
+ *   Protocol, in-flight rules and operand checks: blz_ntt_sumcheck_gate's, by the same code; everything is checked before
+ *   anything is enqueued; one blz_ntt_wait_result.  Memory behind every pointer stays valid until it returns.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing and enqueueing nothing, in this order: a null handle (refused before any other
+ *   argument is looked at); a null gate, tables or weight; every description error of blz_ntt_sumcheck_gate; points == 0; a
+ *   weight that names a buffer (d_ptr == NULL); then everything blz_ntt_sumcheck_gate refuses, in its order - points above 6, a
+ *   null d_out, r naming a buffer or with count != 1, len not a power of two in [2, n] ([4, n] with r), an op in flight, any
+ *   operand error of blz_ntt_vec_op in a table, in r or in the weight (messages name it `weight`), a bad d_out or one that
+ *   overlaps a d_ptr operand - the weight's words, all `count` of them, included, in every mode; with r: a table with
+ *   count < len, two tables whose first len words overlap, r inside the words a table receives, d_out inside the first len
+ *   words of a table; and last, with r, the weight's own: count below len / 2, weight words [0, len / 2) meeting a table's first
+ *   len words, r inside weight words [0, len / 4).  (d_out inside weight words [0, len / 2) is refused by the d_ptr-operand
+ *   rule.) */
+int blz_ntt_zerocheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* tables, const blz_vec_arg* weight,
+                           const blz_vec_arg* r, uint32_t points, uint64_t len, void* d_out);
 
 /* ------------------------------------------------------------------ Poseidon octal Merkle tree (src/ingo_hash/poseidon_api.rs)
  *

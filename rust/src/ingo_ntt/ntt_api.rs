@@ -340,6 +340,23 @@ impl NTTClient {
                                     rr.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg), points, len, d_out))
     }
 
+    /// The gate step of a zerocheck (blz_ntt_zerocheck_gate): `sumcheck_gate` with eq out of the gate and the summed `weight`
+    /// table - device words, for round 0 `vec_mle_eq` over m - 1 variables - in its place.  Without `r`: `d_out`\[t\] =
+    /// sum_p W\[p\] G(pair p at t).  With `r` every table is folded in place, W\[q\] += W\[q + len / 4\] for q < len / 4 (no
+    /// product), and `d_out` is the weighted round of the folded tables: u_i of s_i(X) = c_i eq(tau_{m-1-i}, X) u_i(X), one point
+    /// fewer than with eq as `common`.  `points` is 1 ..= 6; the bind alone stays `sumcheck_gate`'s.
+    ///
+    /// # Safety
+    /// As for `sumcheck_step`; with `r` the first len / 4 words of `weight` are written.
+    pub unsafe fn zerocheck_gate(&self, tables: &[VecOperand], terms: &[(bool, &[u8])], weight: VecOperand, common: Option<u8>, r: Option<VecOperand>,
+                                 points: u32, len: u64, d_out: *mut std::os::raw::c_void) -> Result<()> {
+        let gate = Self::sum_gate(tables.len(), terms, common);
+        let raw: Vec<BlzVecArg> = tables.iter().map(|x| x.raw()).collect();
+        let (rw, rr) = (weight.raw(), r.map(|v| v.raw()));
+        check(blz_ntt_zerocheck_gate(self.h, &gate, if raw.is_empty() { std::ptr::null() } else { raw.as_ptr() }, &rw,
+                                     rr.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg), points, len, d_out))
+    }
+
     /// The `blz_sum_gate` of `ntables` tables, `terms` and `common`, for `sumcheck_gate` and `gate_eval` alike
     fn sum_gate(ntables: usize, terms: &[(bool, &[u8])], common: Option<u8>) -> BlzSumGate {
         let mut gate = BlzSumGate { ntables: ntables as u32, nterms: terms.len() as u32, common: common.map_or(-1, |c| c as i32), reserved: 0,
