@@ -163,6 +163,8 @@ _SIGS = {
     "blz_ntt_gate_eval_lin": (C.c_int, [C.c_void_p, C.POINTER(BlzLinGate), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(C.c_uint64), C.c_uint64]),
     "blz_ntt_zerocheck_gate": (C.c_int, [C.c_void_p, C.POINTER(BlzSumGate), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_uint32,
                                          C.c_uint64, C.c_void_p]),
+    "blz_ntt_mle_tree": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg),
+                                   C.POINTER(BlzVecArg), C.c_uint64]),
     "blz_ntt_vec_op": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg)]),
     "blz_ntt_vec_reduce": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.c_void_p]),
@@ -327,11 +329,34 @@ class DeviceBuffer:
             lib().blz_device_free(self.device_id, self.ptr)
             self.ptr = None
 
+    def view(self, offset_bytes: int, nbytes: int) -> "DeviceBuffer":
+        """`nbytes` bytes of this allocation from `offset_bytes` on, as a buffer that owns nothing: it keeps this one alive, its
+        free() does nothing, upload / download work, and it is an operand wherever a DeviceBuffer is (the library takes pointers
+        into an allocation) - a layer of NTTClient.mle_tree's output as a table of a step op."""
+        if offset_bytes < 0 or nbytes < 0 or offset_bytes + nbytes > self.nbytes:
+            raise ValueError(f"view [{offset_bytes}, {offset_bytes + nbytes}) is outside the buffer's {self.nbytes} bytes")
+        if not self.ptr:
+            raise ValueError("view of a freed buffer")
+        return _DeviceView(self, offset_bytes, nbytes)
+
     def __del__(self):
         try:
             self.free()
         except Exception:
             pass
+
+
+class _DeviceView(DeviceBuffer):
+    """DeviceBuffer.view's result: a range of its parent's bytes"""
+
+    def __init__(self, parent: DeviceBuffer, offset_bytes: int, nbytes: int):
+        self.device_id = parent.device_id
+        self.nbytes = nbytes
+        self.ptr = parent.ptr + offset_bytes
+        self.parent = parent
+
+    def free(self):
+        pass
 
 
 class HostBuffer:

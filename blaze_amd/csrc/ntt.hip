@@ -731,12 +731,12 @@ struct NttVecCall {
 
     // A destination that may be the caller's device words (the multilinear ops): an operand's checks - a transform buffer, or
     // `count` device words, a power of two up to n - and room for the out_len words the op writes from its start.  buf: the
-    // transform buffer it names, -1 for device words
-    int destination(const blz_vec_arg* v, uint64_t out_len, uint32_t*& words, int& buf) {
+    // transform buffer it names, -1 for device words; name: what the messages call it (an op with a second destination)
+    int destination(const blz_vec_arg* v, uint64_t out_len, uint32_t*& words, int& buf, const char* name = "dst") {
         NttVecArg d{};
-        BLZ_TRY(operand("dst", v, d, n));
+        BLZ_TRY(operand(name, v, d, n));
         if (d.mask + 1 < out_len)
-            return fail(BLZ_ERR_INVALID_PARAM, "operand dst: count %llu is below the %llu words the op writes", (unsigned long long)(d.mask + 1),
+            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: count %llu is below the %llu words the op writes", name, (unsigned long long)(d.mask + 1),
                         (unsigned long long)out_len);
         words = const_cast<uint32_t*>(d.p);
         buf = v->d_ptr ? -1 : (int)v->buf;
@@ -1294,6 +1294,42 @@ int blz_ntt_gate_eval_lin(blz_ntt* h, const blz_lin_gate* gate, const blz_vec_ar
     uint64_t rots[BLZ_LIN_MAX_TABLES] = {};
     BLZ_TRY(ntt_gate_in_place(d, len, g.t, t, g.ntables, rot, rots));
     return call.enqueue(buf, [&](uint32_t*) { return h->ops->gate_eval_lin(h->stream, d, g, rots, len); });
+}
+
+// Product and fraction trees (ntt_tree.hip.hpp): every layer under len words, len - 1 words into each destination by
+// blz_ntt_vec_mle_fold's destination rule.  The first op with two destinations: both may be transform buffers (enqueue's
+// buf_dst2).  A later launch reads what an earlier one wrote, so there is no in-place form: a destination meets neither the words
+// read of a source nor the other destination.
+int blz_ntt_mle_tree(blz_ntt* h, uint32_t op, uint32_t flags, const blz_vec_arg* dst, const blz_vec_arg* dst_q, const blz_vec_arg* a,
+                     const blz_vec_arg* a_q, uint64_t len) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (op != BLZ_TREE_PROD && op != BLZ_TREE_FRAC) return fail(BLZ_ERR_INVALID_PARAM, "unknown tree op %u", op);
+    if (flags & ~BLZ_MLE_LOW) return fail(BLZ_ERR_INVALID_PARAM, "unknown multilinear flags 0x%x", flags);
+    const bool frac = op == BLZ_TREE_FRAC;
+    if (!dst || !a || (dst_q != nullptr) != frac || (a_q != nullptr) != frac)
+        return fail(BLZ_ERR_INVALID_PARAM, "%s", frac ? "a fraction tree takes dst, dst_q, a and a_q" : "a product tree takes dst and a, and dst_q and a_q must be NULL");
+    NttVecCall call{h};
+    BLZ_TRY(call.live_length(len));
+    BLZ_TRY(call.begin());
+    NttVecArg src[2] = {};
+    BLZ_TRY(call.resolve({{"a", a, &src[0]}, {"a_q", a_q, &src[1]}}));
+    const uint64_t out_len = len - 1;
+    const int k = frac ? 2 : 1;
+    const blz_vec_arg* const dv[2] = {dst, dst_q};
+    static const char* const dname[2] = {"dst", "dst_q"};
+    static const char* const sname[2] = {"a", "a_q"};
+    uint32_t* d[2] = {nullptr, nullptr};
+    int buf[2] = {-1, -1};
+    for (int i = 0; i < k; ++i) {
+        BLZ_TRY(call.destination(dv[i], out_len, d[i], buf[i], dname[i]));
+        for (int j = 0; j < k; ++j)
+            if (NttVecCall::words_meet(d[i], out_len, src[j].p, std::min(src[j].mask + 1, len)))
+                return fail(BLZ_ERR_INVALID_PARAM, "%s overlaps the words read of %s: a tree is not built in place", dname[i], sname[j]);
+    }
+    if (frac && NttVecCall::words_meet(d[0], out_len, d[1], out_len)) return fail(BLZ_ERR_INVALID_PARAM, "dst and dst_q overlap in the words they receive");
+    // enqueue's first buffer is the one it hands out and may not be -1 beside a second: a lone buffer goes first
+    if (buf[0] < 0) std::swap(buf[0], buf[1]);
+    return call.enqueue(buf[0], [&](uint32_t*) { return h->ops->mle_tree(h->stream, op, flags, d[0], d[1], src[0], src[1], len); }, buf[1]);
 }
 
 int blz_ntt_last_kernel_ms(blz_ntt* h, float* out) {

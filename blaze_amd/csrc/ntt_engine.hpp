@@ -190,6 +190,11 @@ struct NttFieldOps {
     // len / 4 are written, W[q] += W[q + len / 4]; without r it is read at p & w.mask
     int (*zerocheck_gate)(hipStream_t st, const NttGate& g, NttVecArg w, const uint32_t* r, uint32_t points, uint64_t len, uint32_t* out,
                           uint32_t* ws);
+    // Product and fraction trees (blz_ntt_mle_tree; kernels and the layout: ntt_tree.hip.hpp): every layer of the binary tree
+    // under the len = 2^m >= 2 words of a (read at p & mask), a layer of s words at word len - 2s of dst, len - 1 words in all.
+    // op: enum blz_tree_op; BLZ_TREE_FRAC carries (a, a_q) to (dst, dst_q), BLZ_TREE_PROD ignores both _q; flags: BLZ_MLE_LOW.
+    // No destination word may be a word the op reads of a source, nor one of the other destination's
+    int (*mle_tree)(hipStream_t st, uint32_t op, uint32_t flags, uint32_t* dst, uint32_t* dst_q, NttVecArg a, NttVecArg a_q, uint64_t len);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

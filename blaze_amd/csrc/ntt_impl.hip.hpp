@@ -16,6 +16,7 @@
 #include "ntt_zerocheck.hip.hpp"
 #include "ntt_geval.hip.hpp"
 #include "ntt_lineval.hip.hpp"
+#include "ntt_tree.hip.hpp"
 
 namespace blz {
 
@@ -537,6 +538,7 @@ NttFieldOps make_ntt_ops() {
     o.gate_eval = &ntt_gate_eval_t<Fr>;
     o.gate_eval_lin = &ntt_gate_eval_lin_t<Fr>;
     o.zerocheck_gate = &ntt_zerocheck_gate_t<Fr>;
+    o.mle_tree = &ntt_mle_tree_t<Fr>;
     return o;
 }
 

@@ -48,6 +48,7 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
     HORNER_EXCLUSIVE, HORNER_REVERSE = 1, 2         # BLZ_HORNER_*
     MLE_LOW = 1                                     # BLZ_MLE_LOW
     GATE_PRODUCT, GATE_R1CS = 0, 1                  # BLZ_GATE_*
+    TREE_PROD, TREE_FRAC = 0, 1                     # enum blz_tree_op
 
     def __init__(self, _ptype: NTT, dclient: DriverClient, log_size: int = NTT_LOG_SIZE, inverse: bool = False,
                  field: str = "BLS381", flags: int = 0, root: Optional[int] = None):
@@ -488,6 +489,29 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
             length = 1 << self.log_size
         check(lib().blz_ntt_gate_eval_lin(self._h, C.byref(gate), None if vd is None else C.byref(vd), args, rots, int(length)))
         self._vec_keep = (dst, *tables)
+
+    @staticmethod
+    def tree_layer(length: int, k: int):
+        """(word offset, words) of layer k, 1 <= k <= log2(length), in a destination of mle_tree: layer 1 at 0, layer 2 at
+        length / 2, the root at length - 2"""
+        length, k = int(length), int(k)
+        if length < 2 or length & (length - 1) or not 1 <= k < length.bit_length():
+            raise ValueError(f"layer {k} of a tree over {length} words: length is 2^m >= 2 and 1 <= k <= m")
+        return length - (length >> (k - 1)), length >> k
+
+    def mle_tree(self, dst, a, op: int = TREE_PROD, length: Optional[int] = None, low: bool = False, dst_q=None, a_q=None) -> None:
+        """Every layer of the product or fraction tree under a multilinear table (blz_ntt_mle_tree).  Layer 0 is `a`, `length`
+        = 2^m words of it (None: all of it), read periodically; layer k holds length / 2^k words and lands at tree_layer(length,
+        k) of `dst`: length - 1 words are written, every other byte keeps its value.  (lo, hi) = (L[p], L[p + size / 2]) - the
+        top variable, so the halves of a layer are views (DeviceBuffer.view) the step ops take as tables - or, low=True,
+        (L[2p], L[2p + 1]).  TREE_PROD: L'[p] = lo hi, a grand product.  TREE_FRAC: numerators `a` -> `dst` and denominators
+        `a_q` -> `dst_q`, (P, Q)' = (P_lo Q_hi + P_hi Q_lo, Q_lo Q_hi) - logUp's sum of fractions, never inverted; a one-word `a`
+        holding 1 is the numerator of sum 1 / (beta + f).  Operands are ints (transform buffers) or DeviceBuffers; a destination
+        may not overlap a source or the other destination.  Finished by wait_result()."""
+        args = [self._vec_arg(x) for x in (dst, dst_q, a, a_q)]
+        check(lib().blz_ntt_mle_tree(self._h, int(op), self.MLE_LOW if low else 0, *[None if v is None else C.byref(v) for v in args],
+                                     self._mle_len(length, *[x for x in (a, a_q) if x is not None] or [0])))
+        self._vec_keep = (dst, dst_q, a, a_q)
 
     def scalar(self, value: int) -> DeviceBuffer:
         """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""

@@ -363,6 +363,16 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
     void gate_eval_lin(const blz_lin_gate& gate, const blz_vec_arg* dst, const blz_vec_arg* tables, uint64_t len, const uint64_t* rot = nullptr) {
         check(blz_ntt_gate_eval_lin(h_, &gate, dst, tables, rot, len));
     }
+    // every layer of the product (BLZ_TREE_PROD) or fraction (BLZ_TREE_FRAC) tree under the len = 2^m words of a
+    // (blz_ntt_mle_tree): layer k, len / 2^k words, at word tree_layer(len, k) of dst, len - 1 words in all; pairs (L[p],
+    // L[p + size / 2]), or (L[2p], L[2p + 1]) with BLZ_MLE_LOW.  FRAC carries (a, a_q) to (dst, dst_q) by (P_lo Q_hi + P_hi Q_lo,
+    // Q_lo Q_hi); PROD takes neither _q.  A destination is buffer(i) or words(p, count) and meets no source and not the other one
+    void mle_tree(uint32_t op, const blz_vec_arg* dst, const blz_vec_arg* a, uint64_t len, uint32_t flags = 0, const blz_vec_arg* dst_q = nullptr,
+                  const blz_vec_arg* a_q = nullptr) {
+        check(blz_ntt_mle_tree(h_, op, flags, dst, dst_q, a, a_q, len));
+    }
+    // the word offset of layer k (1 .. m) in a destination of mle_tree; the layer holds len >> k words
+    static uint64_t tree_layer(uint64_t len, uint32_t k) { return len - (len >> (k - 1)); }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

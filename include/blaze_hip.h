@@ -768,6 +768,35 @@ typedef struct blz_sum_gate {
 } blz_sum_gate;
 int blz_ntt_sumcheck_gate(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* tables, const blz_vec_arg* r, uint32_t points,
                           uint64_t len, void* d_out);
+/* PRODUCT AND FRACTION TREES over a multilinear table: every layer of the binary tree under len = 2^m words, in one op - what a
+ * GKR-style argument builds before its first sumcheck.  Layer 0 is the source, read at p & (count - 1); layer k, 1 <= k <= m,
+ * holds len / 2^k words, with (lo, hi) = (L_k[p], L_k[p + size_k / 2]) - the top variable, the pairing of the step ops - or
+ * (L_k[2p], L_k[2p + 1]) with BLZ_MLE_LOW:
+ *   BLZ_TREE_PROD  L_{k+1}[p] = lo hi: the grand product of a permutation or memory check (HyperPlonk, Quarks, Spartan, Lasso).
+ *                  Takes dst and a; dst_q and a_q are NULL.
+ *   BLZ_TREE_FRAC  pairs (P, Q): P' = P_lo Q_hi + P_hi Q_lo, Q' = Q_lo Q_hi - the sum of fractions of logUp-GKR down to ONE
+ *                  fraction, never inverted and with no special case for a zero denominator.  P from a to dst, Q from a_q to
+ *                  dst_q; all four are required.  A one-word a holding 1 is the numerator of sum 1 / (beta + f).
+ *   Layout: layer k sits at word len - len / 2^(k - 1) of its destination - layer 1 at 0, layer 2 at len / 2, the root at
+ *   len - 2.  EXACTLY len - 1 words are written; word len - 1 and everything behind it keep their bytes.  With the default
+ *   pairing the two halves of a layer are contiguous power-of-two runs of device words: blz_ntt_sumcheck_gate and the other step
+ *   ops take them as tables (d_ptr into the destination) unchanged.
+ *   len = 2^m, 2 <= len <= n (blz_ntt_vec_mle_fold's live length).  Sources: operands as for blz_ntt_vec_op, periodic ones allowed.
+ *   Destinations: blz_ntt_vec_mle_fold's destination rule with len - 1 words written - a transform buffer, or the caller's
+ *   device words, count a power of two with len - 1 <= count <= n; both may be the two transform buffers.  A destination may not meet
+ *   the words the op reads of any source (min(count, len)), nor the other destination's len - 1 words: there is no in-place form.
+ *   Values: any 256-bit input word counts as its residue; every word written is canonical, little-endian.
+ *   Cost ("Product and fraction trees"; derived from the code): 2 Montgomery products per PROD node, 5 per
+ *   FRAC node; the leaves are read once and a launch keeps 3 (PROD) or 2 (FRAC) layers in registers: about 2.14 len words moved
+ *   for PROD, 4.67 len for FRAC.  No workspace.
+ *   Protocol, in-flight rules and operand checks: blz_ntt_vec_mle_fold's, by the same code; a destination buffer is the buffer
+ *   written.  BLZ_ERR_INVALID_PARAM, changing nothing and enqueueing nothing: a null handle (refused before any other argument
+ *   is looked at), an unknown op, unknown flag bits, a missing or surplus operand for the op, len not 2^m in [2, n], an op in
+ *   flight, any operand error of blz_ntt_vec_op in a source or a destination, a destination count below len - 1, and the
+ *   overlaps above. */
+enum blz_tree_op { BLZ_TREE_PROD = 0, BLZ_TREE_FRAC = 1 };
+int blz_ntt_mle_tree(blz_ntt* h, uint32_t op, uint32_t flags, const blz_vec_arg* dst, const blz_vec_arg* dst_q, const blz_vec_arg* a,
+                     const blz_vec_arg* a_q, uint64_t len);
 /* The same description evaluated POSITION BY POSITION - the element-wise counterpart of the step above: for p < len
  *     dst[p] = T[common][p_c] x sum_{m < nterms} (+/-) prod_{j < nfactors_m} T[factor_mj][p_mj]   (common == -1: the sum alone)
  * with table i read at p_i = (p + rot[i]) & (count_i - 1).  One op where a chain of blz_ntt_vec_op calls - one product or sum

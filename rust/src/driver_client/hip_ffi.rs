@@ -212,6 +212,8 @@ extern "C" {
                                  len: u64) -> c_int;
     pub fn blz_ntt_zerocheck_gate(h: *mut BlzNtt, gate: *const BlzSumGate, tables: *const BlzVecArg, weight: *const BlzVecArg, r: *const BlzVecArg,
                                   points: u32, len: u64, d_out: *mut c_void) -> c_int;
+    pub fn blz_ntt_mle_tree(h: *mut BlzNtt, op: u32, flags: u32, dst: *const BlzVecArg, dst_q: *const BlzVecArg, a: *const BlzVecArg,
+                            a_q: *const BlzVecArg, len: u64) -> c_int;
     pub fn blz_ntt_vec_op(h: *mut BlzNtt, op: c_int, buf_dst: usize, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg) -> c_int;
     pub fn blz_ntt_vec_reduce(h: *mut BlzNtt, op: c_int, a: *const BlzVecArg, b: *const BlzVecArg, d_out: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_scan(h: *mut BlzNtt, op: c_int, flags: u32, buf_dst: usize, a: *const BlzVecArg, d_total: *mut c_void) -> c_int;

@@ -424,9 +424,37 @@ impl NTTClient {
                                     rot.map_or(std::ptr::null(), |k| k.as_ptr()), len))
     }
 
+    /// Every layer of the product or fraction tree under the `len` = 2^m words of `a` (blz_ntt_mle_tree).  Layer k holds
+    /// len / 2^k words at word `tree_layer(len, k).0` of `dst`; len - 1 words are written.  Pairs are (L\[p\], L\[p + size / 2\]),
+    /// or (L\[2p\], L\[2p + 1\]) with `low`.  `TreeOp::Prod`: L'\[p\] = lo hi.  `TreeOp::Frac`: `frac` = `Some((dst_q, a_q))`,
+    /// (P, Q)' = (P_lo Q_hi + P_hi Q_lo, Q_lo Q_hi), never inverted.  A destination meets no source and not the other one.
+    ///
+    /// # Safety
+    /// As for `vec_mle_fold`: device words named by `dst` and `dst_q` are WRITTEN, those named by the sources read, until
+    /// `wait_result` returns.
+    pub unsafe fn mle_tree(&self, op: TreeOp, dst: VecOperand, a: VecOperand, frac: Option<(VecOperand, VecOperand)>, len: u64, low: bool) -> Result<()> {
+        let (rd, ra) = (dst.raw(), a.raw());
+        let rq = frac.map(|(d, s)| (d.raw(), s.raw()));
+        check(blz_ntt_mle_tree(self.h, op as u32, low as u32, &rd, rq.as_ref().map_or(std::ptr::null(), |x| &x.0 as *const BlzVecArg), &ra,
+                               rq.as_ref().map_or(std::ptr::null(), |x| &x.1 as *const BlzVecArg), len))
+    }
+
+    /// (word offset, words) of layer `k` (1 ..= m) in a destination of `mle_tree` over `len` = 2^m words
+    pub fn tree_layer(len: u64, k: u32) -> (u64, u64) {
+        (len - (len >> (k - 1)), len >> k)
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
+}
+
+/// `enum blz_tree_op`
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(u32)]
+pub enum TreeOp {
+    Prod = 0,
+    Frac = 1,
 }
 
 /// `enum blz_vec_op`
