@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "ntt_engine.hpp"
+#include "ntt_fs.hip.hpp"
 
 namespace blz {
 
@@ -1330,6 +1331,114 @@ int blz_ntt_mle_tree(blz_ntt* h, uint32_t op, uint32_t flags, const blz_vec_arg*
     // enqueue's first buffer is the one it hands out and may not be -1 beside a second: a lone buffer goes first
     if (buf[0] < 0) std::swap(buf[0], buf[1]);
     return call.enqueue(buf[0], [&](uint32_t*) { return h->ops->mle_tree(h->stream, op, flags, d[0], d[1], src[0], src[1], len); }, buf[1]);
+}
+
+// The transcript step (ntt_fs.hip.hpp): SHA3-256 of the state and `count` words as stored, the digest back into the state and,
+// masked below the modulus' top bit, into d_r.  An op like any other: it reads `words` (a buffer it names is read-only while it
+// is in flight) and writes no transform buffer.
+static uint32_t ntt_fs_keep_bits(int field) { return field == BLZ_BLS377 ? 252u : field == BLZ_BN254 ? 253u : 254u; }
+
+int blz_ntt_fs_challenge(blz_ntt* h, void* d_state, const blz_vec_arg* words, uint32_t count, void* d_r) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (!d_state) return fail(BLZ_ERR_INVALID_PARAM, "null d_state");
+    if (count > FS_MAX_WORDS) return fail(BLZ_ERR_INVALID_PARAM, "count %u is not in [0, %u]", count, FS_MAX_WORDS);
+    if (count > 0 && !words) return fail(BLZ_ERR_INVALID_PARAM, "a transcript step that absorbs %u words takes them: words is NULL", count);
+    NttVecCall call{h};
+    BLZ_TRY(call.begin());
+    NttVecArg vw{};
+    if (count > 0) {
+        BLZ_TRY(call.resolve({{"words", words, &vw}}));
+        if (vw.mask + 1 < count)
+            return fail(BLZ_ERR_INVALID_PARAM, "operand words: %llu words, the transcript absorbs the first %u as stored", (unsigned long long)(vw.mask + 1), count);
+    }
+    BLZ_TRY(call.device_range("the transcript", "d_state", d_state, 32, 16, 1, "elements"));
+    if (d_r) {
+        BLZ_TRY(call.device_range("the challenge", "d_r", d_r, 32, 16, 1, "elements"));
+        if (NttVecCall::words_meet(d_r, 1, d_state, 1)) return fail(BLZ_ERR_INVALID_PARAM, "d_r overlaps d_state");
+    }
+    if (count > 0) {
+        if (NttVecCall::words_meet(d_state, 1, vw.p, count)) return fail(BLZ_ERR_INVALID_PARAM, "d_state lies in the words absorbed");
+        if (d_r && NttVecCall::words_meet(d_r, 1, vw.p, count)) return fail(BLZ_ERR_INVALID_PARAM, "d_r lies in the words absorbed");
+    }
+    return call.enqueue(-1, [&](uint32_t*) { return ntt_fs_absorb(h->stream, d_state, vw.p, count, d_r, ntt_fs_keep_bits(h->field)); });
+}
+
+// A whole sumcheck in one enqueue: the round alone, then per variable the transcript step over the row just written and - but
+// for the last - the step with that challenge, then the bind alone; weight == NULL takes blz_ntt_sumcheck_gate's steps, else
+// blz_ntt_zerocheck_gate's.  Every launch goes to the compute stream behind the one before it, so nothing waits for the host.
+// Every rule a step of the chain would check is checked here, for the whole chain, before the first launch: the bind rules hold
+// from round 0 (no periodic table, no two tables meeting in their first len words), the weight's are the zerocheck step's, and
+// the three outputs - which are every step's d_out and r - lie off every table, off the weight and off each other.
+// (the description check is blz_ntt_sumcheck_gate's own function, reached as blz_ntt_zerocheck_gate reaches it)
+static constexpr auto ntt_prove_describe = &ntt_gate_describe;
+int blz_ntt_sumcheck_prove(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* tables, const blz_vec_arg* weight, uint32_t points, uint64_t len,
+                           void* d_state, void* d_rounds, void* d_challenges) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (!gate || !tables || !d_state || !d_rounds || !d_challenges)
+        return fail(BLZ_ERR_INVALID_PARAM, "a one-call prover takes %s",
+                    !gate ? "a gate: gate is NULL" : !tables ? "the gate's tables: tables is NULL" : !d_state ? "a transcript: d_state is NULL"
+                    : !d_rounds ? "room for the rounds: d_rounds is NULL" : "room for the challenges: d_challenges is NULL");
+    NttGate g;
+    BLZ_TRY(ntt_prove_describe(gate, g));
+    if (points < 1 || points > BLZ_GATE_MAX_POINTS) return fail(BLZ_ERR_INVALID_PARAM, "points %u is not in [1, %u]", points, BLZ_GATE_MAX_POINTS);
+    if (weight && !weight->d_ptr) return fail(BLZ_ERR_INVALID_PARAM, "operand weight: the weight is device words (d_ptr != NULL), not a transform buffer");
+    const int nt = (int)gate->ntables;
+    NttGateTables t(g, tables);
+    NttVecCall call{h};
+    BLZ_TRY(call.live_length(len));
+    BLZ_TRY(call.begin());
+    NttVecArg vw{};
+    NttVecCall::Operand ops[BLZ_GATE_MAX_TABLES + 1];
+    std::copy_n(t.ops, nt, ops);
+    ops[nt] = {"weight", weight, &vw};
+    BLZ_TRY(call.resolve(ops, (size_t)nt + 1));
+    uint32_t m = 0;   // log2 len
+    while ((len >> m) > 1) ++m;
+    int wbuf[2] = {-1, -1};
+    for (int j = 0; j < nt; ++j) {
+        if (g.t[j].mask + 1 < len)
+            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: %llu words, read periodically over len %llu: the chain folds every table in place, so none is periodic", t.name[j],
+                        (unsigned long long)(g.t[j].mask + 1), (unsigned long long)len);
+        for (int i = 0; i < j; ++i)
+            if (NttVecCall::words_meet(g.t[i].p, len, g.t[j].p, len))
+                return fail(BLZ_ERR_INVALID_PARAM, "%s and %s meet in their first len words: the chain folds each in place", t.name[i], t.name[j]);
+        if (!tables[j].d_ptr) wbuf[wbuf[0] < 0 ? 0 : 1] = (int)tables[j].buf;
+    }
+    if (weight) {
+        if (vw.mask + 1 < len / 2)
+            return fail(BLZ_ERR_INVALID_PARAM, "operand weight: %llu words, a step with r sums len / 2 = %llu", (unsigned long long)(vw.mask + 1),
+                        (unsigned long long)(len / 2));
+        for (int j = 0; j < nt; ++j)
+            if (NttVecCall::words_meet(vw.p, len / 2, g.t[j].p, len))
+                return fail(BLZ_ERR_INVALID_PARAM, "the weight's first len / 2 words meet the first len words of %s, which is folded in place", t.name[j]);
+    }
+    struct Output { const char* name; void* p; uint64_t words; };
+    const Output out[3] = {{"d_state", d_state, 1}, {"d_rounds", d_rounds, (uint64_t)m * points}, {"d_challenges", d_challenges, m}};
+    for (int o = 0; o < 3; ++o) {
+        BLZ_TRY(call.device_range(out[o].name, "the pointer", out[o].p, out[o].words * 32, 16, out[o].words, "elements"));
+        for (int j = 0; j < nt; ++j)
+            if (NttVecCall::words_meet(out[o].p, out[o].words, g.t[j].p, len))
+                return fail(BLZ_ERR_INVALID_PARAM, "%s lies in the live words of %s", out[o].name, t.name[j]);
+        if (weight && NttVecCall::words_meet(out[o].p, out[o].words, vw.p, vw.mask + 1))
+            return fail(BLZ_ERR_INVALID_PARAM, "%s overlaps the words of the weight", out[o].name);
+        for (int i = 0; i < o; ++i)
+            if (NttVecCall::words_meet(out[i].p, out[i].words, out[o].p, out[o].words))
+                return fail(BLZ_ERR_INVALID_PARAM, "%s overlaps %s", out[o].name, out[i].name);
+    }
+    uint32_t* const rounds = (uint32_t*)d_rounds;
+    uint32_t* const chal = (uint32_t*)d_challenges;
+    const uint32_t keep = ntt_fs_keep_bits(h->field);
+    auto step = [&](const uint32_t* r, uint32_t pts, uint64_t live, uint32_t* to) {
+        return weight && pts ? h->ops->zerocheck_gate(h->stream, g, vw, r, pts, live, to, call.ws) : h->ops->sumcheck_gate(h->stream, g, r, pts, live, to, call.ws);
+    };
+    return call.enqueue(wbuf[0], [&](uint32_t*) {
+        BLZ_TRY(step(nullptr, points, len, rounds));
+        for (uint32_t i = 0; i < m; ++i) {
+            BLZ_TRY(ntt_fs_absorb(h->stream, d_state, rounds + (size_t)i * points * 8, points, chal + (size_t)i * 8, keep));
+            if (i + 1 < m) BLZ_TRY(step(chal + (size_t)i * 8, points, len >> i, rounds + (size_t)(i + 1) * points * 8));
+        }
+        return step(chal + (size_t)(m - 1) * 8, 0, 2, nullptr);
+    }, wbuf[1]);
 }
 
 int blz_ntt_last_kernel_ms(blz_ntt* h, float* out) {

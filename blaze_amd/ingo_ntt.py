@@ -513,6 +513,51 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
                                      self._mle_len(length, *[x for x in (a, a_q) if x is not None] or [0])))
         self._vec_keep = (dst, dst_q, a, a_q)
 
+    def fs_challenge(self, state: DeviceBuffer, words=None, count: Optional[int] = None, r: Optional[DeviceBuffer] = None) -> Optional[DeviceBuffer]:
+        """One step of the on-device Fiat-Shamir transcript (blz_ntt_fs_challenge): SHA3-256 of `state` (a one-word DeviceBuffer,
+        read and written) followed by the first `count` words of `words` (an int - a transform buffer - or a DeviceBuffer; count=None
+        means all of a DeviceBuffer, at most 32) exactly as stored.  The digest becomes the new state; with every bit from
+        bitlen(modulus) - 1 upward cleared it is the challenge written to `r`, a one-word DeviceBuffer that a step op takes as its
+        r without the host ever reading it.  r=None absorbs only.  blaze_amd.fiat_shamir.absorb is the host's mirror.  Returns
+        `r`; finished by wait_result()."""
+        if count is None:
+            count = 0 if words is None else (words.nbytes // NTT_WORD_SIZE if isinstance(words, DeviceBuffer) else 1 << self.log_size)
+        vw = self._vec_arg(words)
+        check(lib().blz_ntt_fs_challenge(self._h, state.ptr, None if vw is None else C.byref(vw), int(count), None if r is None else r.ptr))
+        self._vec_keep = (state, words, r)
+        return r
+
+    def sumcheck_prove(self, tables, terms, state: DeviceBuffer, weight: Optional[DeviceBuffer] = None, common: Optional[int] = None,
+                       points: Optional[int] = None, length: Optional[int] = None, rounds: Optional[DeviceBuffer] = None,
+                       challenges: Optional[DeviceBuffer] = None):
+        """A whole sumcheck in ONE call (blz_ntt_sumcheck_prove): the round alone, then per variable fs_challenge over the round
+        just written and the step with that challenge, then the bind alone - m = log2(length) rounds enqueued back to back, no
+        host wait in between.  `tables`, `terms`, `common` describe the gate as for sumcheck_gate; weight=None proves the sum of
+        G, a `weight` (DeviceBuffer, length / 2 words, as for zerocheck_gate) the sum of weight x G with zerocheck_gate's steps.
+        `state` is the transcript, one word, read and left at the state after the last round.  points defaults to the gate's
+        degree + 1 (+ 1 for a common factor), 1 to 6.  Returns (rounds, challenges): DeviceBuffers of m x points and m words
+        (the ones passed, or fresh ones).  After wait_result() word 0 of every table is the table at the challenges, top
+        variable first, and a verifier re-derives the challenges with blaze_amd.fiat_shamir.challenges."""
+        tables = list(tables)
+        gate, degree = self._sum_gate(tables, terms, common)
+        if points is None:
+            points = degree + (common is not None) + 1
+        points = int(points)
+        if length is None:
+            n = 1 << self.log_size
+            length = max([x.nbytes // NTT_WORD_SIZE if isinstance(x, DeviceBuffer) else n for x in tables] or [0])
+        m = max(int(length).bit_length() - 1, 1)
+        if rounds is None:
+            rounds = DeviceBuffer(self.driver_client.id, NTT_WORD_SIZE * m * max(points, 1))
+        if challenges is None:
+            challenges = DeviceBuffer(self.driver_client.id, NTT_WORD_SIZE * m)
+        args = (BlzVecArg * max(len(tables), 1))(*[self._vec_arg(x) for x in tables])
+        vw = self._vec_arg(weight)
+        check(lib().blz_ntt_sumcheck_prove(self._h, C.byref(gate), args, None if vw is None else C.byref(vw), points, int(length),
+                                           state.ptr, rounds.ptr, challenges.ptr))
+        self._vec_keep = (*tables, weight, state, rounds, challenges)
+        return rounds, challenges
+
     def scalar(self, value: int) -> DeviceBuffer:
         """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""
         v = int(value)

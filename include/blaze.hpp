@@ -373,6 +373,21 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
     }
     // the word offset of layer k (1 .. m) in a destination of mle_tree; the layer holds len >> k words
     static uint64_t tree_layer(uint64_t len, uint32_t k) { return len - (len >> (k - 1)); }
+    // one step of the on-device Fiat-Shamir transcript (blz_ntt_fs_challenge): digest = SHA3-256(state || the first count words of
+    // words, as stored), the digest back into d_state and, with every bit from bitlen(modulus) - 1 upward cleared, into d_r
+    // (nullptr: absorb only).  count <= 32; words may be nullptr when count is 0
+    void fs_challenge(void* d_state, const blz_vec_arg* words, uint32_t count, void* d_r) { check(blz_ntt_fs_challenge(h_, d_state, words, count, d_r)); }
+    // a whole sumcheck in one call (blz_ntt_sumcheck_prove): the round alone, then per variable the transcript step over the round
+    // just written and the step with that challenge, then the bind alone, with no host wait in between.  weight == nullptr: the
+    // sum of the gate by sumcheck_gate's steps, else the weighted sum by zerocheck_gate's.  m = log2 len: d_rounds receives
+    // m x points words, d_challenges m words, d_state is the transcript; points defaults to the gate's degree + 1
+    void sumcheck_prove(const blz_sum_gate& gate, const blz_vec_arg* tables, const blz_vec_arg* weight, uint64_t len, void* d_state, void* d_rounds,
+                        void* d_challenges, uint32_t points = 0) {
+        uint32_t degree = 0;
+        for (uint32_t m = 0; m < gate.nterms && m < BLZ_GATE_MAX_TERMS; ++m) degree = gate.term[m].nfactors > degree ? gate.term[m].nfactors : degree;
+        degree += gate.common >= 0 ? 1u : 0u;
+        check(blz_ntt_sumcheck_prove(h_, &gate, tables, weight, points ? points : degree + 1u, len, d_state, d_rounds, d_challenges));
+    }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

@@ -1072,6 +1072,62 @@ int blz_poseidon_stream(blz_poseidon* h, void** hip_stream, int* device_id);
  * the mode stay */
 int blz_poseidon_reset(blz_poseidon* h);
 
+/* ------------------------------------------------------------------ Fiat-Shamir transcript and the one-call sumcheck prover
+ *
+ * Two ops on a blz_ntt handle.  They stand here, behind the step ops they chain (blz_ntt_sumcheck_gate, blz_ntt_zerocheck_gate),
+ * because with them the host leaves the loop: every op above is ONE step, and between two steps a prover had to wait, download
+ * the round polynomial, hash it into a challenge and upload that - about 52 us a round at any table size (DESIGN.md section 4,
+ * "One-call prover").  r was made a device word so that a transcript could be added without touching the steps; this is it.
+ *
+ * THE TRANSCRIPT STEP.  The hash is SHA3-256 (FIPS 202): a byte-oriented hash costs a few microseconds on one wave where a lone
+ * Poseidon permutation costs more than the round trip it would replace.  Python's hashlib.sha3_256 reproduces it.
+ *   d_state is one 32-byte device word, 16-byte aligned.  It is read and written.
+ *   digest = SHA3-256(state || w_0 || ... || w_{count-1}).
+ *   The w_i are the first `count` 32-byte words of `words`, exactly as stored.  Nothing is reduced.  The ops write canonical
+ *   words anyway.
+ *   0 <= count <= 32.  `words` may be NULL when count is 0.
+ *   `words` is a transform buffer or device words, as for any operand (blz_ntt_vec_op's rules; it holds at least `count` words).
+ *   The new state is the digest.
+ *   The challenge written to d_r is the digest read as a little-endian 256-bit integer, with every bit from bit
+ *   bitlen(modulus) - 1 upward cleared.  That keeps 252 bits on BLS12-377, 254 on BLS12-381 and 253 on BN254.
+ *   Because of the masking the challenge is uniform and always canonical.  d_r is nullable; NULL means absorb only.
+ *   The protocol is every op's: checked first, enqueued, finished by blz_ntt_wait_result, timed by blz_ntt_last_kernel_ms.
+ *   d_state and d_r must not overlap each other or the words read.
+ *   A buffer named by `words` is read-only while the op is in flight; no transform buffer is written.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing and enqueueing nothing, in this order: a null handle (refused before any other
+ *   argument is looked at), a null d_state, count above 32, a null `words` with count > 0, an op in flight, any operand error of
+ *   blz_ntt_vec_op in `words`, `words` holding fewer than `count` words, a d_state or d_r that is misaligned, not device memory of
+ *   the handle's device or running past its allocation, d_r overlapping d_state, d_state or d_r inside the words absorbed. */
+int blz_ntt_fs_challenge(blz_ntt* h, void* d_state, const blz_vec_arg* words, uint32_t count, void* d_r);
+/* THE ONE-CALL PROVER.  A whole m-variable sumcheck, m = log2 len >= 1, enqueued by ONE call with no host wait inside: the m + 2
+ * step ops and the m transcript steps between them, on the handle's compute stream, each behind the one before.
+ *   weight == NULL proves sum_p G(p) with blz_ntt_sumcheck_gate's steps; otherwise sum_p W[p] G(p) with blz_ntt_zerocheck_gate's -
+ *   the weight is len / 2 device words, and the eq factor stays with the caller exactly as for the single step.
+ *   gate, tables: blz_ntt_sumcheck_gate's, checked by the same code with the same messages.  1 <= points <= BLZ_GATE_MAX_POINTS.
+ *   The chain:  1. the round alone at len writes d_rounds[0 .. points);
+ *               2. for i = 0 .. m - 1 the transcript step absorbs row i of d_rounds (points words) and writes d_challenges[i];
+ *               3. for i < m - 1 the step with r = d_challenges[i] at live length len >> i follows and writes row i + 1;
+ *               4. last comes the bind alone - blz_ntt_sumcheck_gate with points == 0 at length 2 - with d_challenges[m - 1].
+ *   Afterwards word 0 of every table is that table at the challenges, top variable first; d_rounds holds m x points words,
+ *   d_challenges m words, and d_state the state after the last absorb: a caller chains the next sumcheck, or derives batching
+ *   challenges, with blz_ntt_fs_challenge.  The final table words are NOT absorbed by the call.
+ *   Bytes written are exactly the bytes the equivalent sequence of single ops writes and no others: at most len / 2 words of
+ *   each table, at most len / 4 of the weight, and the three outputs.
+ *   Everything is checked before the first launch.  The bind rules hold from the start - no periodic table, no two tables
+ *   meeting in their first len words; the weight's rules are blz_ntt_zerocheck_gate's; the three outputs lie off every table's
+ *   first len words, off the weight's words and off each other.
+ *   Protocol: one blz_ntt_wait_result finishes the chain and blz_ntt_last_kernel_ms then spans it; blz_ntt_reset drops it.  While
+ *   it runs, every transform buffer that is a table is a buffer being written (both may be), and no op starts.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing and enqueueing nothing, in this order: a null handle (refused before any other
+ *   argument is looked at); a null gate, tables, d_state, d_rounds or d_challenges; every description error of
+ *   blz_ntt_sumcheck_gate; points outside 1 .. 6; a weight that names a buffer; len not a power of two in [2, n]; an op in flight;
+ *   any operand error of blz_ntt_vec_op in a table or in the weight; a table with count < len; two tables whose first len words
+ *   meet; a weight below len / 2 words or whose first len / 2 words meet a table's first len; then per output, in the order
+ *   d_state, d_rounds, d_challenges: misaligned, not device memory of the handle's device or running past its allocation, inside
+ *   a table's first len words, inside the weight's words, overlapping an earlier output. */
+int blz_ntt_sumcheck_prove(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* tables, const blz_vec_arg* weight, uint32_t points,
+                           uint64_t len, void* d_state, void* d_rounds, void* d_challenges);
+
 /* ------------------------------------------------------------------ device / host memory helpers */
 
 /* Device memory owned by the library (hosts without a tensor library of their own; bench.py and the tests use these). */

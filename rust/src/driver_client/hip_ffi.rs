@@ -214,6 +214,9 @@ extern "C" {
                                   points: u32, len: u64, d_out: *mut c_void) -> c_int;
     pub fn blz_ntt_mle_tree(h: *mut BlzNtt, op: u32, flags: u32, dst: *const BlzVecArg, dst_q: *const BlzVecArg, a: *const BlzVecArg,
                             a_q: *const BlzVecArg, len: u64) -> c_int;
+    pub fn blz_ntt_fs_challenge(h: *mut BlzNtt, d_state: *mut c_void, words: *const BlzVecArg, count: u32, d_r: *mut c_void) -> c_int;
+    pub fn blz_ntt_sumcheck_prove(h: *mut BlzNtt, gate: *const BlzSumGate, tables: *const BlzVecArg, weight: *const BlzVecArg, points: u32,
+                                  len: u64, d_state: *mut c_void, d_rounds: *mut c_void, d_challenges: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_op(h: *mut BlzNtt, op: c_int, buf_dst: usize, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg) -> c_int;
     pub fn blz_ntt_vec_reduce(h: *mut BlzNtt, op: c_int, a: *const BlzVecArg, b: *const BlzVecArg, d_out: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_scan(h: *mut BlzNtt, op: c_int, flags: u32, buf_dst: usize, a: *const BlzVecArg, d_total: *mut c_void) -> c_int;

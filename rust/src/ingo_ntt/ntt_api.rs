@@ -444,6 +444,38 @@ impl NTTClient {
         (len - (len >> (k - 1)), len >> k)
     }
 
+    /// One step of the on-device Fiat-Shamir transcript (blz_ntt_fs_challenge): digest = SHA3-256(state || the first `count`
+    /// words of `words`, as stored); the digest is the new state at `d_state` and, with every bit from bitlen(modulus) - 1
+    /// upward cleared (252 bits kept on BLS12-377, 254 on BLS12-381, 253 on BN254), the challenge at `d_r`.  `count` <= 32;
+    /// `words` may be `None` when it is 0; a null `d_r` absorbs only.
+    ///
+    /// # Safety
+    /// `d_state` and `d_r` (if not null) are one 16-byte aligned device word each, WRITTEN, off each other and off the words
+    /// read; all stay valid until `wait_result` returns.
+    pub unsafe fn fs_challenge(&self, d_state: *mut std::os::raw::c_void, words: Option<VecOperand>, count: u32,
+                               d_r: *mut std::os::raw::c_void) -> Result<()> {
+        let rw = words.map(|v| v.raw());
+        check(blz_ntt_fs_challenge(self.h, d_state, rw.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg), count, d_r))
+    }
+
+    /// A whole sumcheck in one call (blz_ntt_sumcheck_prove): the round alone, then per variable the transcript step over the
+    /// round just written and the step with that challenge, then the bind alone - no host wait in between.  `weight` `None`
+    /// proves the sum of the gate with `sumcheck_gate`'s steps, `Some` the weighted sum with `zerocheck_gate`'s (len / 2 device
+    /// words).  m = log2 `len`; `d_rounds` receives m x `points` words, `d_challenges` m words, `d_state` is the transcript.
+    ///
+    /// # Safety
+    /// As for `sumcheck_gate` with `r`: every table is folded in place, the weight summed in place; the three outputs are
+    /// device words off every table, the weight and each other, valid until `wait_result` returns.
+    pub unsafe fn sumcheck_prove(&self, tables: &[VecOperand], terms: &[(bool, &[u8])], weight: Option<VecOperand>, common: Option<u8>, points: u32,
+                                 len: u64, d_state: *mut std::os::raw::c_void, d_rounds: *mut std::os::raw::c_void,
+                                 d_challenges: *mut std::os::raw::c_void) -> Result<()> {
+        let gate = Self::sum_gate(tables.len(), terms, common);
+        let raw: Vec<BlzVecArg> = tables.iter().map(|x| x.raw()).collect();
+        let rw = weight.map(|v| v.raw());
+        check(blz_ntt_sumcheck_prove(self.h, &gate, if raw.is_empty() { std::ptr::null() } else { raw.as_ptr() },
+                                     rw.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg), points, len, d_state, d_rounds, d_challenges))
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
