@@ -1441,6 +1441,107 @@ int blz_ntt_sumcheck_prove(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_a
     }, wbuf[1]);
 }
 
+// The GKR grand product over blz_ntt_mle_tree's layers in one enqueue (include/blaze_hip.h, THE ONE-CALL GKR PROVER; kernels:
+// ntt_gkr.hip.hpp).  From the root down, layer j's tables are the two halves of layer m - 1 - j of the tree (of the leaves for
+// j = m - 1), its point is row j - 1 of d_points and its weight eq over that point's first j - 1 words; its sumcheck is the chain
+// blz_ntt_sumcheck_prove enqueues under a weight, with the challenges written backwards into row j of d_points, and behind it the
+// two final words go to d_claims and through one more transcript step.  Every launch goes to the compute stream behind the one
+// before it.  BLZ_GKR_UNFUSED takes the existing launchers alone (and k_gkr_claims, a copy of two words); without it the rounds
+// at live lengths of 512 and below - all of them for m <= 10 - run inside one block, h->ops->gkr_tail.  Every check stands before
+// the first launch.
+// (the layer gate lo hi is packed by blz_ntt_sumcheck_gate's own function, reached as blz_ntt_sumcheck_prove reaches it)
+static constexpr auto ntt_gkr_describe = &ntt_gate_describe;
+int blz_ntt_gkr_prove(blz_ntt* h, uint32_t op, uint32_t flags, const blz_vec_arg* tree, const blz_vec_arg* a, uint64_t len, void* d_weight,
+                      void* d_state, void* d_rounds, void* d_points, void* d_claims) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (op == BLZ_TREE_FRAC)
+        return fail(BLZ_ERR_INVALID_PARAM, "BLZ_TREE_FRAC is not built: the one-call GKR prover takes BLZ_TREE_PROD (a fraction tree's layer gate needs a scalar that is not folded)");
+    if (op != BLZ_TREE_PROD) return fail(BLZ_ERR_INVALID_PARAM, "unknown tree op %u", op);
+    if (flags & ~BLZ_GKR_UNFUSED) return fail(BLZ_ERR_INVALID_PARAM, "unknown GKR flags 0x%x", flags);
+    if (!tree || !a || !d_weight || !d_state || !d_rounds || !d_points || !d_claims)
+        return fail(BLZ_ERR_INVALID_PARAM, "a one-call GKR prover takes %s",
+                    !tree ? "the product tree: tree is NULL" : !a ? "the leaves: a is NULL" : !d_weight ? "room for the weight: d_weight is NULL"
+                    : !d_state ? "a transcript: d_state is NULL" : !d_rounds ? "room for the rounds: d_rounds is NULL"
+                    : !d_points ? "room for the points: d_points is NULL" : "room for the claims: d_claims is NULL");
+    NttVecCall call{h};
+    BLZ_TRY(call.live_length(len));
+    BLZ_TRY(call.begin());
+    NttVecArg vt{}, va{};
+    BLZ_TRY(call.resolve({{"tree", tree, &vt}, {"a", a, &va}}));
+    if (vt.mask + 1 < len - 1)
+        return fail(BLZ_ERR_INVALID_PARAM, "operand tree: %llu words, a tree over len %llu holds len - 1", (unsigned long long)(vt.mask + 1), (unsigned long long)len);
+    if (va.mask + 1 < len)
+        return fail(BLZ_ERR_INVALID_PARAM, "operand a: %llu words, read periodically over len %llu: the leaves are folded in place, so they are not periodic",
+                    (unsigned long long)(va.mask + 1), (unsigned long long)len);
+    uint32_t m = 0;   // log2 len
+    while ((len >> m) > 1) ++m;
+    // what the op names, in the order of the checks: the two operands, the weight, the four outputs
+    struct Range { const char* name; const void* p; uint64_t words; };
+    const Range rg[7] = {{"tree", vt.p, len - 1}, {"a", va.p, len}, {"d_weight", d_weight, std::max<uint64_t>(len / 4, 1)}, {"d_state", d_state, 1},
+                         {"d_rounds", d_rounds, (uint64_t)3 * m * (m - 1) / 2}, {"d_points", d_points, (uint64_t)m * (m + 1) / 2}, {"d_claims", d_claims, (uint64_t)2 * m}};
+    for (int o = 2; o < 7; ++o) BLZ_TRY(call.device_range(rg[o].name, "the pointer", rg[o].p, rg[o].words * 32, 16, rg[o].words, "elements"));
+    for (int o = 1; o < 7; ++o)
+        for (int i = 0; i < o; ++i)
+            if (rg[i].words && rg[o].words && NttVecCall::words_meet(rg[i].p, rg[i].words, rg[o].p, rg[o].words))
+                return fail(BLZ_ERR_INVALID_PARAM, "%s overlaps %s: %llu words against %llu", rg[o].name, rg[i].name, (unsigned long long)rg[o].words,
+                            (unsigned long long)rg[i].words);
+    int wbuf[2] = {-1, -1};   // the tree's layers and the leaves are folded in place: a buffer either names is written
+    if (!tree->d_ptr) wbuf[0] = (int)tree->buf;
+    if (!a->d_ptr) wbuf[wbuf[0] < 0 ? 0 : 1] = (int)a->buf;
+    const bool fused = !(flags & BLZ_GKR_UNFUSED);
+    const uint32_t keep = ntt_fs_keep_bits(h->field);
+    uint32_t* const weight = (uint32_t*)d_weight;
+    uint32_t* const points = (uint32_t*)d_points;
+    NttGate g;
+    {
+        blz_sum_gate product{};   // + lo hi
+        product.ntables = 2, product.nterms = 1, product.common = -1;
+        product.term[0].nfactors = 2, product.term[0].factor[1] = 1;
+        BLZ_TRY(ntt_gkr_describe(&product, g));
+    }
+    NttGkrTail tail{vt.p, va.p, weight, (uint32_t*)d_state, (uint32_t*)d_rounds, points, (uint32_t*)d_claims, m, 0, 0, 0, 0, keep};
+    return call.enqueue(wbuf[0], [&](uint32_t*) {
+        for (uint32_t j = 0; j < m; ++j) {
+            const uint64_t live = 1ull << j;   // words of lo and of hi
+            if (fused && live <= GKR_TAIL_LEN) {   // every whole layer that fits, in one launch
+                tail.first = j;
+                while (j + 1 < m && (2ull << j) <= GKR_TAIL_LEN) ++j;
+                tail.last = j + 1, tail.tail = 0, tail.claims_only = 0;
+                BLZ_TRY(h->ops->gkr_tail(h->stream, tail));
+                continue;
+            }
+            const uint32_t* const lo = j + 1 == m ? va.p : vt.p + (len - 4 * live) * 8;
+            uint32_t* const rows = (uint32_t*)d_rounds + (size_t)3 * ((size_t)j * (j - 1) / 2) * 8;
+            uint32_t* const row = points + ((size_t)j * (j + 1) / 2) * 8;   // row j of the points; row j - 1 ends where it starts
+            tail.first = j, tail.last = j + 1;
+            if (j >= 1) {
+                g.t[0] = NttVecArg{lo, live - 1};
+                g.t[1] = NttVecArg{lo + live * 8, live - 1};
+                const NttVecArg vw{weight, std::max<uint64_t>(live / 2, 1) - 1};
+                BLZ_TRY(h->ops->vec_mle_eq(h->stream, weight, row - (size_t)j * 8, j - 1, call.ws));
+                BLZ_TRY(h->ops->zerocheck_gate(h->stream, g, vw, nullptr, 3, live, rows, call.ws));
+                // the pairs (transcript step, step with r): all but the last variable's, or down to the live length the block takes
+                const uint32_t chain = fused ? j - GKR_TAIL_LOG : j;
+                for (uint32_t i = 0; i < chain; ++i) {
+                    uint32_t* const r = row + (size_t)(j - 1 - i) * 8;   // backwards: the row ends up in bit order
+                    BLZ_TRY(ntt_fs_absorb(h->stream, d_state, rows + (size_t)i * 3 * 8, 3, r, keep));
+                    if (i + 1 < j) BLZ_TRY(h->ops->zerocheck_gate(h->stream, g, vw, r, 3, live >> i, rows + (size_t)(i + 1) * 3 * 8, call.ws));
+                    else BLZ_TRY(h->ops->sumcheck_gate(h->stream, g, r, 0, 2, nullptr, call.ws));
+                }
+                if (fused) {
+                    tail.tail = 1, tail.claims_only = 0;
+                    BLZ_TRY(h->ops->gkr_tail(h->stream, tail));
+                    continue;
+                }
+            }
+            tail.tail = 0, tail.claims_only = 1;
+            BLZ_TRY(h->ops->gkr_tail(h->stream, tail));
+            BLZ_TRY(ntt_fs_absorb(h->stream, d_state, (uint32_t*)d_claims + (size_t)2 * j * 8, 2, row + (size_t)j * 8, keep));
+        }
+        return (int)BLZ_OK;
+    }, wbuf[1]);
+}
+
 int blz_ntt_last_kernel_ms(blz_ntt* h, float* out) {
     if (!h || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
     *out = h->last_ms;

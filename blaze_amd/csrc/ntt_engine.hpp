@@ -103,6 +103,23 @@ struct NttLinGate {
     uint32_t form[NTT_LIN_MAX_FORMS][NTT_LIN_MAX_SUMMANDS];
     NttVecArg t[NTT_LIN_MAX_TABLES];
 };
+// One launch of the GKR grand product's own kernels (blz_ntt_gkr_prove; kernels and the layout: ntt_gkr.hip.hpp), by value in the
+// kernel arguments.  tree, a: the product tree over 2^m leaves and the leaves; weight: the layer's summed weight (read by a tail
+// alone); state, rounds, points, claims: the op's four outputs.  The layers [first, last) are run by ONE block:
+//   tail != 0    last == first + 1 and 2^first > 512: the chain of step launches has brought layer `first` down to the live
+//                length 512 and left its current row in `rounds`; the block finishes the layer;
+//   tail == 0    whole layers, 2^(last - 1) <= 512: nothing of them has run yet;
+//   claims_only  no sumcheck: word 0 of the two tables of layer `first` goes to its row of the claims (the chain's own step).
+// keep_bits: the challenge keeps bits [0, keep_bits) of a digest
+constexpr int GKR_TAIL_LOG = 9;
+constexpr uint32_t GKR_TAIL_LEN = 1u << GKR_TAIL_LOG;   // the largest live length the block takes: 2 x 512 + 256 words are 40 KiB of LDS
+struct NttGkrTail {
+    const uint32_t* tree;
+    const uint32_t* a;
+    const uint32_t* weight;
+    uint32_t *state, *rounds, *points, *claims;
+    uint32_t m, first, last, tail, claims_only, keep_bits;
+};
 constexpr int NTT_VEC_OPS = 6;              // enum blz_vec_op: ADD SUB MUL MULADD MULSUB INV
 constexpr uint64_t NTT_VEC_INV_TILE = 1024;  // batch inversion: elements per block (256 lanes x 4); one 32-byte total per tile
 constexpr int NTT_FOLD_OPS = 3;              // enum blz_fold_op: SUM DOT EVAL
@@ -195,6 +212,9 @@ struct NttFieldOps {
     // op: enum blz_tree_op; BLZ_TREE_FRAC carries (a, a_q) to (dst, dst_q), BLZ_TREE_PROD ignores both _q; flags: BLZ_MLE_LOW.
     // No destination word may be a word the op reads of a source, nor one of the other destination's
     int (*mle_tree)(hipStream_t st, uint32_t op, uint32_t flags, uint32_t* dst, uint32_t* dst_q, NttVecArg a, NttVecArg a_q, uint64_t len);
+    // The small rounds of a GKR grand product in one block (blz_ntt_gkr_prove; kernels: ntt_gkr.hip.hpp): the layers g names, or
+    // the claims of one layer.  Nothing of the tree, the leaves or the weight is written
+    int (*gkr_tail)(hipStream_t st, const NttGkrTail& g);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

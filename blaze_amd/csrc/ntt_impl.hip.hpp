@@ -17,6 +17,7 @@
 #include "ntt_geval.hip.hpp"
 #include "ntt_lineval.hip.hpp"
 #include "ntt_tree.hip.hpp"
+#include "ntt_gkr.hip.hpp"
 
 namespace blz {
 
@@ -539,6 +540,7 @@ NttFieldOps make_ntt_ops() {
     o.gate_eval_lin = &ntt_gate_eval_lin_t<Fr>;
     o.zerocheck_gate = &ntt_zerocheck_gate_t<Fr>;
     o.mle_tree = &ntt_mle_tree_t<Fr>;
+    o.gkr_tail = &ntt_gkr_tail_t<Fr>;
     return o;
 }
 

@@ -49,6 +49,7 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
     MLE_LOW = 1                                     # BLZ_MLE_LOW
     GATE_PRODUCT, GATE_R1CS = 0, 1                  # BLZ_GATE_*
     TREE_PROD, TREE_FRAC = 0, 1                     # enum blz_tree_op
+    GKR_UNFUSED = 1                                 # BLZ_GKR_UNFUSED
 
     def __init__(self, _ptype: NTT, dclient: DriverClient, log_size: int = NTT_LOG_SIZE, inverse: bool = False,
                  field: str = "BLS381", flags: int = 0, root: Optional[int] = None):
@@ -557,6 +558,37 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
                                            state.ptr, rounds.ptr, challenges.ptr))
         self._vec_keep = (*tables, weight, state, rounds, challenges)
         return rounds, challenges
+
+    def gkr_prove(self, tree, a, state: DeviceBuffer, length: Optional[int] = None, weight: Optional[DeviceBuffer] = None,
+                  rounds: Optional[DeviceBuffer] = None, points: Optional[DeviceBuffer] = None, claims: Optional[DeviceBuffer] = None,
+                  fused: bool = True):
+        """The GKR grand product over a product tree in ONE call (blz_ntt_gkr_prove).  `tree` is what mle_tree(tree, a) left
+        (TREE_PROD, default pairing) over the `length` = 2^m leaves `a` (None: all of `a`); both are ints (transform buffers) or
+        DeviceBuffers and both are consumed: the first half of each half-layer is scratch afterwards.  From the root down, layer
+        j's claim is proven by a sumcheck under the weight eq(point of the layer above) with every challenge made on the device,
+        then the two final words go to `claims` and through one more transcript step.  `state` is the transcript, one word, read
+        and left at the state after the last step; the root is not absorbed.  `weight` is the scratch for the weight, max(length
+        / 4, 1) words.  Returns (rounds, points, claims): DeviceBuffers of 3 m (m - 1) / 2, m (m + 1) / 2 and 2 m words (the
+        ones passed, or fresh ones) laid out as blaze_amd.gkr.layout(m) says; blaze_amd.gkr.verify_product checks them and returns
+        the leaves' claim and point.  fused=False takes the chain of single launches only (GKR_UNFUSED): the same bytes, slower.
+        Finished by wait_result()."""
+        from . import gkr
+        length = self._mle_len(length, a)
+        lay = gkr.layout(max(int(length).bit_length() - 1, 1))
+        dev = self.driver_client.id
+        if weight is None:
+            weight = DeviceBuffer(dev, NTT_WORD_SIZE * lay.weight_words)
+        if rounds is None:
+            rounds = DeviceBuffer(dev, NTT_WORD_SIZE * max(lay.rounds_words, 1))
+        if points is None:
+            points = DeviceBuffer(dev, NTT_WORD_SIZE * lay.points_words)
+        if claims is None:
+            claims = DeviceBuffer(dev, NTT_WORD_SIZE * lay.claims_words)
+        vt, va = self._vec_arg(tree), self._vec_arg(a)
+        check(lib().blz_ntt_gkr_prove(self._h, self.TREE_PROD, 0 if fused else self.GKR_UNFUSED, C.byref(vt), C.byref(va), int(length), weight.ptr,
+                                      state.ptr, rounds.ptr, points.ptr, claims.ptr))
+        self._vec_keep = (tree, a, weight, state, rounds, points, claims)
+        return rounds, points, claims
 
     def scalar(self, value: int) -> DeviceBuffer:
         """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""

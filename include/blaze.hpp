@@ -388,6 +388,22 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
         degree += gate.common >= 0 ? 1u : 0u;
         check(blz_ntt_sumcheck_prove(h_, &gate, tables, weight, points ? points : degree + 1u, len, d_state, d_rounds, d_challenges));
     }
+    // the GKR grand product over a product tree in one call (blz_ntt_gkr_prove): tree is what mle_tree(BLZ_TREE_PROD, tree, a, len)
+    // left over the len = 2^m leaves a; from the root down each layer's sumcheck, its two final words and their transcript step,
+    // with no host wait in between.  d_weight: max(len / 4, 1) words of scratch; d_rounds 3 m (m - 1) / 2 words, d_points
+    // m (m + 1) / 2, d_claims 2 m (gkr_rounds_words and its neighbours); fused == false: BLZ_GKR_UNFUSED, the chain of single
+    // launches.  Both tree and a are consumed
+    void gkr_prove(const blz_vec_arg* tree, const blz_vec_arg* a, uint64_t len, void* d_weight, void* d_state, void* d_rounds, void* d_points,
+                   void* d_claims, bool fused = true) {
+        check(blz_ntt_gkr_prove(h_, BLZ_TREE_PROD, fused ? 0u : BLZ_GKR_UNFUSED, tree, a, len, d_weight, d_state, d_rounds, d_points, d_claims));
+    }
+    // the words of gkr_prove's outputs for a tree over 2^m leaves, and the word of layer j's round i, point row and claims row
+    static uint64_t gkr_rounds_words(uint32_t m) { return 3ull * m * (m - 1) / 2; }
+    static uint64_t gkr_points_words(uint32_t m) { return (uint64_t)m * (m + 1) / 2; }
+    static uint64_t gkr_claims_words(uint32_t m) { return 2ull * m; }
+    static uint64_t gkr_round(uint32_t j, uint32_t i) { return 3 * ((uint64_t)j * (j - 1) / 2 + i); }
+    static uint64_t gkr_point_row(uint32_t j) { return (uint64_t)j * (j + 1) / 2; }
+    static uint64_t gkr_claim_row(uint32_t j) { return 2ull * j; }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

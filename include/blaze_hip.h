@@ -1127,6 +1127,53 @@ int blz_ntt_fs_challenge(blz_ntt* h, void* d_state, const blz_vec_arg* words, ui
  *   a table's first len words, inside the weight's words, overlapping an earlier output. */
 int blz_ntt_sumcheck_prove(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_arg* tables, const blz_vec_arg* weight, uint32_t points,
                            uint64_t len, void* d_state, void* d_rounds, void* d_challenges);
+/* THE ONE-CALL GKR PROVER.  The GKR grand product over a product tree, enqueued by ONE call with no host wait inside: the argument
+ * blz_ntt_mle_tree and blz_ntt_sumcheck_prove were built for.  A grand product over len = 2^m leaves is m layers and
+ * m (m - 1) / 2 sumcheck rounds, almost all of them over tables of a few hundred words; without BLZ_GKR_UNFUSED every round at a
+ * live length of 512 and below - all of them for m <= 10 - runs inside one block that keeps the layer's tables in LDS
+ * ("One-call GKR").
+ *   op: BLZ_TREE_PROD.  BLZ_TREE_FRAC is refused by name: it is not built.
+ *   flags: 0, or BLZ_GKR_UNFUSED: the chain of the existing step launches alone.  Both write the same bytes to the four outputs.
+ *   tree: a BLZ_TREE_PROD tree over the len leaves `a` with the default pairing, exactly as blz_ntt_mle_tree(dst = tree, a) leaves
+ *   it: layer k, 1 <= k <= m, holds len / 2^k words at word len - len / 2^(k-1); layer 0 is `a`.  Both are operands like any
+ *   other - a transform buffer or device words, at least len - 1 and len of them, not periodic - and may be the handle's two
+ *   buffers.  d_weight: max(len / 4, 1) device words, the scratch for the weight.  d_state: the transcript, one word.
+ *   THE LAYERS are taken from the root down, j = 0 .. m - 1.  lo and hi of layer j are the two halves of layer m - 1 - j of the
+ *   tree (of `a` for j = m - 1), 2^j words each.
+ *   OUTPUTS, device words:
+ *     d_rounds  3 m (m - 1) / 2 words; round i < j of layer j is the three words at word 3 (j (j - 1) / 2 + i);
+ *     d_points  m (m + 1) / 2 words; row j is j + 1 words at word j (j + 1) / 2;
+ *     d_claims  2 m words; row j is (lo_f, hi_f) at words 2 j and 2 j + 1.
+ *   LAYER j >= 1: tau is row j - 1 of d_points (tau_i paired with bit i, as blz_ntt_vec_mle_eq reads a point); the weight is
+ *   W = eq(tau_0 .. tau_{j-2}), 2^(j-1) words; the sumcheck is the one blz_ntt_sumcheck_prove enqueues under a weight over the
+ *   tables [lo, hi] and the gate + lo hi at 3 points and live length 2^j, except that round i's three words land at the place
+ *   above and its challenge at word j - 1 - i of row j of d_points: the steps bind the top variable first, so the row is left in
+ *   bit order and is the next layer's point as it stands.  The eq factor stays out of the gate as for blz_ntt_zerocheck_gate:
+ *   the words of d_rounds are u_i(0), u_i(1), u_i(2) with s_i(X) = c eq(tau_{j-1-i}, X) u_i(X).
+ *   EVERY LAYER j >= 0, behind its sumcheck (j = 0 has none): lo[0] and hi[0] - the tables at the challenges; for j = 0 the
+ *   root's own pair - are copied to row j of d_claims, one transcript step absorbs those two words as stored, and its challenge
+ *   rho_j lands at word j of row j of d_points.  lo is the half with the top bit clear: rho_j is the top variable of the layer
+ *   below, whose claim is lo_f + rho_j (hi_f - lo_f).  After the last layer that claim is the multilinear extension of the
+ *   leaves at row m - 1 of d_points.  blaze_amd/gkr.py verify_product is the verifier.
+ *   d_state is read at the start and left at the state after the last step.  The root is NOT absorbed by the call: a caller who
+ *   wants it in the transcript absorbs it with blz_ntt_fs_challenge first.
+ *   BYTES WRITTEN.  The tree is consumed.  Of each layer's halves, and of a's, only the words the chain of single ops writes may
+ *   be touched - the first half of lo and the first half of hi - and their contents afterwards are unspecified (the fused path
+ *   leaves the layers of 512 words and below as they were).  Every other byte of tree and a keeps its value: the upper half of
+ *   each half-layer, and the tree's word beyond len - 2.  Of d_weight at most len / 4 words are written: the equality table of the
+ *   largest layer, whose first len / 8 the steps then sum into.
+ *   Protocol: one blz_ntt_wait_result finishes the op and blz_ntt_last_kernel_ms then spans it; blz_ntt_reset drops it.  While
+ *   it runs, a transform buffer that tree or a names is a buffer being written, and no op starts.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing and enqueueing nothing, in this order: a null handle (refused before any other
+ *   argument is looked at); BLZ_TREE_FRAC or an unknown op; unknown flag bits; a null tree, a, d_weight, d_state, d_rounds,
+ *   d_points or d_claims, each named; len not a power of two in [2, n]; an op in flight; any operand error of blz_ntt_vec_op in
+ *   tree or a, a tree below len - 1 words, leaves below len; then per pointer, in the order d_weight, d_state, d_rounds, d_points,
+ *   d_claims: misaligned, not device memory of the handle's device or running past its allocation; then the overlaps, each message
+ *   naming both sides: a's len words against the tree's len - 1, the weight's max(len / 4, 1) against both, and each output
+ *   against all of those and against the outputs before it. */
+#define BLZ_GKR_UNFUSED 1u   /* the chain of existing launches only: the A/B side of the fused kernel */
+int blz_ntt_gkr_prove(blz_ntt* h, uint32_t op, uint32_t flags, const blz_vec_arg* tree, const blz_vec_arg* a, uint64_t len, void* d_weight,
+                      void* d_state, void* d_rounds, void* d_points, void* d_claims);
 
 /* ------------------------------------------------------------------ device / host memory helpers */
 

@@ -60,6 +60,8 @@ pub struct BlzVecCsr {
 }
 /// `BLZ_MLE_LOW`: `blz_ntt_vec_mle_fold` / `_round` pair (a\[2p\], a\[2p + 1\]) - variable 0 - instead of (a\[p\], a\[p + len / 2\]).
 pub const BLZ_MLE_LOW: u32 = 1;
+/// `BLZ_GKR_UNFUSED`: `blz_ntt_gkr_prove` takes the chain of single launches only, not its one-block kernel.
+pub const BLZ_GKR_UNFUSED: u32 = 1;
 /// `BLZ_GATE_PRODUCT`: the gate of `blz_ntt_sumcheck_step` is the product of its 1 to 3 tables.
 pub const BLZ_GATE_PRODUCT: u32 = 0;
 /// `BLZ_GATE_R1CS`: the gate is a (b c - d) over its four tables.
@@ -217,6 +219,8 @@ extern "C" {
     pub fn blz_ntt_fs_challenge(h: *mut BlzNtt, d_state: *mut c_void, words: *const BlzVecArg, count: u32, d_r: *mut c_void) -> c_int;
     pub fn blz_ntt_sumcheck_prove(h: *mut BlzNtt, gate: *const BlzSumGate, tables: *const BlzVecArg, weight: *const BlzVecArg, points: u32,
                                   len: u64, d_state: *mut c_void, d_rounds: *mut c_void, d_challenges: *mut c_void) -> c_int;
+    pub fn blz_ntt_gkr_prove(h: *mut BlzNtt, op: u32, flags: u32, tree: *const BlzVecArg, a: *const BlzVecArg, len: u64, d_weight: *mut c_void,
+                             d_state: *mut c_void, d_rounds: *mut c_void, d_points: *mut c_void, d_claims: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_op(h: *mut BlzNtt, op: c_int, buf_dst: usize, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg) -> c_int;
     pub fn blz_ntt_vec_reduce(h: *mut BlzNtt, op: c_int, a: *const BlzVecArg, b: *const BlzVecArg, d_out: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_scan(h: *mut BlzNtt, op: c_int, flags: u32, buf_dst: usize, a: *const BlzVecArg, d_total: *mut c_void) -> c_int;

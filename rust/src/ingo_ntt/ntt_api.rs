@@ -476,6 +476,30 @@ impl NTTClient {
                                      rw.as_ref().map_or(std::ptr::null(), |x| x as *const BlzVecArg), points, len, d_state, d_rounds, d_challenges))
     }
 
+    /// The GKR grand product over a product tree in one call (blz_ntt_gkr_prove).  `tree` is what `mle_tree(TreeOp::Prod, tree,
+    /// a, None, len, false)` left over the `len` = 2^m leaves `a`.  From the root down, layer j's sumcheck runs under the weight
+    /// eq(row j - 1 of the points) with every challenge made on the device - written backwards into row j, which is thereby the
+    /// next layer's point -, then the two final words go to the claims and through one more transcript step.  `d_rounds`
+    /// receives 3 m (m - 1) / 2 words, `d_points` m (m + 1) / 2, `d_claims` 2 m (`gkr_layout`); `d_weight` is max(len / 4, 1)
+    /// words of scratch; `d_state` is the transcript.  `fused` false passes BLZ_GKR_UNFUSED: the chain of single launches.
+    ///
+    /// # Safety
+    /// `tree` and `a` are consumed (the first half of each half-layer is WRITTEN); the five pointers are 16-byte aligned device
+    /// words, WRITTEN, off the tree, the leaves and each other; all stay valid until `wait_result` returns.
+    pub unsafe fn gkr_prove(&self, tree: VecOperand, a: VecOperand, len: u64, d_weight: *mut std::os::raw::c_void, d_state: *mut std::os::raw::c_void,
+                            d_rounds: *mut std::os::raw::c_void, d_points: *mut std::os::raw::c_void, d_claims: *mut std::os::raw::c_void,
+                            fused: bool) -> Result<()> {
+        let (rt, ra) = (tree.raw(), a.raw());
+        check(blz_ntt_gkr_prove(self.h, TreeOp::Prod as u32, if fused { 0 } else { BLZ_GKR_UNFUSED }, &rt, &ra, len, d_weight, d_state, d_rounds, d_points,
+                                d_claims))
+    }
+
+    /// (words of rounds, words of points, words of claims) that `gkr_prove` writes for a tree over 2^m leaves; layer j's round i
+    /// is at word 3 (j (j - 1) / 2 + i) of the rounds, its point row at word j (j + 1) / 2, its claims at word 2 j
+    pub fn gkr_layout(m: u64) -> (u64, u64, u64) {
+        (3 * m * m.saturating_sub(1) / 2, m * (m + 1) / 2, 2 * m)
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
