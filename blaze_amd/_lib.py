@@ -170,6 +170,8 @@ _SIGS = {
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "blz_ntt_gkr_prove": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_uint64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "blz_ntt_gkr_prove_frac": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg),
+                                         C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "blz_ntt_vec_op": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.POINTER(BlzVecArg)]),
     "blz_ntt_vec_reduce": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BlzVecArg), C.POINTER(BlzVecArg), C.c_void_p]),
     "blz_ntt_vec_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.POINTER(BlzVecArg), C.c_void_p]),

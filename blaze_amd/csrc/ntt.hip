@@ -1542,6 +1542,130 @@ int blz_ntt_gkr_prove(blz_ntt* h, uint32_t op, uint32_t flags, const blz_vec_arg
     }, wbuf[1]);
 }
 
+// The GKR argument over blz_ntt_mle_tree's FRACTION trees in one enqueue (include/blaze_hip.h, THE ONE-CALL FRACTION GKR PROVER;
+// kernels: ntt_fgkr.hip.hpp).  blz_ntt_gkr_prove's walk over four tables a layer: P_lo, P_hi, Q_lo, Q_hi, the halves of layer
+// m - 1 - j of the two trees (of the leaves for j = m - 1).  Below the root a layer starts with its batching challenge lambda_j
+// (a transcript step that absorbs nothing) and T = P_hi + lambda_j Q_hi written over P_hi by gate_eval: T is folded like a table,
+// so the layer gate P_lo Q_hi + Q_lo T needs no scalar and is zerocheck_gate's as it stands.  Behind the sumcheck the four final
+// words - P_hi's recovered from T's - go to d_claims and through one transcript step.  BLZ_GKR_UNFUSED takes the existing
+// launchers alone (and the claims kernel, one wave); without it the rounds at live lengths of 256 and below - all of them for
+// m <= 9 - run inside one block, h->ops->fgkr_tail.  Every check stands before the first launch.
+// (the gates are packed by blz_ntt_sumcheck_gate's own function, reached as blz_ntt_sumcheck_prove reaches it)
+static constexpr auto ntt_fgkr_describe = &ntt_gate_describe;
+int blz_ntt_gkr_prove_frac(blz_ntt* h, uint32_t flags, const blz_vec_arg* tree_p, const blz_vec_arg* tree_q, const blz_vec_arg* a_p,
+                           const blz_vec_arg* a_q, uint64_t len, void* d_weight, void* d_state, void* d_rounds, void* d_points, void* d_claims,
+                           void* d_lambdas) {
+    if (!h) return fail(BLZ_ERR_INVALID_PARAM, "null handle");
+    if (flags & ~BLZ_GKR_UNFUSED) return fail(BLZ_ERR_INVALID_PARAM, "unknown GKR flags 0x%x", flags);
+    if (!tree_p || !tree_q || !a_p || !a_q || !d_weight || !d_state || !d_rounds || !d_points || !d_claims || !d_lambdas)
+        return fail(BLZ_ERR_INVALID_PARAM, "a one-call fraction GKR prover takes %s",
+                    !tree_p ? "the numerator tree: tree_p is NULL" : !tree_q ? "the denominator tree: tree_q is NULL" : !a_p ? "the numerators: a_p is NULL"
+                    : !a_q ? "the denominators: a_q is NULL" : !d_weight ? "room for the weight: d_weight is NULL" : !d_state ? "a transcript: d_state is NULL"
+                    : !d_rounds ? "room for the rounds: d_rounds is NULL" : !d_points ? "room for the points: d_points is NULL"
+                    : !d_claims ? "room for the claims: d_claims is NULL" : "room for the layer challenges: d_lambdas is NULL");
+    NttVecCall call{h};
+    BLZ_TRY(call.live_length(len));
+    BLZ_TRY(call.begin());
+    static const char* const oname[4] = {"tree_p", "tree_q", "a_p", "a_q"};
+    const blz_vec_arg* const ov[4] = {tree_p, tree_q, a_p, a_q};
+    NttVecArg v[4] = {};
+    BLZ_TRY(call.resolve({{oname[0], ov[0], &v[0]}, {oname[1], ov[1], &v[1]}, {oname[2], ov[2], &v[2]}, {oname[3], ov[3], &v[3]}}));
+    for (int o = 0; o < 2; ++o)
+        if (v[o].mask + 1 < len - 1)
+            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: %llu words, a tree over len %llu holds len - 1", oname[o], (unsigned long long)(v[o].mask + 1),
+                        (unsigned long long)len);
+    for (int o = 2; o < 4; ++o)
+        if (v[o].mask + 1 < len)
+            return fail(BLZ_ERR_INVALID_PARAM, "operand %s: %llu words, read periodically over len %llu: the leaves are folded in place, so they are not periodic",
+                        oname[o], (unsigned long long)(v[o].mask + 1), (unsigned long long)len);
+    uint32_t m = 0;   // log2 len
+    while ((len >> m) > 1) ++m;
+    // what the op names, in the order of the checks: the four operands, the weight, the five outputs
+    struct Range { const char* name; const void* p; uint64_t words; };
+    const Range rg[10] = {{oname[0], v[0].p, len - 1}, {oname[1], v[1].p, len - 1}, {oname[2], v[2].p, len}, {oname[3], v[3].p, len},
+                          {"d_weight", d_weight, std::max<uint64_t>(len / 4, 1)}, {"d_state", d_state, 1}, {"d_rounds", d_rounds, (uint64_t)3 * m * (m - 1) / 2},
+                          {"d_points", d_points, (uint64_t)m * (m + 1) / 2}, {"d_claims", d_claims, (uint64_t)4 * m}, {"d_lambdas", d_lambdas, m}};
+    for (int o = 4; o < 10; ++o) BLZ_TRY(call.device_range(rg[o].name, "the pointer", rg[o].p, rg[o].words * 32, 16, rg[o].words, "elements"));
+    for (int o = 1; o < 10; ++o)
+        for (int i = 0; i < o; ++i)
+            if (rg[i].words && rg[o].words && NttVecCall::words_meet(rg[i].p, rg[i].words, rg[o].p, rg[o].words))
+                return fail(BLZ_ERR_INVALID_PARAM, "%s overlaps %s: %llu words against %llu", rg[o].name, rg[i].name, (unsigned long long)rg[o].words,
+                            (unsigned long long)rg[i].words);
+    int wbuf[2] = {-1, -1};   // the layers and the leaves are folded in place: a buffer any of the four names is written
+    for (int o = 0; o < 4; ++o)
+        if (!ov[o]->d_ptr && wbuf[0] != (int)ov[o]->buf && wbuf[1] != (int)ov[o]->buf) wbuf[wbuf[0] < 0 ? 0 : 1] = (int)ov[o]->buf;
+    const bool fused = !(flags & BLZ_GKR_UNFUSED);
+    const uint32_t keep = ntt_fs_keep_bits(h->field);
+    uint32_t* const weight = (uint32_t*)d_weight;
+    uint32_t* const points = (uint32_t*)d_points;
+    uint32_t* const lambdas = (uint32_t*)d_lambdas;
+    NttGate g, gt;
+    {
+        blz_sum_gate layer{};   // + P_lo Q_hi + Q_lo T over [P_lo, T, Q_lo, Q_hi]
+        layer.ntables = 4, layer.nterms = 2, layer.common = -1;
+        layer.term[0].nfactors = 2, layer.term[0].factor[0] = 0, layer.term[0].factor[1] = 3;
+        layer.term[1].nfactors = 2, layer.term[1].factor[0] = 2, layer.term[1].factor[1] = 1;
+        BLZ_TRY(ntt_fgkr_describe(&layer, g));
+        blz_sum_gate lin{};   // T = + P_hi + lambda Q_hi over [P_hi, lambda, Q_hi]
+        lin.ntables = 3, lin.nterms = 2, lin.common = -1;
+        lin.term[0].nfactors = 1, lin.term[0].factor[0] = 0;
+        lin.term[1].nfactors = 2, lin.term[1].factor[0] = 1, lin.term[1].factor[1] = 2;
+        BLZ_TRY(ntt_fgkr_describe(&lin, gt));
+    }
+    NttFgkrTail tail{v[0].p, v[1].p, v[2].p, v[3].p, weight, (uint32_t*)d_state, (uint32_t*)d_rounds, points, (uint32_t*)d_claims, lambdas, m, 0, 0, 0, 0, keep};
+    return call.enqueue(wbuf[0], [&](uint32_t*) {
+        const uint64_t no_rot[BLZ_GATE_MAX_TABLES] = {};
+        for (uint32_t j = 0; j < m; ++j) {
+            const uint64_t live = 1ull << j;   // words of each of the four tables
+            if (fused && live <= FGKR_TAIL_LEN) {   // every whole layer that fits, in one launch
+                tail.first = j;
+                while (j + 1 < m && (2ull << j) <= FGKR_TAIL_LEN) ++j;
+                tail.last = j + 1, tail.tail = 0, tail.claims_only = 0;
+                BLZ_TRY(h->ops->fgkr_tail(h->stream, tail));
+                continue;
+            }
+            const uint32_t* const plo = j + 1 == m ? v[2].p : v[0].p + (len - 4 * live) * 8;
+            const uint32_t* const qlo = j + 1 == m ? v[3].p : v[1].p + (len - 4 * live) * 8;
+            uint32_t* const rows = (uint32_t*)d_rounds + (size_t)3 * ((size_t)j * (j - 1) / 2) * 8;
+            uint32_t* const row = points + ((size_t)j * (j + 1) / 2) * 8;   // row j of the points; row j - 1 ends where it starts
+            tail.first = j, tail.last = j + 1;
+            if (j >= 1) {
+                uint32_t* const lambda = lambdas + (size_t)j * 8;
+                uint32_t* const phi = const_cast<uint32_t*>(plo) + live * 8;
+                BLZ_TRY(ntt_fs_absorb(h->stream, d_state, nullptr, 0, lambda, keep));
+                gt.t[0] = NttVecArg{phi, live - 1};
+                gt.t[1] = NttVecArg{lambda, 0};
+                gt.t[2] = NttVecArg{qlo + live * 8, live - 1};
+                BLZ_TRY(h->ops->gate_eval(h->stream, phi, gt, no_rot, live));
+                g.t[0] = NttVecArg{plo, live - 1};
+                g.t[1] = NttVecArg{phi, live - 1};
+                g.t[2] = NttVecArg{qlo, live - 1};
+                g.t[3] = NttVecArg{qlo + live * 8, live - 1};
+                const NttVecArg vw{weight, std::max<uint64_t>(live / 2, 1) - 1};
+                BLZ_TRY(h->ops->vec_mle_eq(h->stream, weight, row - (size_t)j * 8, j - 1, call.ws));
+                BLZ_TRY(h->ops->zerocheck_gate(h->stream, g, vw, nullptr, 3, live, rows, call.ws));
+                // the pairs (transcript step, step with r): all but the last variable's, or down to the live length the block takes
+                const uint32_t chain = fused ? j - FGKR_TAIL_LOG : j;
+                for (uint32_t i = 0; i < chain; ++i) {
+                    uint32_t* const r = row + (size_t)(j - 1 - i) * 8;   // backwards: the row ends up in bit order
+                    BLZ_TRY(ntt_fs_absorb(h->stream, d_state, rows + (size_t)i * 3 * 8, 3, r, keep));
+                    if (i + 1 < j) BLZ_TRY(h->ops->zerocheck_gate(h->stream, g, vw, r, 3, live >> i, rows + (size_t)(i + 1) * 3 * 8, call.ws));
+                    else BLZ_TRY(h->ops->sumcheck_gate(h->stream, g, r, 0, 2, nullptr, call.ws));
+                }
+                if (fused) {
+                    tail.tail = 1, tail.claims_only = 0;
+                    BLZ_TRY(h->ops->fgkr_tail(h->stream, tail));
+                    continue;
+                }
+            }
+            tail.tail = 0, tail.claims_only = 1;
+            BLZ_TRY(h->ops->fgkr_tail(h->stream, tail));
+            BLZ_TRY(ntt_fs_absorb(h->stream, d_state, (uint32_t*)d_claims + (size_t)4 * j * 8, 4, row + (size_t)j * 8, keep));
+        }
+        return (int)BLZ_OK;
+    }, wbuf[1]);
+}
+
 int blz_ntt_last_kernel_ms(blz_ntt* h, float* out) {
     if (!h || !out) return fail(BLZ_ERR_INVALID_PARAM, "null argument");
     *out = h->last_ms;

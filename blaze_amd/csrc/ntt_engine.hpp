@@ -120,6 +120,21 @@ struct NttGkrTail {
     uint32_t *state, *rounds, *points, *claims;
     uint32_t m, first, last, tail, claims_only, keep_bits;
 };
+// One launch of the fraction GKR's own kernels (blz_ntt_gkr_prove_frac; kernels and the layout: ntt_fgkr.hip.hpp), by value in the
+// kernel arguments: NttGkrTail over the numerator and denominator trees and leaves, with the layer challenges beside the four
+// outputs.  The layers [first, last) are run by ONE block:
+//   tail != 0    last == first + 1 and 2^first > 256: the chain of step launches has written lambda and T = P_hi + lambda Q_hi
+//                (over P_hi), brought the layer down to the live length 256 and left its current row in `rounds`;
+//   tail == 0    whole layers, 2^(last - 1) <= 256: nothing of them has run yet;
+//   claims_only  no sumcheck: word 0 of the four tables of layer `first` (P_hi's from T and lambda) goes to its row of the claims.
+constexpr int FGKR_TAIL_LOG = 8;
+constexpr uint32_t FGKR_TAIL_LEN = 1u << FGKR_TAIL_LOG;   // the largest live length the block takes: 4 x 256 + 128 words are 36 KiB of LDS
+struct NttFgkrTail {
+    const uint32_t *tree_p, *tree_q, *a_p, *a_q;
+    const uint32_t* weight;
+    uint32_t *state, *rounds, *points, *claims, *lambdas;
+    uint32_t m, first, last, tail, claims_only, keep_bits;
+};
 constexpr int NTT_VEC_OPS = 6;              // enum blz_vec_op: ADD SUB MUL MULADD MULSUB INV
 constexpr uint64_t NTT_VEC_INV_TILE = 1024;  // batch inversion: elements per block (256 lanes x 4); one 32-byte total per tile
 constexpr int NTT_FOLD_OPS = 3;              // enum blz_fold_op: SUM DOT EVAL
@@ -215,6 +230,9 @@ struct NttFieldOps {
     // The small rounds of a GKR grand product in one block (blz_ntt_gkr_prove; kernels: ntt_gkr.hip.hpp): the layers g names, or
     // the claims of one layer.  Nothing of the tree, the leaves or the weight is written
     int (*gkr_tail)(hipStream_t st, const NttGkrTail& g);
+    // The same for a fraction tree (blz_ntt_gkr_prove_frac; kernels: ntt_fgkr.hip.hpp): the layers g names over four tables, or the
+    // claims of one layer.  Nothing of the trees, the leaves or the weight is written
+    int (*fgkr_tail)(hipStream_t st, const NttFgkrTail& g);
 };
 const NttFieldOps& ntt_ops_bls377();
 const NttFieldOps& ntt_ops_bls381();

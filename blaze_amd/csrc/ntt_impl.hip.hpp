@@ -18,6 +18,7 @@
 #include "ntt_lineval.hip.hpp"
 #include "ntt_tree.hip.hpp"
 #include "ntt_gkr.hip.hpp"
+#include "ntt_fgkr.hip.hpp"
 
 namespace blz {
 
@@ -541,6 +542,7 @@ NttFieldOps make_ntt_ops() {
     o.zerocheck_gate = &ntt_zerocheck_gate_t<Fr>;
     o.mle_tree = &ntt_mle_tree_t<Fr>;
     o.gkr_tail = &ntt_gkr_tail_t<Fr>;
+    o.fgkr_tail = &ntt_fgkr_tail_t<Fr>;
     return o;
 }
 

@@ -590,6 +590,42 @@ class NTTClient(DriverPrimitive[NTT, NttInit, NTTInput, bytes]):
         self._vec_keep = (tree, a, weight, state, rounds, points, claims)
         return rounds, points, claims
 
+    def gkr_prove_frac(self, tree_p, tree_q, a_p, a_q, state: DeviceBuffer, length: Optional[int] = None, weight: Optional[DeviceBuffer] = None,
+                       rounds: Optional[DeviceBuffer] = None, points: Optional[DeviceBuffer] = None, claims: Optional[DeviceBuffer] = None,
+                       lambdas: Optional[DeviceBuffer] = None, fused: bool = True):
+        """The GKR argument over a fraction tree (logUp-GKR) in ONE call (blz_ntt_gkr_prove_frac).  `tree_p`, `tree_q` are what
+        mle_tree(tree_p, a_p, TREE_FRAC, dst_q=tree_q, a_q=a_q) left (default pairing) over the `length` = 2^m numerators `a_p`
+        and denominators `a_q` (None: all of `a_p`); the four are ints (transform buffers) or DeviceBuffers, none periodic - a
+        one-word numerator is expanded with vec_gather first - and all are consumed.  From the root down, layer j >= 1 draws a
+        batching challenge lambda_j from the transcript, writes T = P_hi + lambda_j Q_hi over P_hi and proves
+        P(tau) + lambda_j Q(tau) = sum eq(tau, p) (P_lo Q_hi + Q_lo T) by a sumcheck under the weight eq(point of the layer above)
+        with every challenge made on the device; then the four final words (P_lo, P_hi, Q_lo, Q_hi at the challenges) go to
+        `claims` and through one more transcript step.  `state` is the transcript, one word, read and left at the state after
+        the last step; the roots are not absorbed.  `weight` is the scratch for the weight, max(length / 4, 1) words.  Returns
+        (rounds, points, claims, lambdas): DeviceBuffers of 3 m (m - 1) / 2, m (m + 1) / 2, 4 m and m words (the ones passed,
+        or fresh ones; word 0 of lambdas is never written) laid out as blaze_amd.gkr.layout_frac(m) says;
+        blaze_amd.gkr.verify_fraction checks them and returns the leaves' claims and point.  fused=False takes the chain of
+        single launches only (GKR_UNFUSED): the same bytes, slower.  Finished by wait_result()."""
+        from . import gkr
+        length = self._mle_len(length, a_p)
+        lay = gkr.layout_frac(max(int(length).bit_length() - 1, 1))
+        dev = self.driver_client.id
+        if weight is None:
+            weight = DeviceBuffer(dev, NTT_WORD_SIZE * lay.weight_words)
+        if rounds is None:
+            rounds = DeviceBuffer(dev, NTT_WORD_SIZE * max(lay.rounds_words, 1))
+        if points is None:
+            points = DeviceBuffer(dev, NTT_WORD_SIZE * lay.points_words)
+        if claims is None:
+            claims = DeviceBuffer(dev, NTT_WORD_SIZE * lay.claims_words)
+        if lambdas is None:
+            lambdas = DeviceBuffer(dev, NTT_WORD_SIZE * lay.lambdas_words)
+        args = [self._vec_arg(x) for x in (tree_p, tree_q, a_p, a_q)]
+        check(lib().blz_ntt_gkr_prove_frac(self._h, 0 if fused else self.GKR_UNFUSED, *[C.byref(v) for v in args], int(length), weight.ptr, state.ptr,
+                                           rounds.ptr, points.ptr, claims.ptr, lambdas.ptr))
+        self._vec_keep = (tree_p, tree_q, a_p, a_q, weight, state, rounds, points, claims, lambdas)
+        return rounds, points, claims, lambdas
+
     def scalar(self, value: int) -> DeviceBuffer:
         """A one-element operand for vec_op: `value` (any 256-bit integer, taken as its residue) in device memory."""
         v = int(value)

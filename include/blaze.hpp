@@ -404,6 +404,19 @@ class NTTClient : public DriverPrimitive<NTT, NttInit, NTTInput, std::vector<uin
     static uint64_t gkr_round(uint32_t j, uint32_t i) { return 3 * ((uint64_t)j * (j - 1) / 2 + i); }
     static uint64_t gkr_point_row(uint32_t j) { return (uint64_t)j * (j + 1) / 2; }
     static uint64_t gkr_claim_row(uint32_t j) { return 2ull * j; }
+    // the GKR argument over a fraction tree (logUp-GKR) in one call (blz_ntt_gkr_prove_frac): tree_p, tree_q are what
+    // mle_tree(BLZ_TREE_FRAC, tree_p, a_p, len, 0, tree_q, a_q) left over the len = 2^m numerators a_p and denominators a_q, none
+    // periodic.  Layer j >= 1 draws lambda_j, writes T = P_hi + lambda_j Q_hi over P_hi and proves P_lo Q_hi + Q_lo T under the
+    // weight; four final words a layer.  d_rounds and d_points as for gkr_prove, d_claims 4 m words, d_lambdas m (word 0 is never
+    // written); fused == false: BLZ_GKR_UNFUSED.  All four operands are consumed
+    void gkr_prove_frac(const blz_vec_arg* tree_p, const blz_vec_arg* tree_q, const blz_vec_arg* a_p, const blz_vec_arg* a_q, uint64_t len, void* d_weight,
+                        void* d_state, void* d_rounds, void* d_points, void* d_claims, void* d_lambdas, bool fused = true) {
+        check(blz_ntt_gkr_prove_frac(h_, fused ? 0u : BLZ_GKR_UNFUSED, tree_p, tree_q, a_p, a_q, len, d_weight, d_state, d_rounds, d_points, d_claims, d_lambdas));
+    }
+    // the words of gkr_prove_frac's claims and lambdas, and the word of layer j's claims row (rounds and points: gkr_prove's)
+    static uint64_t gkr_frac_claims_words(uint32_t m) { return 4ull * m; }
+    static uint64_t gkr_frac_lambdas_words(uint32_t m) { return m; }
+    static uint64_t gkr_frac_claim_row(uint32_t j) { return 4ull * j; }
     // {device bytes held, pass 2 reads its factor table, pass 1 boundary table, log_size}
     std::array<uint64_t, 4> info() {
         std::array<uint64_t, 4> v{};

@@ -1132,7 +1132,7 @@ int blz_ntt_sumcheck_prove(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_a
  * m (m - 1) / 2 sumcheck rounds, almost all of them over tables of a few hundred words; without BLZ_GKR_UNFUSED every round at a
  * live length of 512 and below - all of them for m <= 10 - runs inside one block that keeps the layer's tables in LDS
  * ("One-call GKR").
- *   op: BLZ_TREE_PROD.  BLZ_TREE_FRAC is refused by name: it is not built.
+ *   op: BLZ_TREE_PROD.  BLZ_TREE_FRAC is refused by name: it is not built here (blz_ntt_gkr_prove_frac takes fraction trees).
  *   flags: 0, or BLZ_GKR_UNFUSED: the chain of the existing step launches alone.  Both write the same bytes to the four outputs.
  *   tree: a BLZ_TREE_PROD tree over the len leaves `a` with the default pairing, exactly as blz_ntt_mle_tree(dst = tree, a) leaves
  *   it: layer k, 1 <= k <= m, holds len / 2^k words at word len - len / 2^(k-1); layer 0 is `a`.  Both are operands like any
@@ -1174,6 +1174,64 @@ int blz_ntt_sumcheck_prove(blz_ntt* h, const blz_sum_gate* gate, const blz_vec_a
 #define BLZ_GKR_UNFUSED 1u   /* the chain of existing launches only: the A/B side of the fused kernel */
 int blz_ntt_gkr_prove(blz_ntt* h, uint32_t op, uint32_t flags, const blz_vec_arg* tree, const blz_vec_arg* a, uint64_t len, void* d_weight,
                       void* d_state, void* d_rounds, void* d_points, void* d_claims);
+/* THE ONE-CALL FRACTION GKR PROVER.  The GKR argument over a FRACTION tree (logUp-GKR, memory checking with fractions), enqueued
+ * by ONE call with no host wait inside: blz_ntt_gkr_prove over four tables a layer.  A sum of len = 2^m fractions a_p / a_q is m
+ * layers and m (m - 1) / 2 sumcheck rounds; without BLZ_GKR_UNFUSED every round at a live length of 256 and below - all of them
+ * for m <= 9 - runs inside one block that keeps the layer's four tables in LDS ("One-call fraction GKR").
+ *   flags: 0, or BLZ_GKR_UNFUSED: the chain of the existing launches alone.  Both write the same bytes to the five outputs.
+ *   tree_p, tree_q: the numerator and the denominator tree, exactly as blz_ntt_mle_tree(BLZ_TREE_FRAC, dst = tree_p, dst_q =
+ *   tree_q, a_p, a_q, len) left them with the default pairing: layer k, 1 <= k <= m, holds len / 2^k words at word len - len /
+ *   2^(k-1) of each; layer 0 is the leaves a_p, a_q.  2 <= len <= n.  All four are operands like any other - a transform buffer
+ *   or device words, at least len - 1 (a tree) and len (leaves) of them - and none is periodic: a one-word numerator 1 is
+ *   expanded by the caller first (blz_ntt_vec_gather), because the leaves are folded in place.  At most two of the four can name
+ *   a transform buffer.  d_weight: max(len / 4, 1) device words, the scratch for the weight, used as in blz_ntt_gkr_prove.
+ *   d_state: the transcript, one word.
+ *   THE LAYERS are taken from the root down, j = 0 .. m - 1.  P_lo, P_hi are the two halves of layer m - 1 - j of tree_p (of a_p
+ *   for j = m - 1), Q_lo, Q_hi the same of tree_q / a_q, 2^j words each; lo is the half with the top bit clear.
+ *   OUTPUTS, device words:
+ *     d_rounds   3 m (m - 1) / 2 words; round i < j of layer j is the three words u_i(0), u_i(1), u_i(2) at word
+ *                3 (j (j - 1) / 2 + i);
+ *     d_points   m (m + 1) / 2 words; row j is j + 1 words at word j (j + 1) / 2;
+ *     d_claims   4 m words; row j is (P_lo_f, P_hi_f, Q_lo_f, Q_hi_f) at word 4 j;
+ *     d_lambdas  m words; word j >= 1 is lambda_j.  Word 0 is never written and keeps its bytes.
+ *   LAYER j >= 1, in order.  Its claims from the layer above are P(tau), Q(tau) with tau row j - 1 of d_points.
+ *     1. One transcript step with count 0 (digest = SHA3-256(state)) writes the batching challenge lambda_j to word j of d_lambdas.
+ *        The layer proves  P(tau) + lambda_j Q(tau) = sum_p eq(tau, p) [ P_lo Q_hi + P_hi Q_lo + lambda_j Q_lo Q_hi ]
+ *                                                  = sum_p eq(tau, p) [ P_lo Q_hi + Q_lo T ],  T = P_hi + lambda_j Q_hi.
+ *     2. T is written over the 2^j words of P_hi, every word canonical.  T is linear in the tables, so binding a variable
+ *        commutes with it, and the gate needs no scalar.
+ *     3. W = eq(tau_0 .. tau_{j-2}), 2^(j-1) words, is built (tau_i paired with bit i, as blz_ntt_vec_mle_eq reads a point).
+ *     4. The sumcheck blz_ntt_sumcheck_prove enqueues under a weight, over the tables [P_lo, T, Q_lo, Q_hi] and the gate
+ *        + [0, 3] + [2, 1] at 3 points and live length 2^j, except that round i's three words land at the place above and its
+ *        challenge at word j - 1 - i of row j of d_points: the steps bind the top variable first, so the row is left in bit order.
+ *        The eq factor stays out of the gate as for blz_ntt_zerocheck_gate: s_i(X) = c eq(tau_{j-1-i}, X) u_i(X).
+ *     5. The claims are P_lo_f, T_f - lambda_j Q_hi_f (canonical), Q_lo_f and Q_hi_f: the four tables at the challenges.
+ *   LAYER 0 has no lambda and no sumcheck: its claims are the root's four children copied as stored.
+ *   EVERY LAYER j >= 0, behind its claims: ONE transcript step absorbs the four claim words as stored - 160 bytes with the state,
+ *   two blocks of SHA3-256's 136-byte rate - and its challenge rho_j lands at word j of row j of d_points.  The next layer's
+ *   claims are P = P_lo_f + rho_j (P_hi_f - P_lo_f) and the same for Q.  After the last layer they are the multilinear extensions
+ *   of a_p and of a_q at row m - 1 of d_points.  The verifier holds a layer's end to
+ *   c (P_lo_f Q_hi_f + P_hi_f Q_lo_f + lambda_j Q_lo_f Q_hi_f) = claim; blaze_amd/gkr.py verify_fraction is that verifier.
+ *   d_state is read at the start and left at the state after the last step.  The roots are NOT absorbed by the call: a caller who
+ *   wants them in the transcript absorbs them with blz_ntt_fs_challenge first.
+ *   BYTES WRITTEN.  The trees and the leaves are consumed.  Of each layer of tree_p / a_p only the whole hi half (T) and the
+ *   first half of the lo half may be touched; of tree_q / a_q only the first half of each half.  Their contents afterwards are
+ *   unspecified (the fused path leaves the layers it takes whole, 256 words a table and below, untouched).  Every other byte
+ *   keeps its value, word len - 2 (the root) and everything behind it included.  Of d_weight at most len / 4 words are written,
+ *   of d_lambdas m - 1.
+ *   Protocol: blz_ntt_gkr_prove's.  One blz_ntt_wait_result finishes the op and blz_ntt_last_kernel_ms then spans it;
+ *   blz_ntt_reset drops it.  While it runs, a transform buffer that any of the four operands names is a buffer being written, and
+ *   no op starts.
+ *   BLZ_ERR_INVALID_PARAM, changing nothing and enqueueing nothing, in this order: a null handle (refused before any other
+ *   argument is looked at); unknown flag bits; a null tree_p, tree_q, a_p, a_q, d_weight, d_state, d_rounds, d_points, d_claims
+ *   or d_lambdas, each named; len not a power of two in [2, n]; an op in flight; any operand error of blz_ntt_vec_op in the four
+ *   operands; a tree below len - 1 words, leaves below len; then per pointer, in the order d_weight, d_state, d_rounds, d_points,
+ *   d_claims, d_lambdas: misaligned, not device memory of the handle's device or running past its allocation; then the overlaps,
+ *   each message naming both sides: every range against every range before it, in the order tree_p, tree_q (len - 1 words
+ *   each), a_p, a_q (len each), the weight's max(len / 4, 1), then the five outputs. */
+int blz_ntt_gkr_prove_frac(blz_ntt* h, uint32_t flags, const blz_vec_arg* tree_p, const blz_vec_arg* tree_q, const blz_vec_arg* a_p,
+                           const blz_vec_arg* a_q, uint64_t len, void* d_weight, void* d_state, void* d_rounds, void* d_points, void* d_claims,
+                           void* d_lambdas);
 
 /* ------------------------------------------------------------------ device / host memory helpers */
 

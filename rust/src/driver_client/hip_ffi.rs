@@ -221,6 +221,9 @@ extern "C" {
                                   len: u64, d_state: *mut c_void, d_rounds: *mut c_void, d_challenges: *mut c_void) -> c_int;
     pub fn blz_ntt_gkr_prove(h: *mut BlzNtt, op: u32, flags: u32, tree: *const BlzVecArg, a: *const BlzVecArg, len: u64, d_weight: *mut c_void,
                              d_state: *mut c_void, d_rounds: *mut c_void, d_points: *mut c_void, d_claims: *mut c_void) -> c_int;
+    pub fn blz_ntt_gkr_prove_frac(h: *mut BlzNtt, flags: u32, tree_p: *const BlzVecArg, tree_q: *const BlzVecArg, a_p: *const BlzVecArg,
+                                  a_q: *const BlzVecArg, len: u64, d_weight: *mut c_void, d_state: *mut c_void, d_rounds: *mut c_void, d_points: *mut c_void,
+                                  d_claims: *mut c_void, d_lambdas: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_op(h: *mut BlzNtt, op: c_int, buf_dst: usize, a: *const BlzVecArg, b: *const BlzVecArg, c: *const BlzVecArg) -> c_int;
     pub fn blz_ntt_vec_reduce(h: *mut BlzNtt, op: c_int, a: *const BlzVecArg, b: *const BlzVecArg, d_out: *mut c_void) -> c_int;
     pub fn blz_ntt_vec_scan(h: *mut BlzNtt, op: c_int, flags: u32, buf_dst: usize, a: *const BlzVecArg, d_total: *mut c_void) -> c_int;

@@ -500,6 +500,33 @@ impl NTTClient {
         (3 * m * m.saturating_sub(1) / 2, m * (m + 1) / 2, 2 * m)
     }
 
+    /// The GKR argument over a fraction tree (logUp-GKR) in one call (blz_ntt_gkr_prove_frac).  `tree_p`, `tree_q` are what
+    /// `mle_tree(TreeOp::Frac, ..)` left over the `len` = 2^m numerators `a_p` and denominators `a_q`; none of the four is
+    /// periodic.  From the root down, layer j >= 1 draws the batching challenge lambda_j from the transcript, writes
+    /// T = P_hi + lambda_j Q_hi over P_hi and proves sum eq (P_lo Q_hi + Q_lo T) under the weight eq(row j - 1 of the points);
+    /// the four final words (P_lo, P_hi, Q_lo, Q_hi at the challenges) go to the claims and through one transcript step.
+    /// `d_rounds` and `d_points` as for `gkr_prove`, `d_claims` 4 m words, `d_lambdas` m words of which word 0 is never written
+    /// (`gkr_layout_frac`).  `fused` false passes BLZ_GKR_UNFUSED: the chain of single launches.
+    ///
+    /// # Safety
+    /// The four operands are consumed (of the numerators the whole hi half and the first half of the lo half of each layer is
+    /// WRITTEN, of the denominators the first half of each half); the six pointers are 16-byte aligned device words, WRITTEN,
+    /// off the operands and each other; all stay valid until `wait_result` returns.
+    pub unsafe fn gkr_prove_frac(&self, tree_p: VecOperand, tree_q: VecOperand, a_p: VecOperand, a_q: VecOperand, len: u64,
+                                 d_weight: *mut std::os::raw::c_void, d_state: *mut std::os::raw::c_void, d_rounds: *mut std::os::raw::c_void,
+                                 d_points: *mut std::os::raw::c_void, d_claims: *mut std::os::raw::c_void, d_lambdas: *mut std::os::raw::c_void,
+                                 fused: bool) -> Result<()> {
+        let (tp, tq, ap, aq) = (tree_p.raw(), tree_q.raw(), a_p.raw(), a_q.raw());
+        check(blz_ntt_gkr_prove_frac(self.h, if fused { 0 } else { BLZ_GKR_UNFUSED }, &tp, &tq, &ap, &aq, len, d_weight, d_state, d_rounds, d_points,
+                                     d_claims, d_lambdas))
+    }
+
+    /// (words of rounds, of points, of claims, of lambdas) that `gkr_prove_frac` writes for trees over 2^m leaves; rounds and
+    /// points are laid out as `gkr_layout` says, layer j's four claims are at word 4 j, lambda_j at word j
+    pub fn gkr_layout_frac(m: u64) -> (u64, u64, u64, u64) {
+        (3 * m * m.saturating_sub(1) / 2, m * (m + 1) / 2, 4 * m, m)
+    }
+
     pub fn reset_engine(&self) -> Result<()> {
         check(unsafe { blz_ntt_reset(self.h) })
     }
