@@ -67,6 +67,66 @@ void arena_drop_table(Arena& a, ArenaExtent& x) {
     arena_drop_build(a, x);
 }
 
+static thread_local const void* g_table_pin = nullptr;
+static thread_local bool g_table_pin_skipped = false;
+void table_pin(const void* rows) {
+    g_table_pin = rows;
+    g_table_pin_skipped = false;
+}
+bool table_pin_skipped() { return g_table_pin_skipped; }
+
+size_t arena_release_auto_tables(Arena& a) {
+    auto pinned = [](const ArenaExtent::WindowTable& t) {
+        return g_table_pin && (const char*)g_table_pin >= (const char*)t.p && (const char*)g_table_pin < (const char*)t.p + t.bytes;
+    };
+    bool any = false;
+    for (const auto& x : a.ext) {
+        if (x.build.tab && x.build.auto_built) any = true;
+        for (const auto& t : x.tables) {
+            if (!t.auto_built) continue;
+            if (pinned(t)) g_table_pin_skipped = true;
+            else any = true;
+        }
+    }
+    if (!any) return 0;
+    // tasks in flight gather from the tables, a build in flight writes its own: bounded drain first (on expiry nothing is freed)
+    if (sync_device_bounded("memory pressure: drain before the auto-built window tables go") != BLZ_OK) return 0;
+    size_t freed = 0;
+    for (auto& x : a.ext) {
+        bool dropped = false;
+        if (x.build.tab && x.build.auto_built) {
+            freed += x.build.bytes;
+            arena_drop_build(a, x);
+            dropped = true;
+        }
+        for (size_t k = x.tables.size(); k-- > 0;) {
+            if (!x.tables[k].auto_built || pinned(x.tables[k])) continue;
+            freed += x.tables[k].bytes;
+            (void)hipFree(x.tables[k].p);
+            x.tables.erase(x.tables.begin() + (long)k);
+            dropped = true;
+        }
+        if (!dropped) continue;
+        if (x.tables.empty()) x.tab_dirty_lo = x.tab_dirty_hi = 0;
+        x.table_refused = true;   // (no rebuild into the same shortage: the next write re-arms the policy)
+        x.reuse = ArenaExtent::Reuse();
+    }
+    (void)hipGetLastError();   // (the failed allocation's sticky code: the caller's retry starts clean)
+    BLZ_LOG(1, "window table: memory pressure - %zu bytes of auto-built tables released; their extents take the plain path until the next write", freed);
+    return freed;
+}
+
+size_t release_auto_tables_on_oom() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    Arena& A = arena_for(dev);
+    std::lock_guard<std::mutex> lk(A.mu);
+    return arena_release_auto_tables(A);
+}
+
 void arena_free_extent(Arena& a, ArenaExtent& x) {
     if (x.raw) {
         if (x.imported) (void)hipIpcCloseMemHandle(x.raw);

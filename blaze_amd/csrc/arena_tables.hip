@@ -7,7 +7,18 @@
 
 namespace blz {
 
-bool wants_table_mode(const blz_msm* h) { return h->pf == 1 && h->window_table != 0; }
+// The handle asked for tables (blz_msm_set_window_table 1 | 2): its launches restore a dieted extent's raw bytes, so the arena diet
+// stays away from its extents.  A handle that left the mode unset (the auto policy below) is a table handle only while a table of
+// its bases exists or is being built - which arena_diet_step sees on the extent itself (build.tab, tables) - and is dieted like a
+// plain handle until then.
+bool wants_table_mode(const blz_msm* h) { return h->pf == 1 && h->window_table > 0; }
+
+// The auto policy applies: the mode was never set on this handle, the process did not switch the policy off
+// (BLAZE_MSM_PLAN auto_table=0), and the handle is of the kind a table pays for - pf = 1, bases addressed in the arena
+// (PointMemoryType HBM), a BLS curve (as mode 1: BN254 loses with a table).
+bool auto_table_handle(const blz_msm* h) {
+    return h->window_table < 0 && h->pf == 1 && h->mem_type == BLZ_HBM && h->curve != BLZ_BN254 && plan_override("auto_table", 1) != 0;
+}
 
 // Resolve the Montgomery-form view of `npts` points stored at arena offset `pos`: (re)builds the part of the
 // extent's shadow that is stale, on this handle's main stream, and orders this stream behind conversions other
@@ -44,7 +55,19 @@ int arena_points_mont(blz_msm* h, uint64_t pos, uint32_t npts, const void** out,
             e->mont = nullptr;
         }
         e->mont_bytes = want_bytes + 16;
-        BLZ_HIP(hipMalloc(&e->mont, e->mont_bytes), BLZ_ERR_UNKNOWN);
+        hipError_t he_mont = hipMalloc(&e->mont, e->mont_bytes);
+        if (he_mont != hipSuccess) {
+            // a full device: the auto-built window tables go, once (arena.hip arena_release_auto_tables), and the allocation is retried
+            (void)hipGetLastError();
+            e->mont = nullptr;
+            if (arena_release_auto_tables(A) > 0) he_mont = hipMalloc(&e->mont, e->mont_bytes);
+        }
+        if (he_mont != hipSuccess) {
+            e->mont = nullptr;
+            e->mont_bytes = 0;
+            e->mont_curve = -1;
+            return fail_hip(BLZ_ERR_UNKNOWN, "hipMalloc of a Montgomery copy failed: %s", hipGetErrorString(he_mont));
+        }
         e->mont_curve = fmt;   // curve and layout of the copy (BN254 has two: msm_engine.hpp `repr`; bit 16: even bases only)
         e->mont_phase = phase;
         e->dirty_lo = 0;
@@ -209,18 +232,35 @@ int arena_precompute_check(blz_msm* h, uint64_t pos, uint32_t nelem, bool* ok, u
 // had: it is still being built, there is no memory for it, a base has even order, or the task is over a sub-range whose
 // best window width is not the table's.
 //
-// The build is never one blocking lump inside a task (round 3 built synchronously inside the first task's launch: 3.1 s for
+// The build is never one blocking lump inside a HOST CALL (round 3 built synchronously inside the first task's launch: 3.1 s for
 // 2^26 bases in a call a host expects to take milliseconds), and it does not run BESIDE the tasks either - measured
 // (profiles/r04_window_table_async.txt): on a lowest-priority stream its long-lived waves hold their registers and halve the
 // tasks' speed for as long as it takes; confined to a quarter of the CUs it is worse (the accumulation's blocks on the shared CUs
-// issue behind the build's older waves and become the kernel's tail).  So the build is PACED by the tasks: it is cut into chunks
+// issue behind the build's older waves and become the kernel's tail).  For the handles that opted in (modes 1 and 2) the build is PACED by the tasks: it is cut into chunks
 // of TABLE_BUILD_CHUNK bases (~5.5 ms of the chip), every task launched over the bases first enqueues `chunk_budget` of them on
 // its own main stream - a fixed, small surcharge per task while the table is being built - and keeps taking the plain path;
 // the first task launched after the last chunk has completed adopts the table.  blz_msm_prepare_window_table enqueues ALL the
 // remaining chunks at once for a host that would rather pay the build now.  Results are bit-identical either way
 // (tests/test_gpu_msm_table.py).
+//
+// AUTO (auto_policy: a handle whose mode was never set, auto_table_handle above; tests/test_gpu_msm_table_auto.py).  Such a handle
+// is served the tables the policy built, and the policy builds when a task of at least auto_table_min bases (2^24: the sizes at
+// which the gain is measured, msm.hip; BLAZE_MSM_PLAN auto_table_min=N) is the SECOND scalars-only task in a row over the
+// identical bases, scalar range and format with no write in between (ArenaExtent::Reuse - one lone task over freshly loaded
+// bases never pays for a table), and the table takes no more than half of the device memory free at that moment
+// (BLAZE_MSM_PLAN table_budget_bytes=N: an absolute cap instead) on top of the fit check every build passes.  A refusal stops
+// new builds until the next write, as ever.  Pacing is the wrong tool here: four chunks per task are 86 tasks at +25 ms each
+// before a 2^26 table exists - a short stream would get slower and never reach it - against 2.3 s of the chip once.  So on the
+// trigger ALL chunks are enqueued at once on the handle's main stream (the path of prepare_window_table with a wait), AHEAD of
+// the triggering task's own kernels: the host call returns as soon as the launches are queued, the triggering task takes the
+// plain path and delivers one late result (the build's time on top of its own), and the first task launched after the build has
+// completed - the one submitted when the late result is collected - adopts the table.  (Behind the triggering task the build
+// would delay the NEXT task instead and the stream would switch one task later.)  "Never one lump" thus still holds for the host
+// call and for the opt-in modes; it no longer holds for the stream of an auto handle.  Auto-built tables are the library's own
+// decision: under memory pressure they are given back (arena.hip arena_release_auto_tables); a table a handle asked for is not
+// served to an unset handle, and the policy builds no second table beside it.
 constexpr uint32_t TABLE_BUILD_CHUNK = 3u << 16;   // bases per launch = the build kernel's lanes (msm_impl.hip.hpp TABLE_BUILD_BLOCKS x 64)
-int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out, int* c_out, int chunk_budget) {
+int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out, int* c_out, int chunk_budget, bool auto_policy) {
     *out = nullptr;
     *c_out = 0;
     const size_t ps = point_size(h), mp = mont_point_bytes(h->curve);
@@ -232,7 +272,9 @@ int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out
         return fail(BLZ_ERR_INVALID_PARAM, "HBM bases: no loaded extent covers [%llu, +%zu) on device %d",
                     (unsigned long long)pos, len, h->device);
     if (npts == 0) return BLZ_OK;
-    BLZ_TRY(arena_restore_raw(A, *e, h->eng.stream));   // (tables are tabulated from the raw bytes)
+    // (tables are tabulated from the raw bytes.  An unset handle restores them only when it has rows to tabulate: until the
+    // policy builds, its extent is dieted like a plain handle's)
+    if (!auto_policy) BLZ_TRY(arena_restore_raw(A, *e, h->eng.stream));
     const uint32_t phase = (uint32_t)((pos - e->start) % ps);
     const uint64_t first = (pos - e->start - phase) / ps;
     const int fmt = h->eng.format_id();
@@ -241,6 +283,27 @@ int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out
     const int want_c = table_window_bits(npts, need);
     if (want_c == 0) return BLZ_OK;
     ArenaExtent::TableBuild& B = e->build;
+    if (auto_policy) {
+        // evidence of reuse: this launch against the one before it
+        ArenaExtent::Reuse& R = e->reuse;
+        const bool same_task = R.count && R.last_handle == h && R.last_label == h->task_label;
+        R.last_handle = h;
+        R.last_label = h->task_label;
+        if (same_task && R.format == fmt && R.phase == phase && R.first == first && R.npts == npts && R.lo == lo && R.hi == hi && R.epoch == e->epoch) {
+            // (this very task, looked at again)
+        } else if (R.count && R.format == fmt && R.phase == phase && R.first == first && R.npts == npts && R.lo == lo && R.hi == hi && R.epoch == e->epoch) {
+            if (R.count < 0xffffffffu) ++R.count;
+        } else {
+            R.format = fmt;
+            R.phase = phase;
+            R.first = first;
+            R.npts = npts;
+            R.lo = lo;
+            R.hi = hi;
+            R.epoch = e->epoch;
+            R.count = 1;
+        }
+    }
     // the chunks this launch owes the build in flight (chained through B.done: the chunks share the scratch rows)
     auto enqueue_chunks = [&](int budget) -> int {
         hipStream_t st = h->eng.stream;
@@ -299,6 +362,7 @@ int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out
         t.lo = B.lo;
         t.hi = B.hi;
         t.build_ms = ms;
+        t.auto_built = B.auto_built;
         e->tables.push_back(t);
         B.tab = nullptr;
         (void)hipEventDestroy(B.done);
@@ -311,7 +375,14 @@ int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out
     // rows of bases that were rewritten since the tables were built (arena_write: small rewrites keep the tables): re-tabulated
     // here, on this handle's main stream, behind a drain (another handle's task may be gathering from the very rows).  A table
     // of another format than this handle's (its curve's other arithmetic), or one whose scratch rows are gone, is dropped instead.
-    if (e->tab_dirty_lo < e->tab_dirty_hi && !e->tables.empty()) {
+    bool patch_rows = e->tab_dirty_lo < e->tab_dirty_hi && !e->tables.empty();
+    if (patch_rows && auto_policy) {
+        // (an unset handle patches for the tables it is served; tables other handles asked for wait for those handles)
+        patch_rows = false;
+        for (const auto& t : e->tables) patch_rows = patch_rows || t.auto_built;
+        if (patch_rows) BLZ_TRY(arena_restore_raw(A, *e, h->eng.stream));
+    }
+    if (patch_rows) {
         BLZ_TRY(sync_device_bounded("window table: drain before the rewritten bases are re-tabulated"));
         uint32_t* pflag = arena_flag_acquire(A);   // owned for this call (every exit below is behind a drained stream, or leaks the word)
         if (pflag && hipMemsetAsync(pflag, 0, 4, h->eng.stream) != hipSuccess) {
@@ -358,6 +429,9 @@ int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out
     const ArenaExtent::WindowTable* T = nullptr;
     for (const auto& t : e->tables)
         if (t.format == fmt && t.phase == phase && first >= t.first && first + npts <= t.first + t.npts && t.lo == lo && t.hi == hi) T = &t;
+    // (a table some handle asked for is that handle's: an unset handle is not served from it, and the policy builds no second
+    // table of the same bases and range beside it)
+    if (T && auto_policy && !T->auto_built) return BLZ_OK;
     if (T && T->c != want_c) return BLZ_OK;   // a sub-range that wants other windows: the plain path, not a rebuild
     if (!T) {
         // (a refusal - no memory for a table, a base of even order - stops NEW builds until the next write; tables that are
@@ -365,11 +439,14 @@ int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out
         if (B.tab) {
             // a build in flight: this launch pays its share if the build is for this handle's bases and range (one build at a
             // time: another's turn comes when this one is through)
-            if (B.format == fmt && B.phase == phase && first >= B.first && first + npts <= B.first + B.npts && B.lo == lo && B.hi == hi)
-                BLZ_TRY(enqueue_chunks(chunk_budget));
+            // (an unset handle owes a paced build nothing; an auto build has all of its chunks enqueued already)
+            if (B.format == fmt && B.phase == phase && first >= B.first && first + npts <= B.first + B.npts && B.lo == lo && B.hi == hi &&
+                (!auto_policy || B.auto_built))
+                BLZ_TRY(enqueue_chunks(B.auto_built ? -1 : chunk_budget));
             return BLZ_OK;
         }
         if (e->table_refused) return BLZ_OK;
+        if (auto_policy && (npts < (uint32_t)plan_override("auto_table_min", 1 << 24) || e->reuse.count < 2)) return BLZ_OK;
         if (e->tables.size() >= ArenaExtent::MAX_TABLES) {
             BLZ_LOG(1, "window table: the extent already holds %zu tables: plain path for this handle", e->tables.size());
             return BLZ_OK;
@@ -387,6 +464,18 @@ int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out
                     bytes, npts, c, W, free_b);
             e->table_refused = true;
             return BLZ_OK;
+        }
+        if (auto_policy) {
+            // the library's own decision stays within a budget: half of what is free now, or the cap the process set
+            const long long cap_env = plan_override_ll("table_budget_bytes", -1);
+            const size_t cap = cap_env >= 0 ? (size_t)cap_env : free_b / 2;
+            if (bytes > cap) {
+                BLZ_LOG(1, "window table: auto policy: %zu bytes for %u bases exceed the budget (%zu: %s): plain path until the next write", bytes,
+                        npts, cap, cap_env >= 0 ? "table_budget_bytes" : "half of the free device memory");
+                e->table_refused = true;
+                return BLZ_OK;
+            }
+            BLZ_TRY(arena_restore_raw(A, *e, h->eng.stream));   // (a dieted extent: the rows are tabulated from the bytes)
         }
         // the build's scratch rows belong to the arena and are kept (freeing them would wait for every task in flight)
         if (A.build_scratch_bytes < scratch_b) {
@@ -450,9 +539,11 @@ int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out
         B.npts = npts;
         B.next_chunk = 0;
         B.recorded = false;
-        BLZ_LOG(1, "window table: build of %u bases x %d windows of %d bits started (%.1f MiB, %u chunks); tasks take the plain path until it is there",
-                npts, W, c, bytes / 1048576.0, (unsigned)((npts + TABLE_BUILD_CHUNK - 1) / TABLE_BUILD_CHUNK));
-        return enqueue_chunks(chunk_budget);   // (the raw bases are in place: every arena write ends with a host-side wait)
+        B.auto_built = auto_policy;
+        BLZ_LOG(1, "window table: %sbuild of %u bases x %d windows of %d bits started (%.1f MiB, %u chunks); tasks take the plain path until it is there",
+                auto_policy ? "auto policy (second task over the same bases): " : "", npts, W, c, bytes / 1048576.0,
+                (unsigned)((npts + TABLE_BUILD_CHUNK - 1) / TABLE_BUILD_CHUNK));
+        return enqueue_chunks(auto_policy ? -1 : chunk_budget);   // (the raw bases are in place: every arena write ends with a host-side wait)
     }
     *out = (const char*)T->p + (first - T->first) * (size_t)T->W * mp;
     *c_out = T->c;
@@ -467,6 +558,29 @@ int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out
 // "where it pays", leaves it on the plain path)
 bool wants_table(const blz_msm* h) {
     return h->pf == 1 && (h->window_table == 2 || (h->window_table == 1 && h->curve != BLZ_BN254));
+}
+
+// ... and for a task of `npts` bases at arena offset `pos` (msm_stage.hip: pieces against a whole launch): an unset handle under
+// the auto policy is a table handle only while an auto-built table of these bases exists or is being built
+bool wants_table_for(const blz_msm* h, uint64_t pos, uint32_t npts) {
+    if (wants_table(h)) return true;
+    if (!auto_table_handle(h)) return false;
+    Arena& A = arena_for(h->device);
+    std::lock_guard<std::mutex> lk(A.mu);
+    const size_t ps = point_size(h);
+    const ArenaExtent* e = arena_find(A, pos, (size_t)npts * ps);
+    if (!e) return false;
+    const uint32_t phase = (uint32_t)((pos - e->start) % ps);
+    const uint64_t first = (pos - e->start - phase) / ps;
+    const int fmt = h->eng.format_id();
+    const int lo = h->range_hi ? h->range_lo : 0, hi = h->range_hi ? h->range_hi : 256;
+    const ArenaExtent::TableBuild& B = e->build;
+    if (B.tab && B.auto_built && B.format == fmt && B.phase == phase && first >= B.first && first + npts <= B.first + B.npts && B.lo == lo && B.hi == hi)
+        return true;
+    for (const auto& t : e->tables)
+        if (t.auto_built && t.format == fmt && t.phase == phase && first >= t.first && first + npts <= t.first + t.npts && t.lo == lo && t.hi == hi)
+            return true;
+    return false;
 }
 
 // BN254 has two arithmetics (msm_engine.hpp `repr`): the 9 x 29-bit reduced radix wins while the accumulation is bound by its
@@ -531,11 +645,15 @@ int resolve_arena_task(blz_msm* h, uint64_t pos, uint32_t n, bool allow_table, b
     } else {
         task_repr_bn254pc(h, false, 0);   // (a precompute handle off the plan: mode iii, the plan switched off)
     }
-    if (allow_table && wants_table(h)) {
+    // (the auto policy counts every scalars-only task of an unset handle - a task enqueued in pieces, allow_table false, is evidence
+    // of reuse and may start the build like any other; it just never gathers from a table)
+    const bool auto_policy = allow_plan && auto_table_handle(h);
+    if ((allow_table && wants_table(h)) || auto_policy) {
         const void* tab = nullptr;
-        BLZ_TRY(arena_points_table(h, pos, *npts, &tab, table_c, TABLE_CHUNKS_PER_TASK));
-        if (tab) *pts = tab;
+        BLZ_TRY(arena_points_table(h, pos, *npts, &tab, table_c, TABLE_CHUNKS_PER_TASK, auto_policy));
+        if (tab && allow_table) *pts = tab;
         else *table_c = 0;
+        if (!*table_c) memset(h->table_info, 0, sizeof(h->table_info));
     }
     if (!*table_c) BLZ_TRY(arena_points_mont(h, pos, *npts, pts));
     return BLZ_OK;

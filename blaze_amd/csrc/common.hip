@@ -64,6 +64,18 @@ int plan_override(const char* key, int dflt) {
     return dflt;
 }
 
+long long plan_override_ll(const char* key, long long dflt) {
+    const char* s = getenv("BLAZE_MSM_PLAN");
+    if (!s || !*s) return dflt;
+    const size_t kl = strlen(key);
+    for (const char* p = s; *p;) {
+        while (*p == ',' || *p == ' ') ++p;
+        if (strncmp(p, key, kl) == 0 && p[kl] == '=') return atoll(p + kl + 1);
+        while (*p && *p != ',') ++p;
+    }
+    return dflt;
+}
+
 int wait_timeout_ms() {
     const char* s = getenv("BLAZE_WAIT_TIMEOUT_MS");
     int v = s && *s ? atoi(s) : 120000;
@@ -164,6 +176,11 @@ int DevBuf::reserve(size_t bytes, bool exact) {
     if (e != hipSuccess) {
         e = hipMalloc(&p, bytes);
         want = bytes;
+    }
+    if (e != hipSuccess) {
+        // a full device: the auto-built window tables are the memory the library took on its own account - given back, once
+        (void)hipGetLastError();
+        if (release_auto_tables_on_oom() > 0) e = hipMalloc(&p, bytes);
     }
     if (e != hipSuccess) {
         p = nullptr;

@@ -81,8 +81,11 @@ inline int exp_knob(const char*, int dflt) { return dflt; }
 #endif
 // BLAZE_MSM_PLAN="c=13,L=64,split_ns=0,table_c=26": overrides of the window planner for tests and sweeps (c: uniform window
 // width; L: unit length; split_ns: the planner's price of a split top window - 0 lets mixed widths appear at sizes the
-// oracle can check; table_c: window width of window tables).  Absent keys keep the planner's own choice.
+// oracle can check; table_c: window width of window tables).  Absent keys keep the planner's own choice.  The auto policy of the
+// window tables (arena_tables.hip) is steered through the same switch: auto_table=0 switches it off for the process,
+// auto_table_min=N is the least number of bases it tabulates, table_budget_bytes=N caps the bytes of a table it may build.
 int plan_override(const char* key, int dflt);
+long long plan_override_ll(const char* key, long long dflt);
 
 // number of usable devices, 0 if the runtime cannot see any
 int device_count();
@@ -143,7 +146,7 @@ struct ArenaExtent {
     uint64_t dirty_lo = 0, dirty_hi = 0;   // byte span (relative to start) whose points are stale in the shadow
     hipEvent_t shadow_ready = nullptr;     // recorded after the last conversion; consumers on other streams wait
     bool shadow_recorded = false;          // shadow_ready has been recorded at least once since the shadow was (re)built
-    // window tables (msm_impl.hip.hpp k_build_window_table; opt-in per handle): for the points [first, +npts) of the grid at `phase`
+    // window tables (msm_impl.hip.hpp k_build_window_table; per handle opt-in, or the auto policy): for the points [first, +npts) of the grid at `phase`
     // the W multiples 2^(lo + c j) P, j < W, in the shadow's point format, point-major.  One per (bases, scalar range) that
     // a handle asked for - the ranks of a job sharded by scalar chunk each tabulate their own range - at most
     // MAX_TABLES per extent.  A write of up to TABLE_PATCH_MAX_POINTS bases has their rows re-tabulated by the next task; a
@@ -156,6 +159,7 @@ struct ArenaExtent {
         uint32_t phase = 0;
         uint64_t first = 0, npts = 0;
         float build_ms = 0;
+        bool auto_built = false;           // built by the auto policy: served to handles that left the mode unset, released under memory pressure
     };
     static constexpr size_t MAX_TABLES = 32;
     static constexpr uint64_t TABLE_PATCH_MAX_POINTS = 1u << 18;
@@ -196,7 +200,19 @@ struct ArenaExtent {
         uint64_t first = 0, npts = 0;
         uint64_t next_chunk = 0;           // chunks [0, next_chunk) have been enqueued
         bool recorded = false;             // `done` has been recorded behind the last enqueued chunk
+        bool auto_built = false;           // started by the auto policy (all chunks enqueued at once)
     } build;
+    // Evidence of reuse for the auto policy (arena_tables.hip arena_points_table): the last scalars-only task a handle with the
+    // table mode unset launched over this extent, and how many such tasks in a row were over the identical bases, scalar range
+    // and format with no write in between (epoch).  The second one starts the build.
+    struct Reuse {
+        int format = -1, lo = 0, hi = 256;
+        uint32_t phase = 0;
+        uint64_t first = 0, npts = 0, epoch = 0;
+        uint32_t count = 0;
+        const void* last_handle = nullptr;   // the task counted last (a task is resolved twice when it is opened for pieces and then
+        uint32_t last_label = 0;             // launched whole: counted once)
+    } reuse;
 };
 struct Arena {
     std::mutex mu;
@@ -230,5 +246,14 @@ int arena_diet_step(Arena& a, ArenaExtent& e, size_t point_bytes, hipStream_t st
 int arena_read_bytes(Arena& a, ArenaExtent& e, uint64_t off, size_t len, void* out, hipStream_t st);
 void arena_drop_table(Arena& a, ArenaExtent& x);   // the tables and a build in flight; the caller has drained the device
 void arena_drop_build(Arena& a, ArenaExtent& x);   // a build in flight only
+// Memory pressure: a hipMalloc of the library's own failed.  The auto-built window tables of the device (and an auto build in
+// flight) go - behind a bounded drain - and their extents refuse new builds until their next write; tables a handle asked for
+// (blz_msm_set_window_table 1 | 2) are the caller's decision and stay.  Returns the bytes freed (0: nothing to give back, or
+// the drain ran into its deadline); the caller retries its allocation once.  A table the calling thread is about to launch a
+// task over (table_pin) is passed over, and table_pin_skipped() says so.
+size_t arena_release_auto_tables(Arena& a);          // the caller holds a.mu
+size_t release_auto_tables_on_oom();                 // the current device's arena, locked here (never called under an arena lock)
+void table_pin(const void* table_rows);              // this thread's launch gathers from these rows (nullptr: none)
+bool table_pin_skipped();                            // a release since the last table_pin() passed the pinned table over
 
 }  // namespace blz

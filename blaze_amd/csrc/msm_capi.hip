@@ -20,7 +20,7 @@ int blz_msm_new(int device_id, int mem_type, int is_precompute, int curve, blz_m
     h->mem_type = mem_type;
     h->pf = is_precompute ? BLZ_PRECOMPUTE_FACTOR : BLZ_PRECOMPUTE_FACTOR_BASE;
     h->curve = curve;
-    h->window_table = 0;   // opt-in: blz_msm_set_window_table
+    h->window_table = -1;   // unset: the auto policy (arena_tables.hip); blz_msm_set_window_table makes it explicit
     int rc = h->eng.init(device_id, curve, (int)h->pf);
     if (rc == BLZ_OK && hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) != hipSuccess)
         rc = fail_hip(BLZ_ERR_UNKNOWN, "copy stream creation failed");

@@ -78,8 +78,8 @@ struct blz_msm {
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_size = 0;
     blz::DevBuf comm_buf;   // [send: one partial | recv: comm_size partials]
-    // resident-base window table (blz_msm_set_window_table; off for new handles)
-    int window_table = 0;   // 0 off, 1 where it pays (the BLS curves), 2 always
+    // resident-base window table (blz_msm_set_window_table; new handles leave it unset: the auto policy of arena_tables.hip)
+    int window_table = -1;   // -1 unset (auto), 0 off, 1 where it pays (the BLS curves), 2 always
     // scalar range of this handle's tasks (blz_msm_set_scalar_range): bits [range_lo, range_hi) of every scalar; 0, 0 = all
     int range_lo = 0, range_hi = 0;
     uint64_t table_info[4] = {0, 0, 0, 0};   // of the last HBM task: table bytes, window bits, windows, build time (us)
@@ -124,11 +124,13 @@ inline bool busy(const blz_msm* h) { return !h->in_flight.empty() || h->feed.slo
 constexpr int TABLE_CHUNKS_PER_TASK = 4;           // ~22 ms on top of a 2^26 task's 117: 86 tasks until a 2^26 table is there
 bool wants_table_mode(const blz_msm* h);
 bool wants_table(const blz_msm* h);
+bool auto_table_handle(const blz_msm* h);   // the mode is unset and the auto policy applies to this handle
+bool wants_table_for(const blz_msm* h, uint64_t pos, uint32_t npts);   // ... or an auto-built table of these bases exists / is being built
 int plan_repr_bn254(uint64_t nelem);
 void task_repr_bn254pc(blz_msm* h, bool on_plan, uint64_t checked_elems);   // the arithmetic of a BN254 precompute handle's next task
 int arena_points_mont(blz_msm* h, uint64_t pos, uint32_t npts, const void** out, bool even = false);
 int arena_precompute_check(blz_msm* h, uint64_t pos, uint32_t nelem, bool* ok, uint64_t* checked_elems = nullptr);
-int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out, int* c_out, int chunk_budget);
+int arena_points_table(blz_msm* h, uint64_t pos, uint32_t npts, const void** out, int* c_out, int chunk_budget, bool auto_policy = false);
 int resolve_arena_task(blz_msm* h, uint64_t pos, uint32_t n, bool allow_table, bool allow_plan, uint32_t* npts, int* sbits, int* table_c,
                        const void** pts);
 // ---- msm_stage.hip

@@ -51,9 +51,20 @@ int launch_if_ready(blz_msm* h) {
     memset(h->pc_info, 0, sizeof(h->pc_info));
     // (a task that has just loaded its own table - mode 3, msm_api.rs:203-216 - is a DMA-mode task as far as the plan is
     // concerned: a check per task would cost more than it saves)
-    if (F.mode != 2) BLZ_TRY(resolve_arena_task(h, F.arena_pos, F.n, true, F.mode == 1, &npts, &sbits, &table_c, &pts));
-    h->eng.inputs_event = F.set >= 0 ? h->set_free[F.set] : nullptr;
-    BLZ_TRY(h->eng.run(pts, F.d_scalars, npts, sbits, &slot, table_c, h->range_lo, h->range_hi));
+    // A task that gathers from an auto-built window table pins it for the launch: an allocation of the launch that fails releases
+    // the device's auto-built tables (arena.hip arena_release_auto_tables) - but not the rows this very task is about to read.  If
+    // that was the memory the launch lacked, the table goes here, behind the failed launch, and the task is launched once more on
+    // the plain path.
+    for (int attempt = 0;; ++attempt) {
+        if (F.mode != 2) BLZ_TRY(resolve_arena_task(h, F.arena_pos, F.n, true, F.mode == 1, &npts, &sbits, &table_c, &pts));
+        h->eng.inputs_event = F.set >= 0 ? h->set_free[F.set] : nullptr;
+        table_pin(table_c ? pts : nullptr);
+        const int rc = h->eng.run(pts, F.d_scalars, npts, sbits, &slot, table_c, h->range_lo, h->range_hi);
+        const bool skipped = table_pin_skipped();
+        table_pin(nullptr);
+        if (rc == BLZ_OK) break;
+        if (!(attempt == 0 && skipped && !wait_timed_out() && release_auto_tables_on_oom() > 0)) return rc;
+    }
     return task_enqueued(h, slot);
 }
 
@@ -202,7 +213,7 @@ static int open_pieces(blz_msm* h, bool one_call) {
     int sbits = h->pf == 1 ? 256 : 32;
     const void* mont = nullptr;
     if (F.mode != 2) {
-        if (!(npts >= (1u << 22) || env_int("BLAZE_MSM_PIECES", 0) > 1) || busy(h) || wants_table(h)) return BLZ_OK;
+        if (!(npts >= (1u << 22) || env_int("BLAZE_MSM_PIECES", 0) > 1) || busy(h) || wants_table_for(h, F.arena_pos, npts)) return BLZ_OK;
         // (stale spans are converted on the main stream; a precompute handle on the checked-table plan: 4n even bases, 64-bit chunks)
         int tc = 0;
         BLZ_TRY(resolve_arena_task(h, F.arena_pos, F.n, false, F.mode == 1, &npts, &sbits, &tc, &mont));

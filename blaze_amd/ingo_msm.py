@@ -241,9 +241,12 @@ class MSMClient(DriverPrimitive[MSMInit, MSMParams, MSMInput, MSMResult]):
         return out.raw
 
     def set_window_table(self, enable) -> None:
-        """Opt in to the resident-base window table (include/blaze_hip.h blz_msm_set_window_table): pf = 1 handles whose
+        """The resident-base window table (include/blaze_hip.h blz_msm_set_window_table): pf = 1 handles whose
         bases live in the arena; built beside the tasks (prepare_window_table), W x the memory of the bases, fewer bucket additions.
-        False / 0 off, True / 1 where it pays (the BLS curves), 2 always."""
+        False / 0 off, True / 1 where it pays (the BLS curves), 2 always.  A client that never calls this is decided for by the
+        library: from the second task in a row over the same >= 2^24 resident BLS bases the table is built at once (one late
+        result), within half of the free device memory, and released again under memory pressure; 0 switches that off for
+        this client, BLAZE_MSM_PLAN=auto_table=0 for the process."""
         check(lib().blz_msm_set_window_table(self._h, int(enable)))
 
     def prepare_window_table(self, nof_elements: int, hbm_addr=(0, 0), wait_ms: int = -1) -> bool:

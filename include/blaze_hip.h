@@ -221,7 +221,17 @@ int blz_msm_plan(int curve, uint32_t nof_elements, int is_precompute, uint32_t o
  * the table does not fit the free memory, when a base has even order (a multiple at infinity cannot be tabulated;
  * never the case in the r-torsion), or for a task over a sub-range that wants a different window width.
  * A handle with a scalar range (blz_msm_set_scalar_range) tabulates 2^(bit_lo + c j) P for the windows of its range.
- * New handles start with 0 (off).  No other value of `enable` is accepted (InvalidPrimitiveParam). */
+ * New handles start UNSET, which is neither of the three: the library decides (the auto policy).  An unset pf = 1 handle of
+ * PointMemoryType HBM on a BLS curve gets the table of its resident bases when a task of at least 2^24 bases is the second
+ * scalars-only task in a row over the identical bases and scalar range with no write in between, and the table takes at most
+ * half of the device memory free at that moment.  That build is not paced: all of it is enqueued at once on the handle's stream
+ * ahead of the triggering task (2.3 s of the chip for 2^26 bases: one late result; the host call does not wait), and the first
+ * task launched after it has completed adopts the table.  A table built this way is given back when an allocation of the
+ * library fails for lack of device memory (the extent then stays on the plain path until its next write); tables built under 1
+ * or 2 are the caller's decision and stay.  Calling this function with 0 is an explicit off; 1 and 2 keep their meaning and
+ * their paced build.  BLAZE_MSM_PLAN keys steer the policy: auto_table=0 switches it off for the process, auto_table_min=N sets
+ * the least number of bases, table_budget_bytes=N replaces the half-of-free rule by an absolute cap.
+ * No other value of `enable` is accepted (InvalidPrimitiveParam). */
 int blz_msm_set_window_table(blz_msm* h, int enable);
 /* The table's build is never one lump inside a task: it is cut into chunks of 196 608 bases (~5.5 ms of the chip), every task
  * launched over the bases first enqueues four of them on its own stream and takes the plain path, like every task until the
